@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """bench.py — stylized frames/sec of the UniVST SD-v1.5 three-branch denoising loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N>1: one rank per GPU — launched by torch.distributed.run, or,
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                   (N>1: one rank per GPU — launched by torch.distributed.run, or,
                                                                     when no launcher environment is present, re-executed under it)
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  --full adds what the headline does not need:
+the per-kernel-class event pass (`roofline`, `kernel_classes_ms`), the skip-dead-branches leg (config.extra_skip_dead_branches_*)
+and the CPU baseline (`cpu_baseline`).  --dump-outputs DIR writes what the timed path returned in its last step (the latents; the
+decoded frames / masks of the other workloads) as DIR/<name>.npy; the inputs are seeded, so runs with the same arguments compare.
 
 Workload (BASELINE.json metric): SD-v1.5 geometry UNet (random-init synthetic weights of that architecture,
 fp16), 16 frames x 512x512 (latents [1,4,16,64,64]), 50 DDIM steps of the three-branch transfer loop
@@ -63,9 +69,15 @@ def parse():
     ap.add_argument("--workload", default="transfer", choices=["transfer", "transfer_nomask", "inversion", "inversion_pair", "maskprop", "warp", "sd3_transfer", "vae_decode"])
     ap.add_argument("--model", default="sd15", choices=["sd15", "sd21"], help="UNet configuration: SD-v1.5 (headline) or the SD-v2.1 layout "
                                                                             "(Linear projections, head_dim 64, 1024-wide text states; SURVEY §8f-3)")
-    ap.add_argument("--full-cpu", action="store_true", help="cpu_baseline: time the two representative steps at the full frame count "
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-kernel-class event pass (roofline), the skip-dead-branches "
+                         "leg and the CPU baseline (each can still be dropped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; "
+                         "a fixed, seeded sample of the elements above 64 MB in all)")
+    ap.add_argument("--full-cpu", action="store_true", help="with --full, cpu_baseline: time the two representative steps at the full frame count "
                                                              "(no extrapolation in F; ~2 min on 16 threads); default: one step at the full count")
-    ap.add_argument("--quick-cpu", action="store_true", help="cpu_baseline: the F=2 sample of rounds 1-3 (14 s, extrapolated x8 in F)")
+    ap.add_argument("--quick-cpu", action="store_true", help="with --full, cpu_baseline: the F=2 sample of rounds 1-3 (14 s, extrapolated x8 in F)")
     ap.add_argument("--selftest-launch", action="store_true", help="multi-rank plumbing only (rendezvous, barriers, MAX over ranks, one JSON "
                                                                     "line); no GPU work, runs on a CPU box with --backend gloo")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -74,7 +86,10 @@ def parse():
     ap.add_argument("--no-skip-dead-branches-leg", action="store_true",
                     help="do not also time the variant that drops branches 0/1 after the PnP window (identical output; reported "
                          "separately in config, never as `value`)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if (a.full_cpu or a.quick_cpu) and not a.full:
+        ap.error("--full-cpu / --quick-cpu choose how the CPU baseline of --full is measured: add --full")
+    return a
 
 
 class Pipe:
@@ -101,6 +116,31 @@ def make_step_fn(pipe, content, style, text3, mask_m, n=50):
         eps = pipe.unet(x, t, encoder_hidden_states=text3).sample[2:3]
         return engine.ddim_step(pipe.scheduler, eps, t, latents)
     return step
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(a, arrays, dist=None, frame_dim=0):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, one DIR/<name>.npy each in float32, so that two builds
+    can be compared output for output.  A frame shard gathers its ranks' frames along `frame_dim` first (rank 0 writes what one GPU
+    would).  Above DUMP_BYTES in all, every array keeps the same share of its elements, drawn with a fixed seed (flat indices, sorted)."""
+    import numpy as np
+    arrays = {k: (v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float32)) for k, v in arrays.items()}
+    if dist is not None:
+        for k, v in arrays.items():
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, v)
+            arrays[k] = np.concatenate(parts, axis=frame_dim)
+        if dist.get_rank() != 0:
+            return
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    total = sum(v.size * 4 for v in arrays.values())
+    for k, v in arrays.items():
+        if total > DUMP_BYTES:
+            idx = np.unique(np.random.default_rng(0).integers(0, v.size, v.size * DUMP_BYTES // total))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(a.dump_outputs, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def usable_cores():
@@ -217,7 +257,7 @@ def run_vae_workload(a, dev):
     F_, h = a.frames, (a.latent or 64)
     cfg = synth.SVD_VAE_CONFIG
     v = vae.NativeTemporalVAE(synth.vae_state_dict(cfg, device=dev), cfg, device=dev)
-    z = torch.randn(F_, 4, h, h, device=dev, dtype=torch.float16)
+    z = torch.randn(F_, 4, h, h, generator=torch.Generator(device=dev).manual_seed(3), device=dev, dtype=torch.float16)
     for _ in range(max(1, a.warmup)):
         v.decode(z, num_frames=F_)
     torch.cuda.synchronize()
@@ -233,6 +273,8 @@ def run_vae_workload(a, dev):
     dev_ms = ev0.elapsed_time(ev1) / reps
     fl = vae_decode_flops(cfg, F_, F_, h, h)
     assert torch.isfinite(out.float()).all()
+    if a.dump_outputs:
+        dump_outputs(a, {"frames": out})
     return {"metric": f"decoded frames/sec, SVD temporal VAE decoder, {F_}x{h * 8}x{h * 8}", "value": round(F_ / wall, 3), "unit": "frames/s", "n_gpus": 1,
             "steps": reps, "warmup": max(1, a.warmup), "ms_per_step": round(wall * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f16", "data": "synthetic",
@@ -291,11 +333,13 @@ def run_aux_workload(a, dev):
     ev0.record()
     t0 = time.perf_counter()
     for _ in range(reps):
-        once()
+        res = once()
     ev1.record()
     torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) / reps
     dev_ms = ev0.elapsed_time(ev1) / reps
+    if a.dump_outputs:
+        dump_outputs(a, {"masks" if a.workload == "maskprop" else "frames": res})
     out = {"metric": f"{unit_desc}/sec, {F_}-frame clip at 512x512 ({a.workload})", "value": round(units / wall, 3), "unit": "frames/s",
            "n_gpus": 1, "steps": reps, "warmup": max(1, a.warmup), "ms_per_step": round(wall * 1e3, 3), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32" if a.workload == "maskprop" else "u8", "data": "synthetic",
@@ -419,6 +463,8 @@ def run_sd3_workload(a, dev, rank=0, world=1, dist=None):
         dist.all_gather_object(outs, ms)
         ms = max(outs)
     assert torch.isfinite(lat.float()).all(), "non-finite latents"
+    if a.dump_outputs:
+        dump_outputs(a, {"latents": lat}, dist)
     N = (hl // 2) ** 2
     F_ = F_all
     fl = sd3_step_flops(model.config, 3 * F_, N, T)
@@ -436,7 +482,7 @@ def run_sd3_workload(a, dev, rank=0, world=1, dist=None):
     tf = fl / (ms * 1e-3) / 1e12 / (emu[1] if emu else world)
     out["roofline"] = {"bound": "mfma", "kernel": "whole step (linears + joint attention), per GPU", "achieved": round(tf, 1), "peak": PEAK_FP16_TFLOPS,
                        "unit": "TFLOP/s", "frac": round(tf / PEAK_FP16_TFLOPS, 4), "traffic": None, "algorithmic_tflop_per_step": round(fl / 1e12, 2)}
-    if not a.no_profile and world == 1:
+    if a.full and not a.no_profile and world == 1:
         _native.profile_enable(True)
         lat2 = step(idx[0], lat)
         torch.cuda.synchronize()
@@ -637,6 +683,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     assert torch.isfinite(lat.float()).all(), "non-finite latents"
+    if a.dump_outputs:
+        dump_outputs(a, {"latents": lat}, dist, frame_dim=2)
     ms_per_step = dt / a.steps * 1e3
     value = F_total * (2 if a.workload == "inversion_pair" else 1) / (50 * ms_per_step / 1e3)
 
@@ -657,17 +705,18 @@ def main():
                                "random-init SD-v1.5 architecture (859M + 201M temporal params), fp16")},
     }
 
-    if rank == 0 and not a.no_profile:
+    profile = a.full and not a.no_profile
+    if rank == 0 and profile:
         # roofline leg: per-kernel-class HIP-event timing over a second pass of the same steps (events bracket every
         # launch on its stream; kept out of the timed region so the event overhead does not perturb `value`)
         _native.profile_enable(True)
-    if not a.no_profile:
+    if profile:
         nprof = min(a.steps, 50)
         l2 = lat
         for i in idx[:nprof]:
             l2 = step(i, l2)
         sync()
-    if rank == 0 and not a.no_profile:
+    if rank == 0 and profile:
         prof = _native.profile_collect()
         launched = _native.profile_symbols()
         _native.profile_enable(False)
@@ -729,7 +778,7 @@ def main():
         out["config"]["algorithmic_tflop_per_step_executed"] = round(tot_flops / 1e12, 2)
         out["roofline"]["whole_step_tflops"] = round(tot_flops / (ms_per_step * 1e-3) / 1e12, 1)
 
-    if not a.no_skip_dead_branches_leg and world == 1 and emu is None and a.steps >= 50 and not inv:
+    if a.full and not a.no_skip_dead_branches_leg and world == 1 and emu is None and a.steps >= 50 and not inv:
         from univst_amd import engine
         sync()
         t0 = time.perf_counter()
@@ -741,7 +790,7 @@ def main():
                                                           "same latents up to fp32 summation order (tests: >= 60 dB), 102 instead of 150 branch-steps; NOT the headline value")
 
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1 and emu is None and a.model == "sd15":
+        if a.full and not a.no_cpu_baseline and world == 1 and emu is None and a.model == "sd15":
             out["cpu_baseline"] = cpu_baseline(F_total, unet, full=a.full_cpu, single_branch=inv, quick=a.quick_cpu)
         print(json.dumps(out))
     if dist is not None:

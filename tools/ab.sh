@@ -23,10 +23,10 @@ if [ -n "$TESTS" ]; then
   echo "pytest rc=$?"; tail -3 $D/tests.log
 fi
 for i in $(seq 1 $REPS); do for v in "${VALS[@]}"; do
-  env $VAR=$v python bench.py $BENCH --no-cpu-baseline --no-skip-dead-branches-leg > $D/${VAR}_${v//\//_}_$i.json 2>> $D/bench.err
+  env $VAR=$v python bench.py $BENCH --full --no-cpu-baseline --no-skip-dead-branches-leg > $D/${VAR}_${v//\//_}_$i.json 2>> $D/bench.err
 done; done
 if [ -n "$EMU" ]; then for v in "${VALS[@]}"; do
-  env $VAR=$v python bench.py $BENCH --no-cpu-baseline --emulate-rank $EMU > $D/${VAR}_${v//\//_}_emu.json 2>> $D/bench.err
+  env $VAR=$v python bench.py $BENCH --full --no-cpu-baseline --emulate-rank $EMU > $D/${VAR}_${v//\//_}_emu.json 2>> $D/bench.err
 done; fi
 python - $D <<'PY'
 import collections, glob, json, os, sys

@@ -1,4 +1,4 @@
-"""stdin: the JSON line of bench.py -> fps, ms/step and the per-kernel-class split."""
+"""stdin: the JSON line of bench.py --full -> fps, ms/step and the per-kernel-class split."""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d["value"], "frames/s", d["ms_per_step"], "ms/step")

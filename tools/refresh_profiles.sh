@@ -9,24 +9,24 @@ ROUND=${ROUND:-6}
 O=$R/gpurun_out/profiles_new
 rm -rf $O && mkdir -p $O/raw
 cd $R
-python bench.py > $O/round${ROUND}_bench_n1.json 2> $O/raw/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw/stats -- python bench.py --no-cpu-baseline --no-skip-dead-branches-leg > $O/round${ROUND}_bench_under_rocprof.json 2> $O/raw/stats.err
+python bench.py --full > $O/round${ROUND}_bench_n1.json 2> $O/raw/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw/stats -- python bench.py --full --no-cpu-baseline --no-skip-dead-branches-leg > $O/round${ROUND}_bench_under_rocprof.json 2> $O/raw/stats.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/raw/fetch -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile > $O/raw/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/raw/write -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile > $O/raw/write.log 2>&1
 bash tools/pmc_attn.sh $O/raw/attn > $O/round${ROUND}_pmc_attn_d40_sq.txt 2>&1
 bash tools/pmc_gemm.sh $O/raw/gemm convp 2>&1 | grep -E "^SQ_" > $O/round${ROUND}_pmc_conv_patch_sq.txt
 # the dominant class by shape: the K = 320 GEGLU projection (fixed-cost bound) and a long-K linear of the same kernel
 for w in ff1 l2qkv ff2; do echo "== $w"; bash tools/pmc_gemm.sh $O/raw/gemm_$w $w 2>&1 | grep -E "^SQ_"; done > $O/round${ROUND}_pmc_gemm_big_sq_raw.txt
-for w in inversion inversion_pair transfer_nomask maskprop warp; do python bench.py --workload $w --no-cpu-baseline > $O/round${ROUND}_bench_$w.json 2>> $O/raw/bench.err; done
-python bench.py --frames 32 --emulate-rank 0/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank0of8.json 2>> $O/raw/bench.err
-python bench.py --frames 32 --emulate-rank 1/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank1of8.json 2>> $O/raw/bench.err
-python bench.py --frames 32 --emulate-rank 7/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank7of8.json 2>> $O/raw/bench.err
-python bench.py --emulate-rank 1/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f16_rank1of8.json 2>> $O/raw/bench.err
+for w in inversion inversion_pair transfer_nomask maskprop warp; do python bench.py --full --workload $w --no-cpu-baseline > $O/round${ROUND}_bench_$w.json 2>> $O/raw/bench.err; done
+python bench.py --full --frames 32 --emulate-rank 0/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank0of8.json 2>> $O/raw/bench.err
+python bench.py --full --frames 32 --emulate-rank 1/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank1of8.json 2>> $O/raw/bench.err
+python bench.py --full --frames 32 --emulate-rank 7/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank7of8.json 2>> $O/raw/bench.err
+python bench.py --full --emulate-rank 1/8 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f16_rank1of8.json 2>> $O/raw/bench.err
 # the same ranks with the wire modelled at 64 GB/s per link.  Round 6: the delay sits on the FORKED stream the multicast really runs on (unet.hip kv_post) and the
 # forward's stream spins on a self-raised flag; _serial = the same packs issued on the forward's own stream (UNIVST_KV_OVERLAP=0: round 5's order), _inf = a wire that
 # costs nothing (what the fork / flag machinery itself costs)
-python bench.py --emulate-rank 1/8 --emulate-wire 64 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f16_rank1of8_wire64.json 2>> $O/raw/bench.err
-python bench.py --frames 32 --emulate-rank 1/8 --emulate-wire 64 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank1of8_wire64.json 2>> $O/raw/bench.err
+python bench.py --full --emulate-rank 1/8 --emulate-wire 64 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f16_rank1of8_wire64.json 2>> $O/raw/bench.err
+python bench.py --full --frames 32 --emulate-rank 1/8 --emulate-wire 64 --no-cpu-baseline > $O/round${ROUND}_bench_emulated_f32_rank1of8_wire64.json 2>> $O/raw/bench.err
 python bench.py --frames 32 --emulate-rank 4/8 --emulate-wire 64 --no-cpu-baseline --no-profile > $O/round${ROUND}_bench_emulated_f32_rank4of8_wire64.json 2>> $O/raw/bench.err
 UNIVST_KV_OVERLAP=0 python bench.py --emulate-rank 1/8 --emulate-wire 64 --no-cpu-baseline --no-profile > $O/round${ROUND}_bench_emulated_f16_rank1of8_wire64_serial.json 2>> $O/raw/bench.err
 UNIVST_KV_OVERLAP=0 python bench.py --frames 32 --emulate-rank 1/8 --emulate-wire 64 --no-cpu-baseline --no-profile > $O/round${ROUND}_bench_emulated_f32_rank1of8_wire64_serial.json 2>> $O/raw/bench.err
@@ -55,10 +55,10 @@ print(f"rank 1 of 8 emulated (F = 16, no wire), under rocprofv3: {b['ms_per_step
       f"kernel-time sum {tot:.1f} ms over {calls} launches in ~{steps} steps = {tot / steps:.2f} ms and {calls / steps:.0f} launches per step")
 PY
 python bench.py --workload sd3_transfer --emulate-rank 0/8 --steps 5 --warmup 1 --no-profile > $O/round${ROUND}_bench_sd3_emulated_rank0of8.json 2>> $O/raw/bench.err
-python bench.py --frames 32 --no-cpu-baseline --no-skip-dead-branches-leg > $O/round${ROUND}_bench_f32_n1.json 2>> $O/raw/bench.err
-python bench.py --model sd21 --no-cpu-baseline > $O/round${ROUND}_bench_sd21_n1.json 2>> $O/raw/bench.err
-[ "${FULLCPU:-1}" = 1 ] && python bench.py --full-cpu --no-profile --no-skip-dead-branches-leg > $O/round${ROUND}_bench_fullcpu.json 2>> $O/raw/bench.err
-python bench.py --workload sd3_transfer --steps 5 --warmup 1 > $O/round${ROUND}_bench_sd3_transfer.json 2>> $O/raw/bench.err
+python bench.py --full --frames 32 --no-cpu-baseline --no-skip-dead-branches-leg > $O/round${ROUND}_bench_f32_n1.json 2>> $O/raw/bench.err
+python bench.py --full --model sd21 --no-cpu-baseline > $O/round${ROUND}_bench_sd21_n1.json 2>> $O/raw/bench.err
+[ "${FULLCPU:-1}" = 1 ] && python bench.py --full --full-cpu --no-profile --no-skip-dead-branches-leg > $O/round${ROUND}_bench_fullcpu.json 2>> $O/raw/bench.err
+python bench.py --full --workload sd3_transfer --steps 5 --warmup 1 > $O/round${ROUND}_bench_sd3_transfer.json 2>> $O/raw/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw/stats_sd3 -- python bench.py --workload sd3_transfer --steps 3 --warmup 1 --no-profile > $O/raw/sd3_rocprof.log 2>&1
 cp $(ls $O/raw/stats_sd3/*/*kernel_stats.csv | head -1) $O/round${ROUND}_kernel_stats_sd3_transfer.csv
 # two ranks on this ONE GPU through the library's IPC communicator: evidence that the multi-rank path executes end to end (not a scaling number)

@@ -136,7 +136,7 @@ int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm);
  *             experiment kept as a switch: -13 % on the isolated chain (tools/bench_mall_bands.py), +0.4 ms per step in the graph.
  *   "gn_fold" (default 1, env UNIVST_GN_FOLD): the per-frame GroupNorm in front of a transformer block (attention.py:121) is folded into proj_in as per-frame
  *             weight sets + an fp32 bias where the copies are cheap against the apply pass they replace (the 64x64 level); 0: always the apply pass.
- *   "attn2_fused" (default 2, env UNIVST_ATTN2_FUSED=0 disables it library-wide): the text cross-attention of a transformer block (attention.py:321-327)
+ *   "attn2_fused" (default 2, env UNIVST_ATTN2_PRE=0 -> 1): the text cross-attention of a transformer block (attention.py:321-327)
  *             as one launch (univst_attn2_fused) where the level's shape is served, instead of q projection + attention + out projection; 2 (default): with the
  *             self-attention's out projection + residual in front of it (univst_attn12_fused), 1: attn2 alone, 0: off.
  *   "kv_overlap" (default 1, env UNIVST_KV_OVERLAP; round 6): the frame shard's K/V exchange of a transformer block (attention.py:384-413 across GPUs)

@@ -2,7 +2,8 @@
 # ONE parameterised A/B driver (round 5; replaces the 28 one-off tools/ab/ab*.sh of round 4, which are in the git history).  Boxes of the pool differ by
 # +-4 %, so every comparison alternates the variants INSIDE one gpurun call:
 #   gpurun --timeout 1800 -- 'bash tools/ab.sh VAR=a,b[,c] [REPS=2] [TESTS="-k expr" | TESTS=all] [BENCH="--steps 20 --warmup 3 ..."] [EMU=1/8] [OUT=name]'
-#     VAR=a,b     environment switch and its values (e.g. UNIVST_ATTN2_FUSED=0,1); "UNIVST_LIB=path1,path2" compares two builds of the library
+#     VAR=a,b     environment variable and its values: "UNIVST_LIB=path1,path2" compares two builds of the library; a handle option's
+#                 environment seed works too (e.g. UNIVST_LN_FOLD=1,2)
 #     TESTS       a pytest selection run first (correctness before timing); all = the whole GPU suite
 #     EMU=r/w     additionally one emulated-rank line per variant
 # Prints per run: ms per step and the per-class split (classes above 0.3 ms), then the mean per variant.

@@ -1,4 +1,5 @@
-"""mid-size linears / convs around the big-tile threshold (A/B aid: UNIVST_GEMM_BIGMIN, UNIVST_GEMM_SPLITK)."""
+"""mid-size linears / convs around the big-tile threshold (gemm.hip BIG_MIN_TILES) and the split-K choice; compare thresholds as two
+builds of the library (tools/ab.sh UNIVST_LIB=a,b)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.bench_gemm import lin, conv_ti

@@ -407,7 +407,7 @@ class Sd3AttnParams(dict):
     def __init__(self, state, device):
         super().__init__()
         t = {k: state[v].detach().to(device=device, dtype=torch.float16).contiguous() for k, v in _SD3_KEYS.items() if state.get(v) is not None}
-        for trio in (("to_q", "to_k", "to_v"), ("add_q", "add_k", "add_v")) if os.environ.get("UNIVST_SD3_FUSED_QKV", "1") != "0" else ():
+        for trio in (("to_q", "to_k", "to_v"), ("add_q", "add_k", "add_v")):
             for suf in ("", "_bias"):
                 names = [n + suf for n in trio]
                 if all(n in t for n in names) and len({tuple(t[n].shape) for n in names}) == 1:

@@ -13,7 +13,6 @@
 // Replaces: attention.py:384-420 (SparseCausalAttention gather + SDPA), pnp_utils.py:59-92 (PnP gather +
 // SDPA), diffusers AttnProcessor2_0 SDPA for attn2.
 #include "common.h"
-#include <stdlib.h>
 
 #include "kernels.h"
 
@@ -463,7 +462,7 @@ __global__ __launch_bounds__(256, 3) void attn_kernel_occ3(AttnParams p) {
 // sched_group_barrier so the in-order wave really alternates MFMA and VALU issue).  K/V tiles of 64 keys live in a 3-stage
 // LDS ring (48 KB, two blocks per CU), prefetched two tiles ahead through registers; one barrier per tile.
 //
-// FOLD: the scale and the running max move INTO the QK^T MFMA.  Q arrives pre-multiplied by scale*log2(e) — the UNet graph
+// The scale and the running max move INTO the QK^T MFMA.  Q arrives pre-multiplied by scale*log2(e) — the UNet graph
 // folds that factor into the to_q weights (AttnParams::q_prescaled), so Q is rounded to fp16 once, exactly as often as the
 // reference rounds it; multiplying an already rounded Q here would add a second 2^-11 error that shows on keys of very
 // large norm (tests) — and the 24 padding columns of the 64-wide contraction carry, on the K side, three columns
@@ -487,9 +486,8 @@ __global__ __launch_bounds__(256, 3) void attn_kernel_occ3(AttnParams p) {
 // front of the tile's barrier, a whole tile after the issue.  Rows past Nkv read a device zero page.
 __device__ __attribute__((aligned(256))) half_t uv_attn_zero_page[128];
 
-template <bool FOLD, int TAG = 0, int STG = 0, bool ONEB = true, bool K16 = false, int TP = 0>
+template <int TAG = 0, int STG = 0, bool K16 = false, int TP = 0>
 __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
-    static_assert(!K16 || FOLD, "the 16-wide second k step carries the folded reference columns");
     constexpr int NW = 4;
     constexpr int D = 40, DV16 = 3, QB = 4, NST = 3;
     constexpr int KSTR = lds_stride_bytes(64 * 2) / 2;       // 80 halfs
@@ -506,11 +504,10 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
     // Head-major order: consecutive logical blocks (= one XCD after xcd_remap) are the query blocks of ONE head over consecutive
     // frames.  Frame f+1 shares two of its three key sources with frame f (the clip's first frame and f itself), so their K/V
     // lines are still in that XCD's L2; with frames outermost every (frame, head) group re-fetched all of its sources from HBM
-    // (PMC: 2.3x the compulsory bytes per launch).  AttnParams::order = 0 keeps the frame-major order (A/B aid UNIVST_ATTN_ORDER).
+    // (PMC: 2.3x the compulsory bytes per launch).  AttnParams::order = 0 is the frame-major order.
     const int qblk = lid % nqb;
     const int h = p.order ? lid / (nqb * p.BF) : (lid / nqb) % p.heads;
     const int bf = p.order ? (lid / nqb) % p.BF : lid / (nqb * p.heads);
-    const float c = p.q_prescaled ? 1.f : p.scale_log2e;     // FOLD is only dispatched for prescaled q (c == 1)
     const h8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
     const int ntile = (p.Nkv + KT - 1) / KT;
@@ -533,7 +530,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
             h8 v = (qrow < p.Nq && dc < D) ? *reinterpret_cast<const h8*>(p.q + ((long)bf * p.Nq + qrow) * p.ldq + h * D + dc) : zero8;
             qf[qb][ks] = v;
         }
-        if (FOLD && !K16 && g == 1) qf[qb][1][2] = (half_t)lw_cur;        // column 42: + log2 multiplicity of the source
+        if (!K16 && g == 1) qf[qb][1][2] = (half_t)lw_cur;        // column 42: + log2 multiplicity of the source
         if (K16) {
             // K16: the second k step covers columns 32..47 only (head_dim 40 + the three folded-reference columns) on the 16-wide
             // MFMA: lane (q, g) holds columns 32 + 4g .. +3 in the LOW half of qf[qb][1] — g 0/1: q[32..39], g 2: (-M_hi, -M_lo, lw, 0)
@@ -546,7 +543,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
             qf[qb][1] = v;
         }
     }
-    // columns 40 / 41 of Q' <- -M (FOLD).  Returns the reference the MFMA will REALLY subtract: -(fp16(-hi) + fp16(-lo)), equal
+    // columns 40 / 41 of Q' <- -M.  Returns the reference the MFMA will REALLY subtract: -(fp16(-hi) + fp16(-lo)), equal
     // to M whenever |M| < 16384 (hi a multiple of 8, lo a multiple of 1/64 below 8 are exact in fp16); beyond that the
     // bookkeeping follows the rounded value, so scores, O^T and the denominator stay on one common scale.
     auto set_shift = [&](int qb, float M) -> float {
@@ -560,11 +557,10 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
     };
 
     f4 o[DV16][QB];
-    float mrun[QB], mc[QB];        // FOLD: mrun = quantised reference M (log2 units).  else: raw running max, mc = lw - mrun*c
+    float mrun[QB];                // quantised reference M (log2 units)
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
-        mrun[qb] = FOLD ? 0.f : -INFINITY;
-        mc[qb] = 0.f;
+        mrun[qb] = 0.f;
 #pragma unroll
         for (int dv = 0; dv < DV16; ++dv) o[dv][qb] = f4{0.f, 0.f, 0.f, 0.f};
     }
@@ -658,7 +654,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
         }
         advance_ld();
     };
-    {   // one-time LDS image: zeros, 1.0 in V column 40 (softmax denominator), FOLD: 1.0 in K columns 40..42
+    {   // one-time LDS image: zeros, 1.0 in V column 40 (softmax denominator), 1.0 in K columns 40..42 (the folded reference)
         for (int i = tid * 8; i < NST * TILE; i += NW * 64 * 8) *reinterpret_cast<h8*>(&smem[i]) = zero8;
         __syncthreads();
         if (tid < KT) {
@@ -666,18 +662,14 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
             for (int st = 0; st < NST; ++st) {
                 if (STG) {          // chunk 5 of a row = columns 40..47: plane 5 of K and of V
                     smem[st * TILE + KAREA + 5 * VPL + tid * 8] = (half_t)1.f;
-                    if (FOLD) {
-                        smem[st * TILE + 5 * KPL + tid * 8] = (half_t)1.f;
-                        smem[st * TILE + 5 * KPL + tid * 8 + 1] = (half_t)1.f;
-                        smem[st * TILE + 5 * KPL + tid * 8 + 2] = (half_t)1.f;
-                    }
+                    smem[st * TILE + 5 * KPL + tid * 8] = (half_t)1.f;
+                    smem[st * TILE + 5 * KPL + tid * 8 + 1] = (half_t)1.f;
+                    smem[st * TILE + 5 * KPL + tid * 8 + 2] = (half_t)1.f;
                 } else {
                     smem[st * TILE + KT * KSTR + tid * VSTR + D] = (half_t)1.f;
-                    if (FOLD) {
-                        smem[st * TILE + tid * KSTR + D] = (half_t)1.f;
-                        smem[st * TILE + tid * KSTR + D + 1] = (half_t)1.f;
-                        smem[st * TILE + tid * KSTR + D + 2] = (half_t)1.f;
-                    }
+                    smem[st * TILE + tid * KSTR + D] = (half_t)1.f;
+                    smem[st * TILE + tid * KSTR + D + 1] = (half_t)1.f;
+                    smem[st * TILE + tid * KSTR + D + 2] = (half_t)1.f;
                 }
             }
         }
@@ -769,21 +761,15 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
             union { fh2 h[4]; h8 v; } u;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                float e0, e1, e2, e3;
-                if (FOLD) {
-                    e0 = __builtin_amdgcn_exp2f(sc[kb][qb][0]); e1 = __builtin_amdgcn_exp2f(sc[kb][qb][1]);
-                    e2 = __builtin_amdgcn_exp2f(sc[kb][qb][2]); e3 = __builtin_amdgcn_exp2f(sc[kb][qb][3]);
-                } else {
-                    e0 = __builtin_amdgcn_exp2f(fmaf(sc[kb][qb][0], c, mc[qb])); e1 = __builtin_amdgcn_exp2f(fmaf(sc[kb][qb][1], c, mc[qb]));
-                    e2 = __builtin_amdgcn_exp2f(fmaf(sc[kb][qb][2], c, mc[qb])); e3 = __builtin_amdgcn_exp2f(fmaf(sc[kb][qb][3], c, mc[qb]));
-                }
+                const float e0 = __builtin_amdgcn_exp2f(sc[kb][qb][0]), e1 = __builtin_amdgcn_exp2f(sc[kb][qb][1]);
+                const float e2 = __builtin_amdgcn_exp2f(sc[kb][qb][2]), e3 = __builtin_amdgcn_exp2f(sc[kb][qb][3]);
                 u.h[kb * 2] = __builtin_amdgcn_cvt_pkrtz(e0, e1);
                 u.h[kb * 2 + 1] = __builtin_amdgcn_cvt_pkrtz(e2, e3);
             }
             pb[qb] = u.v;
         }
     };
-    auto exp_half = [&](const f4 (&sc)[2][QB], h8 (&pb)[QB], int half) {      // query blocks 2*half, 2*half + 1 (FOLD arithmetic)
+    auto exp_half = [&](const f4 (&sc)[2][QB], h8 (&pb)[QB], int half) {      // query blocks 2*half, 2*half + 1
 #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
             const int qb = half * 2 + q2;
@@ -824,59 +810,40 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
     };
     // reference update for the scores `sc` of the NEXT step (deferred, T13).  Everything exponentiated so far is already in
     // O^T (the PV of the previous step precedes this in program order), so O^T is rescaled exactly once per change.
-    // ONEB: one wave-wide test over the four query blocks in front of the per-block tests (the common case — no reference moves —
+    // One wave-wide test over the four query blocks in front of the per-block tests (the common case — no reference moves —
     // then costs 1 max3 + 1 max + 1 compare + 1 branch instead of 4 compares + 4 branches: +1.2 % in four same-box A/B pairs)
-    auto decide = [&](f4 (&sc)[2][QB], const float (&mx)[QB], float lw, bool first) {
-        if (FOLD && ONEB && !first) {
+    auto decide = [&](f4 (&sc)[2][QB], const float (&mx)[QB], bool first) {
+        if (!first) {
             const float mall = fmaxf(max3f(mx[0], mx[1], mx[2]), mx[3]);
             if (__builtin_amdgcn_ballot_w64(mall > DEFER) == 0) return;
         }
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
-            if (FOLD) {
-                if (__builtin_amdgcn_ballot_w64(first || mx[qb] > DEFER) != 0) {
-                    float m = mx[qb];
-                    const float o16 = __shfl_xor(m, 16, 64);
-                    m = max3f(m, o16, o16);
-                    const float o32 = __shfl_xor(m, 32, 64);
-                    m = max3f(m, o32, o32);
-                    float delta = floorf(m * 64.f + 0.5f) * (1.f / 64.f);          // shifted row max, quantised
-                    if (!first) delta = fmaxf(delta, 0.f);
-                    const float mnew = set_shift(qb, mrun[qb] + delta);
-                    delta = mnew - mrun[qb];
-                    mrun[qb] = mnew;
-                    // (first reference: O^T is still zero, and 2^-delta overflows for a strongly negative first row max — 0 * inf)
-                    const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
+            if (__builtin_amdgcn_ballot_w64(first || mx[qb] > DEFER) != 0) {
+                float m = mx[qb];
+                const float o16 = __shfl_xor(m, 16, 64);
+                m = max3f(m, o16, o16);
+                const float o32 = __shfl_xor(m, 32, 64);
+                m = max3f(m, o32, o32);
+                float delta = floorf(m * 64.f + 0.5f) * (1.f / 64.f);          // shifted row max, quantised
+                if (!first) delta = fmaxf(delta, 0.f);
+                const float mnew = set_shift(qb, mrun[qb] + delta);
+                delta = mnew - mrun[qb];
+                mrun[qb] = mnew;
+                // (first reference: O^T is still zero, and 2^-delta overflows for a strongly negative first row max — 0 * inf)
+                const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
 #pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) {
-                        sc[kb][qb][0] -= delta; sc[kb][qb][1] -= delta; sc[kb][qb][2] -= delta; sc[kb][qb][3] -= delta;
-                    }
-#pragma unroll
-                    for (int dv = 0; dv < DV16; ++dv) {
-                        o[dv][qb][0] *= alpha; o[dv][qb][1] *= alpha; o[dv][qb][2] *= alpha; o[dv][qb][3] *= alpha;
-                    }
+                for (int kb = 0; kb < 2; ++kb) {
+                    sc[kb][qb][0] -= delta; sc[kb][qb][1] -= delta; sc[kb][qb][2] -= delta; sc[kb][qb][3] -= delta;
                 }
-            } else {
-                const float lwr = lw * (1.f / c);
-                float m = mx[qb] + lwr;
-                if (__builtin_amdgcn_ballot_w64((m - mrun[qb]) * c > DEFER) != 0) {
-                    const float o16 = __shfl_xor(m, 16, 64);
-                    m = max3f(m, o16, o16);
-                    const float o32 = __shfl_xor(m, 32, 64);
-                    m = max3f(m, o32, o32);
-                    const float mnew = fmaxf(mrun[qb], m);
-                    const float alpha = __builtin_amdgcn_exp2f((mrun[qb] - mnew) * c);
-                    mrun[qb] = mnew;
 #pragma unroll
-                    for (int dv = 0; dv < DV16; ++dv) {
-                        o[dv][qb][0] *= alpha; o[dv][qb][1] *= alpha; o[dv][qb][2] *= alpha; o[dv][qb][3] *= alpha;
-                    }
+                for (int dv = 0; dv < DV16; ++dv) {
+                    o[dv][qb][0] *= alpha; o[dv][qb][1] *= alpha; o[dv][qb][2] *= alpha; o[dv][qb][3] *= alpha;
                 }
-                mc[qb] = fmaf(-mrun[qb], c, lw);
             }
         }
     };
-    auto set_lw = [&](float lw) {                                  // FOLD: column 42 of Q' <- log2 multiplicity of the source
+    auto set_lw = [&](float lw) {                                  // column 42 of Q' <- log2 multiplicity of the source
         if (g == (K16 ? 2 : 1)) {
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb) qf[qb][1][2] = (half_t)lw;
@@ -887,7 +854,6 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
     _Pragma("unroll") for (int i_ = 0; i_ < 16; ++i_) {                           \
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        \
         if (i_ < 6) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);            \
-        if (!FOLD) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);             \
         __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);                        \
         __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                        \
     }
@@ -941,7 +907,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
     qk(kf, scA);
     if (t0_cur + KT > p.Nkv) mask_tail(scA, t0_cur);
     local_max(scA, mx);
-    decide(scA, mx, lw_cur, true);
+    decide(scA, mx, true);
     kfrag_read(b_cur, 1, kf);
 
     for (int tt = 0; tt < T; ++tt) {
@@ -977,9 +943,9 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
         UV_PP_PIN4(mx);
         UV_PP_PHASE2();
         __builtin_amdgcn_sched_barrier(0);
-        decide(scB, mx, lw_cur, false);
+        decide(scB, mx, false);
         // ---- step (tt, 1): scores of (tt+1, 0)
-        if (FOLD && lw_nxt != lw_cur) set_lw(lw_nxt);
+        if (lw_nxt != lw_cur) set_lw(lw_nxt);
         vfrag_read(b_cur, 1, vf);
         if (K16) {
             qk_a(kf, scA);
@@ -1006,7 +972,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
         UV_PP_PIN4(mx);
         UV_PP_PHASE2();
         __builtin_amdgcn_sched_barrier(0);
-        if (has_next) decide(scA, mx, lw_nxt, false);
+        if (has_next) decide(scA, mx, false);
         // ---- end of tile: tile tt+2 into the stage tile tt-1 vacated one barrier ago
         if (!STG && tt + 2 < T) store_tile(b_ld);
         if (STG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of tile tt+2 have landed
@@ -1034,8 +1000,8 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
         const int qrow = qblk * 64 * NW + wave * 16 * QB + qb * 16 + l15;
         if (qrow >= p.Nq) continue;
         half_t* op = p.o + ((long)bf * p.Nq + qrow) * p.ldo + h * D;
-        if constexpr (TP != 0) {          // two-phase attention (AttnParams; TP == 1 first phase, 2 merge phase): the reference in log2 units is M (FOLD) or the raw running max times c
-            const float m2 = FOLD ? mrun[qb] : mrun[qb] * c;
+        if constexpr (TP != 0) {          // two-phase attention (AttnParams; TP == 1 first phase, 2 merge phase): the reference in log2 units is M
+            const float m2 = mrun[qb];
             const long srow = (((long)bf * p.heads + h) * p.Nq + qrow) * 2;
             if constexpr (TP == 1) {
                 if (g == 0) *reinterpret_cast<float2*>(p.state_out + srow) = make_float2(m2, l);
@@ -1078,9 +1044,6 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
 //   * 16 data planes per tile and stage (8 K + 8 V), four DMA instructions per wave and tile, no constant planes, no LDS init;
 //   * the EXTRA key segment of the joint attention (AttnParams::kx: the frame's text tokens, own length / stride / buffers,
 //     multiplicity 1) is one more source of the tile sequence.
-// D, QB (round 5): the same kernel at head_dim 80 (the 32x32 level of the SD-v1.5 UNet) with QB = 2 query blocks (32 rows) per wave: three 32-wide k
-// steps whose last half is padding (two K planes of a stage that are zeroed once and never written by the DMAs; Q is zero there), five V^T
-// fragments, 20 data planes per tile = five DMA instructions per wave; 23.25 KB per stage, 70 KB per block, two blocks per CU.
 // Register budget (2 waves per SIMD: 256): O^T 64 + two score sets 64 + Q 32 + cfold 16 + K / V / P fragments 48 + bookkeeping: 256, no
 // spill.  Measured (12 frames x 24 heads x 4096 queries over 3 x 4096 keys, same box): 3.85 ms = 963 TF against 4.23 ms = 878 TF of
 // attn_body<64, 4, 4>; with ONE wave per SIMD 6.79 ms (546 TF: the second wave hides the tile barrier and the LDS latency); without
@@ -1088,16 +1051,16 @@ __global__ __launch_bounds__(256, 2) void attn_pp40_kernel(AttnParams p) {
 // per SIMD the step costs the SUM of its MFMA cycles (32 x 16 = 512) and its VALU / transcendental issue cycles (~450): the two do not
 // overlap across the two waves of a SIMD (tools/probes/coissue_probe.hip) and hardly inside one here.  What is left is less work per
 // key, not a better order.
-template <int D = 64, int QB = 4, int TAG = 0, int TP = 0>
+template <int TAG = 0, int TP = 0>
 __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(AttnParams p) {
-    static_assert(D % 16 == 0 && D % 8 == 0 && (QB == 2 || QB == 4), "whole V^T fragments, 16-byte K / V chunks");
+    constexpr int D = 64, QB = 4;
     constexpr int NW = 4, DV16 = D / 16, NST = 3;
-    constexpr int KS = (D + 31) / 32;                        // 32-wide k steps of QK^T (D = 80: the third is half padding)
-    constexpr int NDK = D / 8, NPK = KS * 4, NPV = D / 8;    // data chunks of a K row, K planes of a stage (NPK - NDK zero planes), V planes
+    constexpr int KS = D / 32;                               // 32-wide k steps of QK^T
+    constexpr int NDK = D / 8, NPV = D / 8;                  // K planes (data chunks of a K row), V planes of a stage
     constexpr int RB = NW * 16 * QB;                         // query rows of a block
     constexpr int KPL = 512, VPL = 576;                      // plane strides in halfs (1024 B / 1152 B: see attn_pp40_kernel STG)
-    constexpr int KAREA = NPK * KPL;
-    constexpr int TILE = NPK * KPL + NPV * VPL;              // 17 KB per stage (D = 64), 23.25 KB (D = 80)
+    constexpr int KAREA = NDK * KPL;
+    constexpr int TILE = NDK * KPL + NPV * VPL;              // 17 KB per stage
     __shared__ __attribute__((aligned(16))) half_t smem[NST * TILE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1280,7 +1243,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(AttnParams p) {
     // and cfold takes the new reference for every later step.
     auto decide = [&](f4 (&sc)[2][QB], const float (&mx)[QB], float lw, bool first) {
         if (!first) {
-            const float mall = QB == 4 ? fmaxf(max3f(mx[0], mx[1], mx[2]), mx[QB - 1]) : fmaxf(mx[0], mx[1]);
+            const float mall = fmaxf(max3f(mx[0], mx[1], mx[2]), mx[3]);
             if (__builtin_amdgcn_ballot_w64(mall > DEFER) == 0) return;
         }
 #pragma unroll
@@ -1319,7 +1282,7 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(AttnParams p) {
     };
 // issue order inside the two overlapped regions (LLVM SchedGroupMask: VALU 0x2, MFMA 0x8, DS read 0x100, TRANS 0x400)
 /* phase 1: 2 KS QB QK^T MFMAs over 2 DV16 V fragment reads, 8 QB exponentials and 4 QB conversions; phase 2: DV16 QB PV MFMAs over 2 KS K fragment */ \
-/* reads and 8 QB max3 / dot2 (D = 64, QB = 4: 16 | 8, 32, 16 and 16 | 4, 32 — the round-3 pattern) */ \
+/* reads and 8 QB max3 / dot2 (16 | 8, 32, 16 and 16 | 4, 32 — the round-3 pattern) */ \
 #define UV_P64_PHASE1()                                                           \
     _Pragma("unroll") for (int i_ = 0; i_ < 2 * KS * QB; ++i_) {                  \
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        \
@@ -1335,12 +1298,8 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(AttnParams p) {
         if (i_ < 2 * KS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       \
         if (i_ < 4 * QB) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);       \
     }
-#define UV_P64_PIN4(a) do { if constexpr (QB == 4) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])); else asm volatile("" : "+v"(a[0]), "+v"(a[1])); } while (0)
+#define UV_P64_PIN4(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]))
 
-    if constexpr (NPK > NDK) {      // the padding planes of K (columns D .. 32 KS - 1) are zero for the whole launch: the DMAs never write them
-        for (int i = tid * 8; i < NST * TILE; i += NW * 64 * 8) *reinterpret_cast<h8*>(&smem[i]) = zero8;
-        __syncthreads();
-    }
     // ---- prologue: tiles 0 and 1 into the ring, scores + reference of step (0, 0)
     dma_tile(0);
     if (T > 1) dma_tile(TILE);
@@ -1655,17 +1614,16 @@ int launch_attn_tp(const AttnParams& p, hipStream_t stream) {
     if constexpr (DPAD == 64 && DV16 == 3) {
         if (p.q_prescaled && p.Nq >= 2048) {
             const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_pp40_kernel<true, 0, 1, true, true, TP>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((attn_pp40_kernel<0, 1, true, TP>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
             UV_LAUNCH_CHECK();
             return UV_OK;
         }
     }
     if constexpr (DPAD == 64 && DV16 == 4) {      // head_dim 64 (the SD3 joint attention of ranks > 0): the pipelined kernel, as launch_attn picks it
-        static const int pp64 = getenv("UNIVST_ATTN_PP64") ? atoi(getenv("UNIVST_ATTN_PP64")) : 2;
         // (the text queries of a joint attention — 333 rows — take it too, in the merge phase even without the text-key segment)
-        if (pp64 && p.q_prescaled && (p.Nq >= 1024 || (pp64 == 2 && (p.kx || TP == 2) && p.Nq >= 192))) {
+        if (p.q_prescaled && (p.Nq >= 1024 || ((p.kx || TP == 2) && p.Nq >= 192))) {
             const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_pp64_kernel<64, 4, 0, TP>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((attn_pp64_kernel<0, TP>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
             UV_LAUNCH_CHECK();
             return UV_OK;
         }
@@ -1699,75 +1657,34 @@ template <int DPAD, int DV16>
 int launch_attn(const AttnParams& p, hipStream_t stream) {
     if (p.state_out) return launch_attn_tp<DPAD, DV16, 1>(p, stream);
     if (p.state_in) return launch_attn_tp<DPAD, DV16, 2>(p, stream);
-    static const int qb4 = getenv("UNIVST_ATTN_QB4") ? atoi(getenv("UNIVST_ATTN_QB4")) : 1;   // 64 query rows per wave for long sequences
     if constexpr (DPAD == 64 && DV16 == 3) {
-        // UNIVST_ATTN_PP (A/B aid): 2 = software-pipelined kernel with scale/max folded into the MFMA when q is prescaled
-        // (default; plain q takes attn_body), 1 = software-pipelined with plain softmax arithmetic, 0 = attn_body
-        static const int pp = getenv("UNIVST_ATTN_PP") ? atoi(getenv("UNIVST_ATTN_PP")) : 2;
-        if (!p.kx && p.Nq >= 2048 && ((pp == 2 && p.q_prescaled) || pp == 1)) {
+        // head_dim 40 with prescaled q: the software-pipelined kernel with scale / max folded into the MFMA (plain q takes attn_body)
+        if (!p.kx && p.Nq >= 2048 && p.q_prescaled) {
             const int nqb4 = (p.Nq + 255) / 256;
-            const bool text = p.nsrc == 1 && p.Nkv <= 128;
-            // UNIVST_ATTN_STG (A/B aid): 1 (default) = K/V ring filled by LDS-DMA + one wave-wide reference test + 16-wide second k step;
-            // 2 = the same with four per-block tests, 3 = with the 32-wide second k step; 0 = the round-2 kernel (ring through registers)
-            static const int stg = getenv("UNIVST_ATTN_STG") ? atoi(getenv("UNIVST_ATTN_STG")) : 1;
-            if (pp == 2 && text && !p.state_out && !p.state_in) hipLaunchKernelGGL((attn_pp40_kernel<true, 1>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            else if (pp == 2 && stg == 2) hipLaunchKernelGGL((attn_pp40_kernel<true, 0, 1, false, true>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            else if (pp == 2 && stg == 3) hipLaunchKernelGGL((attn_pp40_kernel<true, 0, 1, true, false>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            else if (pp == 2 && stg) hipLaunchKernelGGL((attn_pp40_kernel<true, 0, 1, true, true>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            else if (pp == 2) hipLaunchKernelGGL((attn_pp40_kernel<true, 0>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            else hipLaunchKernelGGL((attn_pp40_kernel<false, 0>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
+            // one short source (81..128 keys, or weighted by src_logw: what attn_text_kernel declines): the register-staged ring under its own symbol;
+            // otherwise the K/V ring filled by LDS-DMA + one wave-wide reference test + 16-wide second k step
+            if (p.nsrc == 1 && p.Nkv <= 128) hipLaunchKernelGGL((attn_pp40_kernel<1>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
+            else hipLaunchKernelGGL((attn_pp40_kernel<0, 1, true>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
             UV_LAUNCH_CHECK();
             return UV_OK;
         }
     }
     if constexpr (DPAD == 64 && DV16 == 4) {
-        // head_dim 64 with prescaled q (the SD3 joint attention folds the factor into the q RMSNorm weight): software-pipelined kernel.
-        // UNIVST_ATTN_PP64=0 (A/B aid): the generic body
-        static const int pp64 = getenv("UNIVST_ATTN_PP64") ? atoi(getenv("UNIVST_ATTN_PP64")) : 2;
-        // (pp64 = 2, default since round 4: also the text queries of a joint attention — 333 rows over 12 621 keys — which otherwise take the
-        // generic body: SD3.5 step 944 / 947 -> 934 / 943 ms, same box; 1 = image queries only)
-        if (pp64 && !p.state_out && !p.state_in && p.q_prescaled && (p.Nq >= 1024 || (pp64 == 2 && p.kx && p.Nq >= 192))) {
+        // head_dim 64 with prescaled q (the SD3 joint attention folds the factor into the q RMSNorm weight): software-pipelined kernel,
+        // also for the text queries of a joint attention — 333 rows over 12 621 keys — which otherwise take the generic body
+        // (round 4: SD3.5 step 944 / 947 -> 934 / 943 ms, same box)
+        if (p.q_prescaled && (p.Nq >= 1024 || (p.kx && p.Nq >= 192))) {
             const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_pp64_kernel<64, 4, 0>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((attn_pp64_kernel<0>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
             UV_LAUNCH_CHECK();
             return UV_OK;
         }
     }
-    if constexpr (DPAD == 96 && DV16 == 5) {
-        // head_dim 80 (the 32x32 level of SD-v1.5) with prescaled q: the same pipeline at 32 query rows per wave (round 5) — measured and NOT
-        // dispatched by default.  It runs two waves per SIMD where attn_kernel_occ3 runs three, and with 44 MFMAs per wave between two tile
-        // barriers the third wave hides more than the leaner instruction stream saves: same box, alternating, the 32x32-level attention of the
-        // full step 2.18 -> 2.27 ms; of a rank's shard (384 blocks) 0.435 -> 0.404 ms — and the generic body with the same arithmetic savings
-        // (attn_body CF, built right after) takes 1.86 ms / 0.364 ms.  UNIVST_ATTN_PP80 = 1: grids of at most one round, 2: always (A/B aid)
-        static const int pp80 = getenv("UNIVST_ATTN_PP80") ? atoi(getenv("UNIVST_ATTN_PP80")) : 0;
-        const int nqb2 = (p.Nq + 127) / 128;
-        if (pp80 && !p.state_out && !p.state_in && p.q_prescaled && !p.kx && p.Nq >= 512 && (pp80 == 2 || (long)nqb2 * p.heads * p.BF <= 512)) {
-            hipLaunchKernelGGL((attn_pp64_kernel<80, 2, 0>), dim3(nqb2 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    // (probe, round 5) UNIVST_ATTN_CF40=1 with UNIVST_ATTN_PP=0: head_dim 40 on the generic body with the accumulator-folded reference at three waves per SIMD
-    static const int cf40 = getenv("UNIVST_ATTN_CF40") ? atoi(getenv("UNIVST_ATTN_CF40")) : 0;
-    if constexpr (DPAD == 64 && DV16 == 4) {      // (probe) UNIVST_ATTN_CF64=1 with UNIVST_ATTN_PP64=0: the same at head_dim 64 (SD3 joint attention, SD-v2.1)
-        static const int cf64 = getenv("UNIVST_ATTN_CF64") ? atoi(getenv("UNIVST_ATTN_CF64")) : 0;
-        if (cf64 && p.q_prescaled && p.Nq >= 192) {
-            const int nqb2 = (p.Nq + 127) / 128;
-            hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2, true>), dim3(nqb2 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    if constexpr (DPAD == 64 && DV16 == 3) {
-        if (cf40 && p.q_prescaled && p.Nq >= 512) {
-            const int nqb2 = (p.Nq + 127) / 128;
-            hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2, true>), dim3(nqb2 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
+    // (head_dim 80 keeps the generic body: round 5 measured the pipelined kernel at 32 query rows per wave there — two waves per SIMD
+    // where attn_kernel_occ3 runs three, and with 44 MFMAs per wave between two tile barriers the third wave hides more than the leaner
+    // instruction stream saves: the 32x32-level attention of the full step 2.18 -> 2.27 ms.)
     if constexpr (DPAD <= 64) {
-        if (qb4 && p.Nq >= 2048) {
+        if (p.Nq >= 2048) {         // 64 query rows per wave for long sequences
             const int nqb4 = (p.Nq + 255) / 256;
             hipLaunchKernelGGL((attn_kernel_occ2<DPAD, DV16, 4>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
             UV_LAUNCH_CHECK();
@@ -1779,9 +1696,8 @@ int launch_attn(const AttnParams& p, hipStream_t stream) {
     dim3 grid(nqb * p.heads * p.BF), block(256);
     if constexpr (DPAD >= 96) {
         // prescaled q on the wide heads (80, 160: the 32x32 / 16x16 levels of SD-v1.5): the reference rides in the MFMA accumulator, row sums by
-        // v_dot2 (attn_body CF).  UNIVST_ATTN_CF=0 (A/B aid): the plain softmax arithmetic
-        static const int cfenv = getenv("UNIVST_ATTN_CF") ? atoi(getenv("UNIVST_ATTN_CF")) : 1;
-        if (cfenv && p.q_prescaled) {
+        // v_dot2 (attn_body CF)
+        if (p.q_prescaled) {
             if constexpr (DPAD == 96) {
                 if (QB == 2) hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2, true>), grid, block, 0, stream, p);
                 else hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 1, true>), grid, block, 0, stream, p);
@@ -1811,9 +1727,8 @@ int launch_attn(const AttnParams& p, hipStream_t stream) {
 static int attn_dispatch(const AttnParams& p, hipStream_t stream);
 
 int uv_launch_attention(const AttnParams& p0, hipStream_t stream) {
-    static const int order_env = getenv("UNIVST_ATTN_ORDER") ? atoi(getenv("UNIVST_ATTN_ORDER")) : 1;
     AttnParams p = p0;
-    p.order = order_env;
+    p.order = 1;                          // head-major block order (the kernels read it)
     UV_REQUIRE(p.d % 8 == 0, "attention: head_dim=%d must be a multiple of 8", p.d);
     UV_REQUIRE(p.nsrc >= 1 && p.Nkv >= 1 && p.Nq >= 1, "attention: empty problem");
     UV_REQUIRE(p.ldq % 8 == 0 && p.ldkv % 8 == 0 && p.ldo % 4 == 0, "attention: row strides must be multiples of 8");
@@ -1832,9 +1747,8 @@ int uv_launch_attention(const AttnParams& p0, hipStream_t stream) {
 }
 
 static int attn_dispatch(const AttnParams& p, hipStream_t stream) {
-    // text cross-attention: one short source, K/V held in registers (attn_text_kernel).  UNIVST_ATTN_TEXT=0: generic kernels (A/B aid)
-    static const int text_env = getenv("UNIVST_ATTN_TEXT") ? atoi(getenv("UNIVST_ATTN_TEXT")) : 1;
-    if (text_env && !p.kx && !p.state_out && !p.state_in && p.nsrc == 1 && p.Nkv <= 80 && !p.src_logw && (p.d == 40 || p.d == 80) && p.Nq >= 256) {
+    // text cross-attention: one short source, K/V held in registers (attn_text_kernel)
+    if (!p.kx && !p.state_out && !p.state_in && p.nsrc == 1 && p.Nkv <= 80 && !p.src_logw && (p.d == 40 || p.d == 80) && p.Nq >= 256) {
         const int nchunk = (p.Nq + 1023) / 1024;
         const dim3 grid((unsigned)(nchunk * p.heads * p.BF));
         if (p.d == 40) hipLaunchKernelGGL((attn_text_kernel<40>), grid, dim3(256), 0, stream, p);

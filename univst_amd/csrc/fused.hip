@@ -19,7 +19,6 @@
 // Arithmetic: fp32 accumulation; Q, P, O and Y are rounded to fp16 where the unfused graph rounds them, plus Y once before the residual
 // add (the reference's own order: Linear output in fp16, then `+ hidden_states`).
 #include "common.h"
-#include <stdlib.h>
 
 #include "kernels.h"
 
@@ -432,8 +431,7 @@ long uv_attn2_kvf_halfs(int B, int heads, int D) {
 }
 
 bool uv_attn2_fused_ok(int C, int heads, int rows_per_branch, int Nkv) {
-    static const int env = getenv("UNIVST_ATTN2_FUSED") ? atoi(getenv("UNIVST_ATTN2_FUSED")) : 1;
-    return env != 0 && C == 320 && heads == 8 && rows_per_branch % 64 == 0 && Nkv >= 1 && Nkv <= 80;
+    return C == 320 && heads == 8 && rows_per_branch % 64 == 0 && Nkv >= 1 && Nkv <= 80;
 }
 
 int uv_launch_kv_frag_pack(const half_t* kv, half_t* out, int B, int T, int C, int heads, hipStream_t s) {

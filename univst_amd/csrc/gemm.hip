@@ -20,7 +20,6 @@
 // proj_out), attention.py:375-377,425 + pnp_utils.py:39-43,97 (to_q/k/v/out), diffusers FeedForward/GEGLU,
 // diffusers Attention projections, unet_3d_blocks.py:523,618 (torch.cat skip), resnet.py:145 (nearest x2).
 #include "common.h"
-#include <stdlib.h>
 
 #include "kernels.h"
 
@@ -1409,34 +1408,27 @@ static bool uv_conv_patch_eligible(const GemmParams& p, int bmb) {
            bmb % p.Wo == 0 && (bmb / p.Wo + 2 + bmb / p.Wo / p.Ho + 1) * (p.Wo + 2) <= 512 && !p.geglu;
 }
 
-// ONE copy of what the 256x320 path requires of a problem's shape / environment: used by the launcher below and by the predicate the
+// fewest 256x320 tiles a problem needs to take the big tile without split-K: measured cross-over (tools/bench_gemm_mid.py)
+constexpr long BIG_MIN_TILES = 150;
+
+// ONE copy of what the 256x320 path requires of a problem's shape: used by the launcher below and by the predicate the
 // UNet graph consults before it decides to fold a LayerNorm (the two used to be separate copies that could drift apart).
-struct BigEnv {
-    int nobig, epi;
-    long bigmin;
-};
-static const BigEnv& big_env() {
-    static const BigEnv e = {getenv("UNIVST_GEMM_NOBIG") ? atoi(getenv("UNIVST_GEMM_NOBIG")) : 0,
-                             getenv("UNIVST_GEMM_EPI") ? atoi(getenv("UNIVST_GEMM_EPI")) : 1,
-                             (getenv("UNIVST_GEMM_BIGMIN") && atol(getenv("UNIVST_GEMM_BIGMIN"))) ? atol(getenv("UNIVST_GEMM_BIGMIN")) : 150};   // measured cross-over (tools/bench_gemm_mid.py)
-    return e;
-}
 // ragged: a plain linear (no GEGLU, no LayerNorm fold / statistics, no split-K) may end in a partly filled column tile (N % 8 == 0):
 // the MM-DiT widths of the SD3 path (1536, 4608, 6144 = 4.8 / 14.4 / 19.2 tiles) lose 4 % of the MFMA work to padding and still run
 // 1.4x faster than on the 128 x 128 tile.  Weight rows >= N come from the zero page; both epilogues skip columns >= N.
 // (round 5: ragged_min — convolutions of widths 256 / 512 (the temporal VAE: a last column tile 80 % / 60 % full) also take the 256x320 tile: 900+ TFLOP/s of
-// useful work against ~500 on the 128 x 128 tile; UNIVST_CONV_RAGGED=0 switches that off)
+// useful work against ~500 on the 128 x 128 tile)
 static bool big_shape_ok(int N, int K, long x_elems, bool ragged = false, int ragged_min = 640) {      // x_elems: extent of the activation operand in elements (32-bit DMA offsets)
-    return !big_env().nobig && (N % 320 == 0 || (ragged && N % 8 == 0 && N >= ragged_min)) && (long)N * K < (1L << 31) && x_elems < (1L << 31);
+    return (N % 320 == 0 || (ragged && N % 8 == 0 && N >= ragged_min)) && (long)N * K < (1L << 31) && x_elems < (1L << 31);
 }
 
 // Does a plain linear [M, K] (row stride ldx, 0 = K) x [N, K]^T take the direct (no split-K) 256x320 path whose epilogue can fold a
-// LayerNorm / emit row statistics?  Same conditions as the launcher (which still re-checks and fails loudly on a mismatch), incl.
-// the LDS epilogue switch; pointer alignment is the caller's business (the UNet arena is 256-byte aligned).
+// LayerNorm / emit row statistics?  Same conditions as the launcher (which still re-checks and fails loudly on a mismatch);
+// pointer alignment is the caller's business (the UNet arena is 256-byte aligned).
 bool uv_linear_takes_big_direct(long M, int N, int K, long ldx) {
-    if (!big_shape_ok(N, K, M * (ldx ? ldx : (long)K)) || big_env().epi == 0) return false;
+    if (!big_shape_ok(N, K, M * (ldx ? ldx : (long)K))) return false;
     const long n256 = ((M + 255) / 256) * (N / 320), n192 = ((M + 191) / 192) * (N / 320);
-    return n256 >= big_env().bigmin && n192 >= big_env().bigmin;      // whichever tile height the launcher picks
+    return n256 >= BIG_MIN_TILES && n192 >= BIG_MIN_TILES;      // whichever tile height the launcher picks
 }
 
 int uv_launch_geglu_xres_permute(const half_t* in, half_t* out, int rows, int cols, hipStream_t stream) {
@@ -1447,11 +1439,10 @@ int uv_launch_geglu_xres_permute(const half_t* in, half_t* out, int rows, int co
 }
 // M = 0: the shape alone (weight preparation).  With M: a block walks ALL column tiles of its 128 rows (74 us at N = 2 560), so the grid
 // has to fill whole rounds of the CUs: at least two rounds, the last one >= 80 % full — one rank of an 8-GPU job (192 blocks) and a 1.5-round
-// grid stay on the 256x320 tile (emulated rank: 1.34 vs 1.41 ms for the class).  UNIVST_GEGLU_XRES=0: never, =2: whenever the shape fits.
+// grid stay on the 256x320 tile (emulated rank: 1.34 vs 1.41 ms for the class).
 bool uv_geglu_xres_ok(int N, int K, long M) {
-    static const int env = getenv("UNIVST_GEGLU_XRES") ? atoi(getenv("UNIVST_GEGLU_XRES")) : 1;
-    if (env == 0 || K != XR_K || N % XR_BN != 0) return false;
-    if (M <= 0 || env == 2) return true;
+    if (K != XR_K || N % XR_BN != 0) return false;
+    if (M <= 0) return true;
     const long blocks = (M + XR_BM - 1) / XR_BM, ncu = uv_num_cus(), rounds = (blocks + ncu - 1) / ncu;
     return blocks >= 2 * ncu && blocks * 10 >= rounds * ncu * 8;
 }
@@ -1468,17 +1459,14 @@ static SmallPlan small_plan(long M, int N, int K, bool geglu, int mode, bool wan
     sp.nf5 = !geglu && (N % 160 == 0) && ((N % 128 != 0) || want_stats);
     sp.bn = sp.nf5 ? 160 : 128;
     sp.nt = (int)(((M + BM_DEFAULT - 1) / BM_DEFAULT) * ((N + sp.bn - 1) / sp.bn));
-    // small-M problems (deepest UNet level: 3072 rows): 64-row tiles double the block count so the chip is filled
-    // UNIVST_GEMM_SMALLM (A/B aid): 0 = never, 1 = whenever the 128-row tiles are < 2 per CU, 2 (default) = convs only when
-    // split-K cannot supply the parallelism instead (short K); linears always (measured: tools/bench_gemm_mid.py)
-    static const int smallm_mode = getenv("UNIVST_GEMM_SMALLM") ? atoi(getenv("UNIVST_GEMM_SMALLM")) : 2;
-    sp.small_m = !sp.nf5 && sp.nt < 2 * uv_num_cus() && M > 64 && smallm_mode != 0 &&
-                 (smallm_mode == 1 || mode == 0 || geglu || (K + 63) / 64 < 16);
+    // small-M problems (deepest UNet level: 3072 rows): 64-row tiles double the block count so the chip is filled when the
+    // 128-row tiles are < 2 per CU — linears always, convs only when split-K cannot supply the parallelism instead (short K;
+    // measured: tools/bench_gemm_mid.py)
+    sp.small_m = !sp.nf5 && sp.nt < 2 * uv_num_cus() && M > 64 && (mode == 0 || geglu || (K + 63) / 64 < 16);
     if (sp.small_m) sp.nt = (int)(((M + 63) / 64) * ((N + sp.bn - 1) / sp.bn));
     // split-K when the tiles alone leave most CUs idle and K is long (deep levels; every level of a frame shard)
     sp.splits = 1;
-    static const int splitk = getenv("UNIVST_GEMM_SPLITK") ? atoi(getenv("UNIVST_GEMM_SPLITK")) : 1;
-    if (splitk && !geglu && N % 4 == 0 && sp.nt < 384) {
+    if (!geglu && N % 4 == 0 && sp.nt < 384) {
         const int nk = (K + 63) / 64;
         const int s = uv_pick_splits(sp.nt, nk, 2L * uv_num_cus(), 4, 16, 1.0, (double)M * N * 4.0);     // two resident blocks per CU
         if (s >= 2) sp.splits = s;
@@ -1492,8 +1480,7 @@ static SmallPlan small_plan(long M, int N, int K, bool geglu, int mode, bool wan
 // problem lives in the reduction kernel).  The GEGLU consumer exists in the 256x320 kernel only.
 bool uv_linear_fold_producer_ok(long M, int N, int K) {
     if (uv_linear_takes_big_direct(M, N, K)) return true;
-    static const int env = getenv("UNIVST_LN_FOLD_SMALL") ? atoi(getenv("UNIVST_LN_FOLD_SMALL")) : 1;
-    if (!env || N % 160 != 0 || K % 8 != 0) return false;
+    if (N % 160 != 0 || K % 8 != 0) return false;
     if (big_shape_ok(N, K, M * (long)K)) {      // the 256x320 path with split-K would take it (long reductions): no epilogue there
         const long n256 = ((M + 255) / 256) * (N / 320);
         if (n256 >= 8 && K >= 128 * 64) return false;
@@ -1502,8 +1489,7 @@ bool uv_linear_fold_producer_ok(long M, int N, int K) {
 }
 bool uv_linear_fold_consumer_ok(long M, int N, int K, bool geglu) {
     if (uv_linear_takes_big_direct(M, N, K)) return true;
-    static const int env = getenv("UNIVST_LN_FOLD_SMALL") ? atoi(getenv("UNIVST_LN_FOLD_SMALL")) : 1;
-    if (!env || geglu || N % 4 != 0 || K % 160 != 0) return false;
+    if (geglu || N % 4 != 0 || K % 160 != 0) return false;
     if (big_shape_ok(N, K, M * (long)K)) {
         const long n256 = ((M + 255) / 256) * (N / 320);
         if (n256 >= 8 && K >= 128 * 64) return false;
@@ -1561,27 +1547,23 @@ int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
         UV_REQUIRE(!p.W32 || sym3, "conv: the LDS-patch weight copy is for the 3x3 / padding-1 kernel");
     }
     {   // large-M path: 256x320 tiles when they tile N exactly and fill the chip (>= 2 blocks per CU)
-        const int nobig = big_env().nobig;
         // tile height: 256 rows, or 192 when that fills whole rounds of the CUs better (49152 x 640 is 384 tiles of 256 = 1.5
         // rounds but 512 tiles of 192 = 2 exact ones; 12288 x 1280 is 192 vs 256 tiles)
-        static const int bm_env = getenv("UNIVST_GEMM_BM") ? atoi(getenv("UNIVST_GEMM_BM")) : 0;     // A/B aid: force 256 / 192
         const long ncu = uv_num_cus();
-        static const int conv_ragged = getenv("UNIVST_CONV_RAGGED") ? atoi(getenv("UNIVST_CONV_RAGGED")) : 1;
         // a ragged last column tile: plain linears (N >= 640) and, since round 5, plain convs whose width fills a whole number of 64-column wave halves
         // and at least 80 % of one tile (256, 512, 576, ...: not the UNet's widths, which are multiples of 320)
-        const bool conv_rag = mode == 1 && conv_ragged && !p.gn_out && p.N % 64 == 0 && p.N >= 256 && (p.N % 320 == 0 || p.N % 320 >= 192);
+        const bool conv_rag = mode == 1 && !p.gn_out && p.N % 64 == 0 && p.N >= 256 && (p.N % 320 == 0 || p.N % 320 >= 192);
         const bool ragged = (mode == 0 && !p.geglu && !lnf) || conv_rag;
         const int ntn_c = (p.N + 319) / 320;
         const long n256 = (long)((p.M + 255) / 256) * ntn_c, n192 = (long)((p.M + 191) / 192) * ntn_c;
         // per-row cost of the 192-row tile relative to the 256-row one, measured at equal round counts: convs 0.96-1.0, linears 1.02-1.07
         // (round 5: the conv factor was 0.99, which at the 64x64 level — 768 tiles of 256 rows = 3 full rounds against 1 024 of 192 = 4 — picked 192
         // by a hair; measured on the LDS-patch kernel the 256-row tile is 2.5 - 4 % faster there (0.357 / 0.936 / 0.585 ms against 0.366 / 0.973 /
-        // 0.609 for 320->320, 960->320, 640->320 at 64 x 64), while the 32x32 and 16x16 levels keep 192: fewer rounds.  UNIVST_CONV_192_COST: A/B aid)
-        static const double conv192 = getenv("UNIVST_CONV_192_COST") ? atof(getenv("UNIVST_CONV_192_COST")) : 1.03;
-        const double c256 = (double)((n256 + ncu - 1) / ncu) * 256.0, c192 = (double)((n192 + ncu - 1) / ncu) * 192.0 * (mode == 1 ? conv192 : 1.05);
+        // 0.609 for 320->320, 960->320, 640->320 at 64 x 64), while the 32x32 and 16x16 levels keep 192: fewer rounds)
+        const double c256 = (double)((n256 + ncu - 1) / ncu) * 256.0, c192 = (double)((n192 + ncu - 1) / ncu) * 192.0 * (mode == 1 ? 1.03 : 1.05);
         // (the MM-DiT epilogue instantiation fits the 256-VGPR budget only with the 192-row tile: 223 registers; 256 rows spill 48)
         const bool mmdit_epi = mode == 0 && (p.act || p.gate);
-        bool use192 = mmdit_epi ? true : (bm_env ? bm_env == 192 : (c192 < c256 && n192 >= 150));
+        bool use192 = mmdit_epi || (c192 < c256 && n192 >= BIG_MIN_TILES);
         if (p.w_rows_per_set) {           // weight sets per row range: a tile must lie inside one set
             UV_REQUIRE(mode == 0 && p.bias32 && !p.geglu && !p.ln_stats && !mmdit_epi && p.M % p.w_rows_per_set == 0 && (p.w_rows_per_set % 256 == 0 || p.w_rows_per_set % 192 == 0) &&
                        (long)(p.M / p.w_rows_per_set) * p.N * p.K + (long)p.N * p.K < (1L << 31),
@@ -1590,21 +1572,18 @@ int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
         }
         const long nblk = use192 ? n192 : n256;
         const long xmax = (mode == 0) ? (long)p.M * p.ldx : (long)p.M * (p.C1 > p.C2 ? p.C1 : p.C2) * 4;
-        const long bigmin = big_env().bigmin;
         // few tiles but a long reduction (the 8x8-level convs; most convs of a frame shard): the big tile with split-K
         int bsplits = 1;
-        static const int splitk_big = getenv("UNIVST_GEMM_SPLITK") ? atoi(getenv("UNIVST_GEMM_SPLITK")) : 1;
-        if (splitk_big && !nobig && !p.geglu && p.N % 320 == 0 && nblk < bigmin && nblk >= 8 && p.K >= 128 * 64) {   // fp32 partials cost ~35 us: long reductions only
+        if (!p.geglu && p.N % 320 == 0 && nblk < BIG_MIN_TILES && nblk >= 8 && p.K >= 128 * 64) {   // fp32 partials cost ~35 us: long reductions only
             const int nk = (p.K + 63) / 64;
             int sp = uv_pick_splits(nblk, nk, uv_num_cus(), 24, 8, 2.2, (double)p.M * p.N * 4.0);
             while (sp >= 2 && (size_t)sp * p.M * p.N * sizeof(float) > UV_SPLITK_WS_BYTES) --sp;     // what the partial workspace holds
             if (sp >= 2 && nblk * sp >= 128) bsplits = sp;
         }
-        static const int patch_env = getenv("UNIVST_CONV_PATCH") ? atoi(getenv("UNIVST_CONV_PATCH")) : 1;
-        const bool use_patch = patch_env && mode == 1 && (nblk >= bigmin || bsplits > 1) && uv_conv_patch_eligible(p, use192 ? 192 : 256);
+        const bool use_patch = mode == 1 && (nblk >= BIG_MIN_TILES || bsplits > 1) && uv_conv_patch_eligible(p, use192 ? 192 : 256);
         UV_REQUIRE(p.W || use_patch, "conv: only the [Cin/32][9][32] weight copy was given but the problem is not eligible for the LDS-patch kernel "
                    "(3x3, stride 1, whole image rows per 256/192-row tile, >= 150 tiles or a reduction long enough for split-K)");
-        if (big_shape_ok(p.N, p.K, xmax, ragged, conv_rag ? 256 : 640) && (nblk >= bigmin || bsplits > 1)) {
+        if (big_shape_ok(p.N, p.K, xmax, ragged, conv_rag ? 256 : 640) && (nblk >= BIG_MIN_TILES || bsplits > 1)) {
             char sym[48];
             if (use_patch) snprintf(sym, sizeof sym, "conv_patch_kernel<%d>", use192 ? 3 : 4);
             else snprintf(sym, sizeof sym, "gemm_big_kernel<%d,%d,%d>", mode, use192 ? 3 : 4, mode == 0 ? (p.ln_stats ? 2 : (p.stats_out ? 1 : (mmdit_epi ? 3 : 0))) : 0);
@@ -1612,31 +1591,22 @@ int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
             uv_gemm_bytes(p, mode, &by, &byx);
             uv_prof_begin(mode == 0 ? UV_CLS_GEMM_BIG : (use_patch ? UV_CLS_CONV_PATCH : UV_CLS_CONV_BIG), 2.0 * p.M * (double)p.N * p.K, by, stream, sym, byx);
             // row-contiguous epilogue through LDS needs 16-byte aligned rows everywhere it touches; it pays for the plain
-            // and residual epilogues (-12..19 % at K=320) but not for GEGLU, whose stores are half as many (UNIVST_GEMM_EPI=2 forces it)
-            const int epi = big_env().epi;
+            // and residual epilogues (-12..19 % at K=320) but not for GEGLU, whose stores are half as many
             auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
             GemmParams q = p;
-            {   // row-group x column-block tile order for wide outputs (see gemm_big_kernel); UNIVST_GEMM_TILEORDER=0: column-fastest
-                static const int to_env = getenv("UNIVST_GEMM_TILEORDER") ? atoi(getenv("UNIVST_GEMM_TILEORDER")) : 1;
-                const int ntn = ntn_c;
-                q.tile_gn = 0;
-                if (to_env && mode == 0 && ntn > 4 && (long)p.N * p.K * 2 > (3L << 20)) {      // W larger than ~3 MB: it cannot stay in L2 as a whole
-                    q.tile_gn = ntn % 2 == 0 ? 2 : 0;       // 8 x 2 measured best of 8x4 / 16x2 / 4x8 / 16x4 / 32x4 (all within 2 %); 10 x 3 was a loss
-                    q.tile_gm = 8;
-                    if (to_env > 1) { q.tile_gn = to_env % 100; q.tile_gm = to_env / 100; if (ntn % q.tile_gn) q.tile_gn = 0; }    // A/B: gm*100 + gn
-                }
+            // row-group x column-block tile order for wide outputs (see gemm_big_kernel); otherwise column-fastest
+            q.tile_gn = 0;
+            if (mode == 0 && ntn_c > 4 && (long)p.N * p.K * 2 > (3L << 20)) {      // W larger than ~3 MB: it cannot stay in L2 as a whole
+                q.tile_gn = ntn_c % 2 == 0 ? 2 : 0;     // 8 x 2 measured best of 8x4 / 16x2 / 4x8 / 16x4 / 32x4 (all within 2 %); 10 x 3 was a loss
+                q.tile_gm = 8;
             }
-            // next tile's DMA: activation rows before the first k-half's MFMAs, weight rows before the second (1, default; +2..8 % on
-            // the linears: the LDS-DMA writes at 64 B/clk and competes with the fragment reads) or all at once (0)
-            static const int issue_mode = getenv("UNIVST_GEMM_ISSUE") ? atoi(getenv("UNIVST_GEMM_ISSUE")) : 1;
-            q.issue_mode = issue_mode;
-            q.epi_lds = epi && (!p.geglu || epi == 2) && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && al16(p.bias2) && al16(p.rowbias) && p.ldrb % 8 == 0 &&
+            q.epi_lds = !p.geglu && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && al16(p.bias2) && al16(p.rowbias) && p.ldrb % 8 == 0 &&
                         (!p.R || (p.ldr % 8 == 0 && al16(p.R)));
-            // GEGLU (round 4): register math + fp16 slab + row-contiguous 16-byte stores (epi_lds = 3); UNIVST_GEMM_EPI=4 keeps the 8-byte register stores (A/B)
-            const bool geglu_slab = p.geglu && mode == 0 && epi != 0 && epi != 2 && epi != 4 && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && p.N % 16 == 0;
+            // GEGLU (round 4): register math + fp16 slab + row-contiguous 16-byte stores (epi_lds = 3)
+            const bool geglu_slab = p.geglu && mode == 0 && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && p.N % 16 == 0;
             if (geglu_slab) q.epi_lds = 3;
             // the fp32 bias (GroupNorm folded into the linear) exists in the row epilogue through LDS only: a launch that would land on the register
-            // epilogue (misaligned Y / R, UNIVST_GEMM_EPI=0) or on split-K must not drop it silently
+            // epilogue (misaligned Y / R) or on split-K must not drop it silently
             UV_REQUIRE(!p.bias32 || (q.epi_lds == 1 && bsplits <= 1), "linear: the fp32 bias needs the LDS row epilogue of the direct path (16-byte aligned Y / R / bias rows, no split-K)");
             // (Measured and rejected on this tile, DESIGN.md §4: a 32-wide-k 4-stage DMA ring with counted vmcnt (-10 %), the same
             // with two wave groups staggered by half a k tile + s_setprio (-0..18 %), and a five-phase / two-barriers-per-phase
@@ -1663,10 +1633,6 @@ int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
                 else if (p.gn_emitted) *p.gn_emitted = 1;
             }
             const dim3 bgrid((unsigned)(nblk * q.splits));
-            if (use_patch) {
-                static const int wissue = getenv("UNIVST_CONV_PATCH_WISSUE") ? atoi(getenv("UNIVST_CONV_PATCH_WISSUE")) : 1;
-                q.issue_mode = wissue ? 1 : 0;
-            }
             if (use_patch) {          // 3x3 / stride 1 on whole image rows: input patch in LDS, k order [Cin/32][9][32] (p.W32)
                 if (use192) hipLaunchKernelGGL((conv_patch_kernel<3>), bgrid, dim3(512), 0, stream, q);
                 else hipLaunchKernelGGL((conv_patch_kernel<4>), bgrid, dim3(512), 0, stream, q);

@@ -43,7 +43,7 @@ struct GemmParams {
     size_t partial_bytes = 0;
     int splits = 1, ktps = 0;          // set by the launcher
     int tile_gn = 0, tile_gm = 0;      // 256x320 kernel: tile order in groups of tile_gm row tiles x tile_gn column tiles (0: column tile fastest); set by the launcher
-    int issue_mode = 0;                // 256x320 kernel, A/B aid: how the next tile's DMA is spread over the current tile's MFMAs
+    int issue_mode = 0;                // unused: no kernel reads it (kept so the kernel-argument layout stays put)
     // LayerNorm folded into the linears around it (uv_linear_fold_producer_ok / uv_linear_fold_consumer_ok):
     //  producer: stats_out[m][N/160][2] <- (sum, sum of squares) of the stored fp16 outputs per 160-column slot;
     //  consumer: X holds the RAW rows, W = gamma (.) W, and the epilogue computes rstd*(acc - mean*ln_wsum[n]) + ln_bias[n]

@@ -5,8 +5,6 @@
 // Replaces src/mask_propagation.py:72-83 (mask_propogation core) and :60-69 (upsample / norm_mask / argmax).
 // The random sub-sampling (:87-97, torch.randperm on the host RNG) stays on the host on purpose so that the
 // index stream is bit-identical to the reference's.
-#include <stdlib.h>
-
 #include "common.h"
 #include "kernels.h"
 
@@ -26,61 +24,11 @@ __global__ void rownorm_kernel(const float* __restrict__ x, float* __restrict__ 
     for (int c = lane; c < C; c += 64) y[r * C + c] = x[r * C + c] / d;
 }
 
-// C[m][n] = sum_k A[m][k] * (TRANSB ? B[n][k] : B[k][n]); EXP: C = exp(C / T).  64x64 tile, 4x4 per thread.
-template <bool TRANSB, bool EXP>
-__global__ __launch_bounds__(256) void sgemm_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                    float* __restrict__ Cm, int M, int N, int K, float T) {
-    __shared__ float As[16][64 + 4];
-    __shared__ float Bs[16][64 + 4];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    float acc[4][4] = {};
-    for (int k0 = 0; k0 < K; k0 += 16) {
-        for (int e = threadIdx.x; e < 64 * 16; e += 256) {
-            int mm = e / 16, kk = e % 16;                       // A row-major [M,K]
-            int gm = m0 + mm, gk = k0 + kk;
-            As[kk][mm] = (gm < M && gk < K) ? A[(long)gm * K + gk] : 0.f;
-            if (TRANSB) {
-                int gn = n0 + mm;
-                Bs[kk][mm] = (gn < N && gk < K) ? B[(long)gn * K + gk] : 0.f;
-            }
-        }
-        if (!TRANSB) {
-            for (int e = threadIdx.x; e < 64 * 16; e += 256) {
-                int kk = e / 64, nn = e % 64;
-                int gk = k0 + kk, gn = n0 + nn;
-                Bs[kk][nn] = (gk < K && gn < N) ? B[(long)gk * N + gn] : 0.f;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            float a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = As[kk][ty * 4 + i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = Bs[kk][tx * 4 + j];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int gm = m0 + ty * 4 + i, gn = n0 + tx * 4 + j;
-            if (gm < M && gn < N) Cm[(long)gm * N + gn] = EXP ? expf(acc[i][j] / T) : acc[i][j];
-        }
-}
-
-// The same GEMM on the fp32 matrix cores (round 3): v_mfma_f32_32x32x2_f32 is bit-for-bit a k-ordered fmaf chain (guide §3
-// "FP32-input MFMA": one rounding per product, no wider accumulation), i.e. EXACTLY what sgemm_kernel's inner loop computes, at
-// 64 FLOP/clk/SIMD next to an idle VALU — the masks stay bit-identical to the VALU kernel's by construction (k ascending, zero
-// padded tails add +0).  Block = 4 waves (2 x 2), wave tile = WM x WN MFMA tiles of 32 x 32; K in 16-wide LDS tiles, k-major
-// ([k][m]: a fragment read is 32 consecutive floats per k -> conflict-free ds_read_b32).
+// C[m][n] = sum_k A[m][k] * (TRANSB ? B[n][k] : B[k][n]); EXP: C = exp(C / T).  On the fp32 matrix cores (round 3):
+// v_mfma_f32_32x32x2_f32 is bit-for-bit a k-ordered fmaf chain (guide §3 "FP32-input MFMA": one rounding per product, no wider
+// accumulation), i.e. EXACTLY the chain acc = fmaf(A[m][k], B(k, n), acc) over k = 0, 1, ..., K - 1 (the arithmetic of the VALU SGEMM of rounds 1-2),
+// at 64 FLOP/clk/SIMD next to an idle VALU (k ascending, zero padded tails add +0).  Block = 4 waves (2 x 2), wave tile = WM x WN MFMA
+// tiles of 32 x 32; K in 32-wide LDS tiles, k-major ([k][m]: a fragment read is 32 consecutive floats per k -> conflict-free ds_read_b32).
 typedef float f16v __attribute__((ext_vector_type(16)));
 template <bool TRANSB, bool EXP, int WM, int WN>
 __global__ __launch_bounds__(256) void sgemm_mfma_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -285,20 +233,6 @@ __global__ __launch_bounds__(1024) void topk_normalize_kernel(float* __restrict_
     }
 }
 
-// A/B path only (UNIVST_MASKPROP_MFMA=0): rebuild the dense normalised column from the survivor list for the dense label GEMM
-__global__ void densify_kernel(float* __restrict__ aff, int Nsrc, int hw, const int* __restrict__ cnt, const int* __restrict__ idx,
-                               const float* __restrict__ val) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= hw || cnt[i] < 0) return;
-    const int n = cnt[i];
-    for (int j = blockIdx.y; j < Nsrc; j += gridDim.y) {
-        float v = 0.f;
-        for (int e = 0; e < n; ++e)
-            if (idx[(long)i * MP_CAP + e] == j) v = val[(long)i * MP_CAP + e];
-        aff[(long)j * hw + i] = v;
-    }
-}
-
 // [ncls][Nsrc] -> [Nsrc][ncls] (32 x 32 LDS tiles): a source row's class vector becomes 1 KB of contiguous memory
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int Cc) {
     __shared__ float tile[32][33];
@@ -436,10 +370,7 @@ int uv_launch_maskprop_frame(const float* feat_tar, const float* feat_src, const
     float* aff = (float*)w;
     hipLaunchKernelGGL(rownorm_kernel, dim3((hw + 3) / 4), dim3(256), 0, s, feat_tar, tn, hw, C);
     hipLaunchKernelGGL(rownorm_kernel, dim3((Nsrc + 3) / 4), dim3(256), 0, s, feat_src, sn, Nsrc, C);
-    // UNIVST_MASKPROP_MFMA=0 (A/B aid): the fp32 VALU SGEMMs and the dense label product of rounds 1-2 (bit-identical results)
-    static const int mfma = getenv("UNIVST_MASKPROP_MFMA") ? atoi(getenv("UNIVST_MASKPROP_MFMA")) : 1;
-    if (mfma) hipLaunchKernelGGL((sgemm_mfma_kernel<true, true, 2, 2>), dim3((hw + 127) / 128, (Nsrc + 127) / 128), dim3(256), 0, s, sn, tn, aff, Nsrc, hw, C, T);
-    else hipLaunchKernelGGL((sgemm_kernel<true, true>), dim3((hw + 63) / 64, (Nsrc + 63) / 64), dim3(256), 0, s, sn, tn, aff, Nsrc, hw, C, T);
+    hipLaunchKernelGGL((sgemm_mfma_kernel<true, true, 2, 2>), dim3((hw + 127) / 128, (Nsrc + 127) / 128), dim3(256), 0, s, sn, tn, aff, Nsrc, hw, C, T);
     // stream-ordered scratch for the survivor lists and the transposed labels (their size depends on ncls, which the public
     // workspace query does not take)
     char* sc = nullptr;
@@ -450,16 +381,10 @@ int uv_launch_maskprop_frame(const float* feat_tar, const float* feat_src, const
     float* val = (float*)(sc + b_cnt + b_idx);
     float* segsT = (float*)(sc + b_cnt + b_idx + b_val);
     hipLaunchKernelGGL((topk_normalize_kernel<16>), dim3((hw + 63) / 64), dim3(1024), 0, s, aff, Nsrc, hw, topk, cnt, idx, val);
-    if (mfma) {
-        UV_REQUIRE((size_t)ncls * 65 * 4 <= 160 * 1024, "maskprop: ncls=%d too large for the label tile", ncls);
-        hipLaunchKernelGGL(transpose_kernel, dim3((Nsrc + 31) / 32, (ncls + 31) / 32), dim3(256), 0, s, segs_src, segsT, ncls, Nsrc);
-        hipLaunchKernelGGL(sparse_label_kernel, dim3((hw + 63) / 64), dim3(256), (size_t)ncls * 65 * 4, s, segsT, segs_src, aff, cnt, idx, val, segs_tar,
-                           ncls, hw, Nsrc);
-    } else {
-        hipLaunchKernelGGL(densify_kernel, dim3((hw + 63) / 64, 64), dim3(64), 0, s, aff, Nsrc, hw, cnt, idx, val);
-        hipLaunchKernelGGL((sgemm_kernel<false, false>), dim3((hw + 63) / 64, (ncls + 63) / 64), dim3(256), 0, s, segs_src, aff, segs_tar,
-                           ncls, hw, Nsrc, 1.f);
-    }
+    UV_REQUIRE((size_t)ncls * 65 * 4 <= 160 * 1024, "maskprop: ncls=%d too large for the label tile", ncls);
+    hipLaunchKernelGGL(transpose_kernel, dim3((Nsrc + 31) / 32, (ncls + 31) / 32), dim3(256), 0, s, segs_src, segsT, ncls, Nsrc);
+    hipLaunchKernelGGL(sparse_label_kernel, dim3((hw + 63) / 64), dim3(256), (size_t)ncls * 65 * 4, s, segsT, segs_src, aff, cnt, idx, val, segs_tar,
+                       ncls, hw, Nsrc);
     (void)hipFreeAsync(sc, s);
     UV_LAUNCH_CHECK();
     return UV_OK;

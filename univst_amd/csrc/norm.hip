@@ -9,7 +9,6 @@
 // Replaces: resnet.py:338,369 + unet_3d_condition.py:439 (5-D GroupNorm eps 1e-5 + SiLU),
 // attention.py:69-71,121 (per-frame GroupNorm eps 1e-6), attention.py:289-343 (LayerNorms).
 #include "common.h"
-#include <stdlib.h>
 #include "kernels.h"
 
 namespace {
@@ -425,7 +424,7 @@ int uv_launch_groupnorm(const half_t* s1, const half_t* s2, int C1, int C2, long
     UV_REQUIRE(rows % rows_per_stat == 0, "groupnorm: rows=%ld not a multiple of rows_per_stat=%d", rows, rows_per_stat);
     const int S = (int)(rows / rows_per_stat);
     // small tensors: one launch (statistics + apply in the block that owns the (unit, group)), or statistics only when they are summed over ranks
-    static const long small_bytes = getenv("UNIVST_GN_SMALL") ? atol(getenv("UNIVST_GN_SMALL")) : (4L << 20);
+    constexpr long small_bytes = 4L << 20;
     const bool sharded_stats = comm && comm->world > 1;
     // producer statistics are usable when every source has them and the groups are whole runs of 10-channel sub-groups
     if (pre_part && !((!s2 || pre_part2) && (C / G) % 10 == 0 && C1 % 10 == 0 && C2 % 10 == 0 && rows_per_stat % 16 == 0)) pre_part = nullptr;

@@ -69,7 +69,7 @@ __global__ void geglu_interleave_kernel(const half_t* __restrict__ in, half_t* _
     int src = j < 16 ? 16 * q + j : rows / 2 + 16 * q + (j - 16);
     out[i] = in[(long)src * cols + c];
 }
-// out[i] = fp16(in[i] * f): to_q weights with log2(e)/sqrt(head_dim) folded in (attention.hip, FOLD kernel)
+// out[i] = fp16(in[i] * f): to_q weights with log2(e)/sqrt(head_dim) folded in (attention.hip, attn_pp40_kernel)
 __global__ void scale_f16_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, long n, float f) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (half_t)((float)in[i] * f);
@@ -268,8 +268,7 @@ int UNet::comm_streams() {
     if (xstream) return UV_OK;
     int lo = 0, hi = 0;                         // (numerically lowest = greatest priority): the exchange's few kernels go ahead of the queued compute
     UV_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    static const int prio_env = getenv("UNIVST_XSTREAM_PRIO") ? atoi(getenv("UNIVST_XSTREAM_PRIO")) : 1;      // 0: default priority (A/B aid)
-    UV_HIP(hipStreamCreateWithPriority(&xstream, hipStreamNonBlocking, prio_env ? hi : lo));
+    UV_HIP(hipStreamCreateWithPriority(&xstream, hipStreamNonBlocking, hi));
     UV_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     UV_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
     return UV_OK;
@@ -1016,11 +1015,10 @@ struct Fwd {
         // (round 4: also on the 128-wide kernel where that runs these linears without split-K — the 64x64 / 32x32 levels of a frame shard)
         const bool fold = u.ln_fold > 0 && C % 160 == 0 && uv_linear_fold_producer_ok(rows, C, C) && uv_linear_fold_consumer_ok(rows, 3 * C, C, false) &&
                           uv_linear_fold_consumer_ok(rows, C, C, false);
-        // norm3 with the statistics from a 128-wide producer: UNIVST_LN_FOLD_SMALL=1 leaves it a LayerNorm launch (A/B: emulated rank of 8,
-        // F = 16: 12.83 ms per step without the 128-wide fold, 12.81 with norm1 / norm2 only, 12.70 with all three)
-        static const int fold_small = getenv("UNIVST_LN_FOLD_SMALL") ? atoi(getenv("UNIVST_LN_FOLD_SMALL")) : 2;
+        // norm3 is folded also with the statistics from a 128-wide producer (A/B: emulated rank of 8, F = 16: 12.83 ms per step
+        // without the 128-wide fold, 12.81 with norm1 / norm2 only, 12.70 with all three)
         const bool xres3 = u.find(b + ".ff.net.0.proj.weight#xres") != nullptr && uv_geglu_xres_ok(8 * C, C, rows);
-        const bool fold3 = fold && u.ln_fold > 1 && (xres3 || uv_linear_fold_consumer_ok(rows, 8 * C, C, true)) && (fold_small > 1 || uv_linear_takes_big_direct(rows, C, C));
+        const bool fold3 = fold && u.ln_fold > 1 && (xres3 || uv_linear_fold_consumer_ok(rows, 8 * C, C, true));
         float* lnst = fold ? (float*)alloc(rows * (C / 160) * 4) : nullptr;      // [rows][C/160][2] fp32
         if (fold && !lnst) return UV_ERR_STATE;
         RUN(linear(gnf ? x.p : t0, C, rows, C, wpi, p + ".proj_in.bias", C, h, C, nullptr, 0, nullptr, 0, lnst, nullptr, nullptr, wsets, b32, N));

@@ -1,7 +1,12 @@
 // Point-matching mask propagation on the GPU (fp32 like the reference's .float() features).
 //   aff[j][i]  = exp( <tar_i/|tar_i|, src_j/|src_j|> / T )            [Nsrc, hw]
-//   keep entries >= the top-k-th value of their column, column-normalise, segs_tar = segs_src @ aff
-//   finalize: bilinear up to HxW (torch align_corners=False), per-class min-max, FIRST-max argmax, !=0 -> 255
+//   keep entries >= the top-k-th value of their column (ALL of them: a tie at the threshold leaves more than k survivors, up
+//   to Nsrc when a zero target row makes every affinity exp(0)), column-normalise, segs_tar = segs_src @ aff.  A column with up
+//   to MP_CAP = 32 survivors goes through a compact list, a longer one through the dense fallback; both run the same
+//   ascending-source-row fmaf chain.
+//   finalize: bilinear up to HxW (torch align_corners=False), per-class min-max of the classes whose max is > 0, arg-max as
+//   torch.max does it on the CPU (the first maximum; a NaN — a constant positive class is 0 / 0 after the min-max — counts as the
+//   maximum, the first one wins), != 0 -> 255
 // Replaces src/mask_propagation.py:72-83 (mask_propogation core) and :60-69 (upsample / norm_mask / argmax).
 // The random sub-sampling (:87-97, torch.randperm on the host RNG) stays on the host on purpose so that the
 // index stream is bit-identical to the reference's.
@@ -343,7 +348,9 @@ __global__ __launch_bounds__(256) void argmax_mask_kernel(const float* __restric
             v = v - mn;
             v = v / (mx - mn);
         }
-        if (v > best) {                       // strict '>' keeps the FIRST maximum (torch.max on CPU)
+        // torch.max on the CPU: the FIRST maximum (strict '>'), and a NaN is the maximum — the first NaN class is taken and
+        // then kept (best != best lets nothing in).  norm_mask makes one: a constant positive class is 0 / 0 after the rescale.
+        if (best == best && (v > best || v != v)) {
             best = v;
             bi = c;
         }
@@ -361,7 +368,9 @@ int64_t uv_maskprop_workspace_bytes(int hw, int Nsrc, int C) {
 
 int uv_launch_maskprop_frame(const float* feat_tar, const float* feat_src, const float* segs_src, float* segs_tar, int hw,
                              int Nsrc, int C, int ncls, float T, int topk, void* ws, hipStream_t s) {
-    UV_REQUIRE(topk >= 1 && topk <= 16 && topk <= Nsrc, "maskprop: topk=%d must be in 1..16 and <= Nsrc", topk);
+    UV_REQUIRE(hw >= 1 && Nsrc >= 1 && C >= 1 && ncls >= 1, "maskprop: hw=%d, Nsrc=%d, C=%d, ncls=%d must all be >= 1", hw, Nsrc, C, ncls);
+    UV_REQUIRE(topk >= 1 && topk <= 16 && topk <= Nsrc, "maskprop: topk=%d must be in 1..16 and <= Nsrc=%d", topk, Nsrc);
+    UV_REQUIRE((size_t)ncls * 65 * 4 <= 160 * 1024, "maskprop: ncls=%d too large for the label tile", ncls);
     char* w = (char*)ws;
     float* tn = (float*)w;
     w += al((size_t)hw * C * 4);
@@ -381,7 +390,6 @@ int uv_launch_maskprop_frame(const float* feat_tar, const float* feat_src, const
     float* val = (float*)(sc + b_cnt + b_idx);
     float* segsT = (float*)(sc + b_cnt + b_idx + b_val);
     hipLaunchKernelGGL((topk_normalize_kernel<16>), dim3((hw + 63) / 64), dim3(1024), 0, s, aff, Nsrc, hw, topk, cnt, idx, val);
-    UV_REQUIRE((size_t)ncls * 65 * 4 <= 160 * 1024, "maskprop: ncls=%d too large for the label tile", ncls);
     hipLaunchKernelGGL(transpose_kernel, dim3((Nsrc + 31) / 32, (ncls + 31) / 32), dim3(256), 0, s, segs_src, segsT, ncls, Nsrc);
     hipLaunchKernelGGL(sparse_label_kernel, dim3((hw + 63) / 64), dim3(256), (size_t)ncls * 65 * 4, s, segsT, segs_src, aff, cnt, idx, val, segs_tar,
                        ncls, hw, Nsrc);

@@ -52,7 +52,9 @@ def _ws(nbytes, device):
 
 def mask_propogation(feat_src_rows, feat_tar, segs, args):
     """mask_propagation.py:72-99.  Layout differs from the reference only in that source features are kept
-    row-major [Nsrc, C] (the reference keeps [C, Nsrc]); returns (segs_tar, sampled feats [n, C], sampled segs)."""
+    row-major [Nsrc, C] (the reference keeps [C, Nsrc]); returns (segs_tar, sampled feats [n, C], sampled segs).  Like the
+    reference, a column keeps EVERY affinity >= its topk-th largest, so a tie at the threshold leaves more than topk sources
+    (all Nsrc of them for a zero target row).  topk must be in 1..16 and <= Nsrc: anything else raises."""
     lib = _native.load()
     hw, C_ = feat_tar.shape
     Nsrc, ncls = feat_src_rows.shape[0], segs.shape[0]
@@ -77,7 +79,9 @@ def mask_propogation(feat_src_rows, feat_tar, segs, args):
 
 
 def norm_argmax_mask(segs_tar, h, w, H, W):
-    """mask_propagation.py:60-69: bilinear up, norm_mask, argmax, != 0 -> 255; uint8 [H, W] on the device."""
+    """mask_propagation.py:60-69: bilinear up, norm_mask, argmax, != 0 -> 255; uint8 [H, W] on the device.  The arg-max is
+    torch.max's on the CPU: the first maximum wins, and so does the first NaN (norm_mask turns a constant positive class into
+    0 / 0 = NaN: such a class takes every pixel)."""
     lib = _native.load()
     ncls = segs_tar.shape[0]
     out = torch.empty(H, W, dtype=torch.uint8, device=segs_tar.device)

@@ -173,6 +173,35 @@ int univst_vae_decode(univst_vae* h, const void* z, int64_t imgs, int num_frames
  * (mean | logvar; sampling stays with the caller, which owns the RNG) */
 int univst_vae_encode(univst_vae* h, const void* x, int64_t imgs, int H, int W, void* moments, void* stream);
 
+/* ------------------------------------------------------------------ RAFT-large optical flow handle (the `flow_fn` of src/cal_optica_flow.py)
+ * The flow estimator behind get_warp (cal_optica_flow.py:51-99) and the sliding-window smoother (stable_diffusion.py:731-747): torchvision's
+ * raft_large as one graph of gfx950 kernels per image pair (12 flow updates, final flow only, eval mode).  THIRD-PARTY network, restated from its
+ * published definition with that model's state-dict keys (csrc/raft.hip); parity unpinned by the reference. */
+typedef struct univst_raft univst_raft;
+int univst_raft_create(univst_raft** out);
+int univst_raft_destroy(univst_raft* h);
+/* key = torchvision state-dict name ("feature_encoder.layer2.0.downsample.0.weight", "update_block.flow_head.conv2.bias", ...); kept in fp32
+ * (the BatchNorm fold of the context encoder is done in fp32); the derived fp16 layouts are built by the first call that needs them */
+int univst_raft_load_tensor(univst_raft* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+/* img1, img2: uint8 [H, W, 3] (scaled by 1/255 inside: preprocess_image, cal_optica_flow.py:11-13) -> flow fp32 [H, W, 2] (x, y) from img1 to img2.
+ * H, W multiples of 8, at least 128.  The workspace is allocated by the first call at a size; later calls at that size neither allocate nor sync. */
+int univst_raft_forward(univst_raft* h, const uint8_t* img1, const uint8_t* img2, int H, int W, float* flow, void* stream);
+/* stages of the same graph (tests, tools/bench_flow.py).  encode: both encoders -> fmap fp16 [2, N, 256] (image 1 | image 2; N = (H/8)(W/8) rows in
+ * y-major order), hidden fp32 [N, 128] = tanh half and context fp16 [N, 128] = relu half of the context encoder (outputs may be NULL).
+ * gru: one RecurrentBlock step (convgru1 1x5, convgru2 5x1) over [hidden | context | motion]: hidden fp32 [N, 128] in place, context / motion fp16 [N, 128]. */
+int univst_raft_encode(univst_raft* h, const uint8_t* img1, const uint8_t* img2, int H, int W, void* fmap, float* hidden, void* context, void* stream);
+int univst_raft_gru(univst_raft* h, float* hidden, const void* context, const void* motion, int fh, int fw, void* stream);
+/* corr[i][j] = <fmap1[i], fmap2[j]> / 16 (fmaps fp16 [N, 256]) and its 2x2-average-pooled levels (floor), fp32, level l at
+ * [N][fh >> l][fw >> l] behind the levels before it: univst_raft_pyramid_floats(fh, fw) floats in all */
+int64_t univst_raft_pyramid_floats(int fh, int fw);
+int univst_raft_corr_pyramid(const void* fmap1, const void* fmap2, int fh, int fw, float* pyramid, void* stream);
+/* radius-4 lookup at coords fp32 [N, 2] (x, y): channel l*81 + a*9 + b = level l sampled bilinearly (zeros outside) at x / 2^l + (a - 4),
+ * y / 2^l + (b - 4).  out_f32 [N, 324] and / or out_f16 [N, 328] (the row the 1x1 conv behind it reads; 4 zero columns) */
+int univst_raft_corr_lookup(const float* pyramid, const float* coords, int fh, int fw, float* out_f32, void* out_f16, void* stream);
+/* flow fp32 [fh, fw, 2], mask fp16 [N, 576] (the mask predictor's conv output BEFORE its factor 0.25; channel k*64 + i*8 + j) -> out fp32
+ * [8 fh, 8 fw, 2]: softmax over the 9 taps k of each sub-pixel (i, j) applied to the 3x3 neighbourhood (zero padded) of 8 * flow */
+int univst_raft_convex_upsample(const float* flow, const void* mask, int fh, int fw, float* out, void* stream);
+
 /* ------------------------------------------------------------------ stand-alone operators (also used by tests) */
 /* Y[M,N] = X[M,K] W[N,K]^T + bias + residual; geglu != 0: the diffusers GEGLU projection (FeedForward net[0], attention.py:241) — writes the
  * N/2 columns x * gelu(gate), W / bias rows pre-interleaved: geglu = 1 in blocks of [16 x rows | 16 gate rows] (any K), geglu = 2 in the

@@ -81,6 +81,16 @@ SIGNATURES = {
     "univst_vae_finalize": (_I, [_P, _P]),
     "univst_vae_decode": (_I, [_P, _P, _L, _I, _I, _I, _P, _P]),
     "univst_vae_encode": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "univst_raft_create": (_I, [C.POINTER(_P)]),
+    "univst_raft_destroy": (_I, [_P]),
+    "univst_raft_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),
+    "univst_raft_forward": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "univst_raft_encode": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "univst_raft_gru": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "univst_raft_pyramid_floats": (_L, [_I, _I]),
+    "univst_raft_corr_pyramid": (_I, [_P, _P, _I, _I, _P, _P]),
+    "univst_raft_corr_lookup": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "univst_raft_convex_upsample": (_I, [_P, _P, _I, _I, _P, _P]),
     "univst_attn2_fused_workspace_bytes": (_L, [_I, _I, _I]),
     "univst_attn12_fused": (_I, [_P, _L, _P, _P, _P, _L, _F, _P, _P, _P, _I, _P, _I, _I, _L, _P, _P, _P, _L, _L, _I, _I, _P, _P, _P]),
     "univst_attn2_fused": (_I, [_P, _L, _P, _F, _P, _P, _P, _I, _P, _I, _I, _L, _P, _P, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P]),

@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "unet.h"
 #include "vae.h"
+#include "raft.h"
 
 static thread_local char g_err[1024] = "";
 void uv_set_error(const char* fmt, ...) {
@@ -221,6 +222,62 @@ int univst_vae_decode(univst_vae* h, const void* z, int64_t imgs, int num_frames
 int univst_vae_encode(univst_vae* h, const void* x, int64_t imgs, int Hh, int W, void* moments, void* s) {
     UV_REQUIRE(h && x && moments, "vae_encode: null argument");
     return h->impl.encode(H(x), imgs, Hh, W, HM(moments), S(s));
+}
+struct univst_raft {
+    Raft impl;
+};
+int univst_raft_create(univst_raft** out) {
+    UV_REQUIRE(out, "raft_create: null argument");
+    univst_raft* h = new (std::nothrow) univst_raft();
+    UV_REQUIRE(h, "raft_create: out of host memory");
+    *out = h;
+    return UV_OK;
+}
+int univst_raft_destroy(univst_raft* h) {
+    delete h;
+    return UV_OK;
+}
+int univst_raft_load_tensor(univst_raft* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
+}
+int univst_raft_forward(univst_raft* h, const uint8_t* img1, const uint8_t* img2, int Hh, int W, float* flow, void* s) {
+    UV_REQUIRE(h && img1 && img2 && flow, "raft_forward: null argument");
+    return h->impl.forward(img1, img2, Hh, W, flow, S(s));
+}
+int univst_raft_encode(univst_raft* h, const uint8_t* img1, const uint8_t* img2, int Hh, int W, void* fmap, float* hidden, void* context, void* s) {
+    UV_REQUIRE(h && img1 && img2, "raft_encode: null argument");
+    int rc = h->impl.encode(img1, img2, Hh, W, S(s));
+    if (rc) return rc;
+    const size_t N = (size_t)(Hh / 8) * (W / 8);
+    if (fmap) UV_HIP(hipMemcpyAsync(fmap, h->impl.fmap, 2 * N * 256 * 2, hipMemcpyDeviceToDevice, S(s)));
+    if (hidden) UV_HIP(hipMemcpyAsync(hidden, h->impl.h32, N * 128 * 4, hipMemcpyDeviceToDevice, S(s)));
+    if (context) UV_HIP(hipMemcpyAsync(context, h->impl.ctx16, N * 128 * 2, hipMemcpyDeviceToDevice, S(s)));
+    return UV_OK;
+}
+int univst_raft_gru(univst_raft* h, float* hidden, const void* context, const void* motion, int fh, int fw, void* s) {
+    UV_REQUIRE(h && hidden && context && motion, "raft_gru: null argument");
+    UV_REQUIRE(fh >= 16 && fw >= 16 && fh <= 512 && fw <= 512, "raft_gru: feature map %d x %d (at least 16 x 16)", fh, fw);
+    if (!h->impl.finalized) {
+        int rc = h->impl.finalize(S(s));
+        if (rc) return rc;
+    }
+    int rc = h->impl.reserve(fh * 8, fw * 8);
+    if (rc) return rc;
+    return h->impl.gru(hidden, h->impl.h16, H(context), H(motion), fh, fw, S(s));
+}
+int64_t univst_raft_pyramid_floats(int fh, int fw) { return fh > 0 && fw > 0 ? uv_raft_pyramid_floats(fh, fw) : 0; }
+int univst_raft_corr_pyramid(const void* f1, const void* f2, int fh, int fw, float* pyr, void* s) {
+    UV_REQUIRE(f1 && f2 && pyr, "raft_corr_pyramid: null argument");
+    return uv_raft_corr_pyramid(H(f1), H(f2), fh, fw, pyr, S(s));
+}
+int univst_raft_corr_lookup(const float* pyr, const float* coords, int fh, int fw, float* out32, void* out16, void* s) {
+    UV_REQUIRE(pyr && coords, "raft_corr_lookup: null argument");
+    return uv_raft_corr_lookup(pyr, coords, fh, fw, out32, HM(out16), S(s));
+}
+int univst_raft_convex_upsample(const float* flow, const void* mask, int fh, int fw, float* out, void* s) {
+    UV_REQUIRE(flow && mask && out, "raft_convex_upsample: null argument");
+    return uv_raft_convex_upsample(flow, 0, H(mask), fh, fw, out, S(s));
 }
 int univst_frag_pack(const void* W, void* out, int N, int K, void* s) {
     UV_REQUIRE(W && out, "frag_pack: null argument");

@@ -1,10 +1,10 @@
 """Mirror of src/cal_optica_flow.py of the reference + the sliding-window block of
 stable_diffusion.py:723-751, on the GPU (csrc/warp.hip).
 
-RAFT (torchvision ``raft_large`` + weights) is third-party and is NOT re-implemented: every entry takes a
-``flow_fn(img1_u8[H,W,3], img2_u8[H,W,3]) -> float32 [H,W,2]`` callable (device tensors).
-``make_raft_flow_fn`` builds one from torchvision when it is installed (model created ONCE, not once per
-call as the reference does, cal_optica_flow.py:53-55)."""
+Every entry takes a ``flow_fn(img1_u8[H,W,3], img2_u8[H,W,3]) -> float32 [H,W,2]`` callable (device tensors).
+``make_native_flow_fn`` builds one on the library's own RAFT-large (univst_amd/flow.py, csrc/raft.hip: torchvision's ``raft_large``
+restated, its checkpoint loaded as is); ``make_raft_flow_fn`` builds one from torchvision when it is installed (model created ONCE,
+not once per call as the reference does, cal_optica_flow.py:53-55)."""
 import ctypes as C
 
 import torch
@@ -22,6 +22,14 @@ def make_raft_flow_fn(device="cuda"):
         b = img2.permute(2, 0, 1).float().unsqueeze(0) / 255.0
         return model(a, b)[-1].squeeze(0).permute(1, 2, 0).contiguous()
     return flow_fn
+
+
+def make_native_flow_fn(path_or_state_dict, device="cuda"):
+    """the native RAFT-large as a ``flow_fn``: a torchvision ``raft_large`` checkpoint (``.pth`` / ``.safetensors`` path) or its state dict"""
+    from ..flow import NativeRAFT
+    if isinstance(path_or_state_dict, dict):
+        return NativeRAFT.from_state_dict(path_or_state_dict, device=device)
+    return NativeRAFT.from_file(path_or_state_dict, device=device)
 
 
 def warp_accumulate_(acc, key, now, fwd, bwd, threshold=1.5):

@@ -21,8 +21,11 @@ def smoother_kwargs(a, pipe, n_frames, hw=(64, 64)):
         return {}
     if not a.mask_path:
         raise SystemExit("--smoother needs --mask_path (stable_diffusion.py:751 composites the smoothed frames with the mask)")
-    from ..cal_optica_flow import make_raft_flow_fn, make_latent_flows
-    flow_fn = make_raft_flow_fn("cuda")          # torchvision raft_large + Raft_Large_Weights.DEFAULT (third-party, as in the reference)
+    from ..cal_optica_flow import make_raft_flow_fn, make_native_flow_fn, make_latent_flows
+    if getattr(a, "raft_ckpt", ""):              # the library's own RAFT-large on a torchvision raft_large checkpoint (no torchvision needed)
+        flow_fn = make_native_flow_fn(a.raft_ckpt, "cuda")
+    else:
+        flow_fn = make_raft_flow_fn("cuda")      # torchvision raft_large + Raft_Large_Weights.DEFAULT (third-party, as in the reference)
     if a.smoother == "pixel":
         return {"smoother": "pixel", "flow_fn": flow_fn}
     if not a.content_path:
@@ -66,6 +69,8 @@ def parser():
     p.add_argument("--smoother", choices=["none", "pixel", "latent"], default="none",
                    help="extra: sliding-window optical-flow smoothing on steps 20..24 (stable_diffusion.py:713-759; the reference hard-wires None)")
     p.add_argument("--content_path", type=str, default="", help="content frames (folder / .mp4) for --smoother latent")
+    p.add_argument("--raft_ckpt", type=str, default="",
+                   help="extra: torchvision raft_large checkpoint (.pth / .safetensors); both smoothers then run the native flow estimator instead of torchvision's")
     p.add_argument("--no_shard", action="store_true", help="under torchrun: keep every rank on the whole clip (no frame sharding)")
     return p
 

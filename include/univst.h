@@ -455,6 +455,39 @@ int univst_debug_tr16(float* out256, void* stream);
  * bytes / link rate when one rank of a multi-GPU job is emulated on a 1-GPU box */
 int univst_debug_delay_us(double us, void* stream);
 
+/* What the GEMM / conv launcher and the attention launcher would do for a problem, read out on the host: no GPU, no stream, no device pointers
+ * (every kernel-selection decision of the library is made by plain host code; tests/test_dispatch_plan.py holds it to a recorded table).  buf receives
+ *     <kernel symbol> grid=<blocks> block=<threads> splits=<s>[ +splitk_reduce]
+ * followed, for the GEMM, by the predicates the UNet graph consults for that shape:
+ *      big_direct=<0|1> fold_producer=<0|1> fold_consumer=<0|1> geglu_consumer=<0|1> geglu_xres=<0|1>
+ * or, with the launcher's non-zero return code, the launcher's error message.  Operands are 16-byte aligned with natural leading dimensions unless a flag
+ * says otherwise.  ncu: compute units to plan for (an MI355X has 256).
+ * gemm: mode 0 = linear [M, K] x [N, K]^T (geglu as univst_linear; rows_per_set > 0: weight sets with an fp32 bias, as univst_linear_sets);
+ *       mode 1 = conv over M images of Hs x Ws with C1 + C2 channels (K is derived), as univst_conv_nhwc, or with one of the VAE's geometries.
+ * M = N = 0 (Nq = Nkv = 0): buf receives the ';'-joined kernel symbols the launcher can launch. */
+#define UNIVST_PLAN_BIAS 1
+#define UNIVST_PLAN_RESIDUAL 2
+#define UNIVST_PLAN_ROWBIAS 4
+#define UNIVST_PLAN_LN_STATS 8        /* a LayerNorm folded into this linear (univst_linear_ln's ln_stats / ln_wsum / ln_bias) */
+#define UNIVST_PLAN_STATS_OUT 16      /* row statistics of the output (univst_linear_ln's stats_out) */
+#define UNIVST_PLAN_ACT 32            /* univst_linear_gated: GELU(tanh) */
+#define UNIVST_PLAN_GATE 64           /* univst_linear_gated: gate rows */
+#define UNIVST_PLAN_W32_ONLY 128      /* only the LDS-patch weight copy (univst_conv3x3_patch) */
+#define UNIVST_PLAN_W32 256           /* the LDS-patch weight copy beside the plain one (the UNet graph) */
+#define UNIVST_PLAN_GN_OUT 512        /* GroupNorm statistics of 10-channel sub-groups from the epilogue (the UNet graph) */
+#define UNIVST_PLAN_TAPINNER 1024     /* univst_conv_nhwc_tapinner's k order */
+#define UNIVST_PLAN_Y_UNALIGNED 2048  /* the output is 8 bytes off a 16-byte boundary */
+#define UNIVST_PLAN_WORKSPACE 4096    /* the caller holds the split-K workspace (the UNet graph, RAFT) */
+#define UNIVST_PLAN_GEOM_3X3 0        /* 3x3 with padding 1 (taps = 9) or 1x1 (taps = 1) */
+#define UNIVST_PLAN_GEOM_PAD_END 1    /* 3x3 over an input padded at the bottom / right only (the VAE encoder's stride-2 conv) */
+#define UNIVST_PLAN_GEOM_FRAME 2      /* 3x1 (taps = 3) over image rows = frames, image columns = pixels (the VAE's Conv3d (3,1,1)) */
+int univst_debug_gemm_plan(int ncu, int mode, int M, int N, int K, int geglu, int flags, int rows_per_set, int C1, int C2, int Hs, int Ws, int upsample,
+                           int stride, int taps, int geom, char* buf, int n);
+#define UNIVST_PLAN_SRC_LOGW 1        /* per-source log2 multiplicities */
+#define UNIVST_PLAN_EXTRA_KEYS 2      /* the extra key segment (77 text tokens of the SD3 joint attention) */
+/* phase 0: univst_attention; 1 / 2: the first / the merge launch of univst_attention_phase */
+int univst_debug_attention_plan(int BF, int heads, int Nq, int Nkv, int nsrc, int d, int q_prescaled, int flags, int phase, char* buf, int n);
+
 #ifdef __cplusplus
 }
 #endif

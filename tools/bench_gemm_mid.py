@@ -1,5 +1,5 @@
-"""mid-size linears / convs around the big-tile threshold (gemm.hip BIG_MIN_TILES) and the split-K choice; compare thresholds as two
-builds of the library (tools/ab.sh UNIVST_LIB=a,b)."""
+"""mid-size linears / convs around the big-tile threshold (BIG_MIN_TILES) and the split-K choice of the plan (csrc/gemm.hip uv_gemm_plan; what it picks for
+a shape: univst_debug_gemm_plan, tests/data/dispatch_plan.txt); compare thresholds as two builds of the library (tools/ab.sh UNIVST_LIB=a,b)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.bench_gemm import lin, conv_ti

@@ -1,6 +1,7 @@
 """Per-SHAPE table of one step from a rocprofv3 --kernel-trace CSV: launches of a kernel symbol are grouped by (symbol, grid size), i.e. by
 layer shape, and reported as launches per step, average duration and ms per step — the table DESIGN.md §4 quotes next to
-max(flops / 1 200 TF, bytes / 5 TB/s).
+max(flops / 1 200 TF, bytes / 5 TB/s).  Which (symbol, grid) a layer shape gets is decided by uv_gemm_plan / uv_attention_plan (csrc/gemm.hip,
+csrc/attention.hip); tests/data/dispatch_plan.txt records it for the shapes of a step, and the host-only univst_debug_*_plan entries print it for any shape.
 
     rocprofv3 --kernel-trace --output-format csv -d gpurun_out/trace -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-profile
     python tools/step_shapes.py gpurun_out/trace 12 [filter-regex]        # 12 = steps + warmup

@@ -133,6 +133,8 @@ SIGNATURES = {
     "univst_window_store": (_I, [_P, _F, _P, _L, _P]),
     "univst_debug_tr16": (_I, [_P, _P]),
     "univst_debug_delay_us": (_I, [C.c_double, _P]),
+    "univst_debug_gemm_plan": (_I, [_I] * 16 + [C.c_char_p, _I]),
+    "univst_debug_attention_plan": (_I, [_I] * 9 + [C.c_char_p, _I]),
     "univst_profile_enable": (_I, [_I]),
     "univst_profile_symbols": (_I, [_I, C.c_char_p, _I]),
     "univst_profile_collect": (_I, [C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),

@@ -478,6 +478,68 @@ int univst_mask_resize(const uint8_t* mask, void* out, int F, int Hh, int W, int
 }
 int univst_debug_tr16(float* out, void* s) { return uv_launch_tr16_probe(out, S(s)); }
 int univst_debug_delay_us(double us, void* s) { return uv_launch_delay_us(us, S(s)); }
+// host-only read-outs of the launch plans: stand-in operands (never dereferenced), 16-byte aligned with natural leading dimensions
+int univst_debug_gemm_plan(int ncu, int mode, int M, int N, int K, int geglu, int flags, int rows_per_set, int C1, int C2, int Hs, int Ws, int upsample,
+                           int stride, int taps, int geom, char* buf, int n) {
+    UV_REQUIRE(buf && n > 0 && ncu > 0, "debug_gemm_plan: null buffer or ncu <= 0");
+    if (M == 0 && N == 0) {
+        snprintf(buf, (size_t)n, "%s", uv_gemm_plan_symbols().c_str());
+        return UV_OK;
+    }
+    alignas(16) static float arena[8];                // an address to stand for every operand
+    half_t* const h = (half_t*)arena;
+    auto on = [&](int bit) { return (flags & bit) != 0; };
+    GemmParams g;
+    g.X = h; g.Y = on(UNIVST_PLAN_Y_UNALIGNED) ? h + 4 : h;
+    g.W = on(UNIVST_PLAN_W32_ONLY) ? nullptr : h;
+    g.W32 = on(UNIVST_PLAN_W32_ONLY) || on(UNIVST_PLAN_W32) ? h : nullptr;
+    g.N = N; g.geglu = geglu;
+    const int No = geglu ? N / 2 : N;
+    if (mode == 0) {
+        g.M = M; g.K = K; g.ldx = K;
+    } else {                                          // M: images
+        g.C1 = C1; g.C2 = C2; g.X2 = C2 ? h : nullptr; g.Hs = Hs; g.Ws = Ws; g.up = upsample ? 1 : 0; g.stride = stride; g.taps = taps;
+        const int He = Hs << g.up, We = Ws << g.up;
+        if (geom == UNIVST_PLAN_GEOM_FRAME) {         // the 3x1 frame conv: image rows = frames, image columns = pixels
+            g.tapw = 1; g.pady = 1; g.padx = 0; g.Ho = He; g.Wo = We;
+        } else if (geom == UNIVST_PLAN_GEOM_PAD_END) {    // input padded at the bottom / right only
+            g.tapw = 3; g.pady = g.padx = 0; g.Ho = (He + 1 - 3) / stride + 1; g.Wo = (We + 1 - 3) / stride + 1;
+        } else {
+            g.Ho = (He - 1) / stride + 1; g.Wo = (We - 1) / stride + 1;
+        }
+        g.M = M * g.Ho * g.Wo; g.K = taps * (C1 + C2);
+        g.korder = on(UNIVST_PLAN_TAPINNER) ? 1 : 0;
+    }
+    g.ldy = No; g.ldr = No;
+    if (on(UNIVST_PLAN_BIAS)) g.bias = h;
+    if (on(UNIVST_PLAN_RESIDUAL)) g.R = h;
+    if (on(UNIVST_PLAN_ROWBIAS)) g.rowbias = h;
+    if (on(UNIVST_PLAN_LN_STATS)) { g.ln_stats = arena; g.ln_wsum = arena; g.ln_bias = arena; g.ln_slots = g.K / 160; }
+    if (on(UNIVST_PLAN_STATS_OUT)) g.stats_out = arena;
+    if (on(UNIVST_PLAN_ACT)) g.act = 1;
+    if (on(UNIVST_PLAN_GATE)) { g.gate = h; g.ld_gate = N; }
+    if (on(UNIVST_PLAN_GN_OUT)) { g.gn_out = arena; g.gn_gw = 10; g.gn_G = N / 10; }
+    if (on(UNIVST_PLAN_WORKSPACE)) { g.partial = arena; g.partial_bytes = UV_SPLITK_WS_BYTES; }
+    if (rows_per_set > 0) { g.w_rows_per_set = rows_per_set; g.bias32 = arena; }
+    return uv_gemm_plan_text(g, mode, ncu, buf, n);
+}
+int univst_debug_attention_plan(int BF, int heads, int Nq, int Nkv, int nsrc, int d, int q_prescaled, int flags, int phase, char* buf, int n) {
+    UV_REQUIRE(buf && n > 0 && phase >= 0 && phase <= 2, "debug_attention_plan: null buffer or phase outside 0..2");
+    if (Nq == 0 && Nkv == 0) {
+        snprintf(buf, (size_t)n, "%s", uv_attention_plan_symbols().c_str());
+        return UV_OK;
+    }
+    alignas(16) static float arena[8];
+    half_t* const h = (half_t*)arena;
+    AttnParams a;
+    a.q = a.k = a.v = h; a.o = h; a.ldq = a.ldkv = a.ldo = (long)heads * d; a.src_idx = (const int*)arena;
+    a.nsrc = nsrc; a.BF = BF; a.Nq = Nq; a.Nkv = Nkv; a.heads = heads; a.d = d; a.q_prescaled = q_prescaled != 0;
+    if (flags & UNIVST_PLAN_SRC_LOGW) a.src_logw = arena;
+    if (flags & UNIVST_PLAN_EXTRA_KEYS) { a.kx = a.vx = h; a.x_idx = (const int*)arena; a.ldkv_x = a.ldkv; a.Nkv_x = 77; }
+    if (phase == 1) a.state_out = arena;
+    if (phase == 2) a.state_in = arena;
+    return uv_attention_plan_text(a, buf, n);
+}
 int univst_profile_enable(int on) {
     uv_prof_enable(on);
     return UV_OK;

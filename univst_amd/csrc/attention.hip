@@ -12,8 +12,9 @@
 // Softmax statistics in fp32, exp2 with the 1/sqrt(d)*log2(e) scale folded in.
 // Replaces: attention.py:384-420 (SparseCausalAttention gather + SDPA), pnp_utils.py:59-92 (PnP gather +
 // SDPA), diffusers AttnProcessor2_0 SDPA for attn2.
-#include "common.h"
+#include <string.h>
 
+#include "common.h"
 #include "kernels.h"
 
 namespace {
@@ -1607,167 +1608,148 @@ __global__ __launch_bounds__(256, 2) void attn_kernel_occ2(AttnParams p) {
     attn_body<DPAD, DV16, QB>(p);
 }
 
-// two-phase launches (AttnParams::state_out / state_in): their own instantiations (TP), so the epilogue of the one-launch kernels is untouched —
-// the pipelined head_dim-40 kernel for long sequences with prescaled q, the generic body otherwise
-template <int DPAD, int DV16, int TP>
-int launch_attn_tp(const AttnParams& p, hipStream_t stream) {
-    if constexpr (DPAD == 64 && DV16 == 3) {
-        if (p.q_prescaled && p.Nq >= 2048) {
-            const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_pp40_kernel<0, 1, true, TP>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    if constexpr (DPAD == 64 && DV16 == 4) {      // head_dim 64 (the SD3 joint attention of ranks > 0): the pipelined kernel, as launch_attn picks it
-        // (the text queries of a joint attention — 333 rows — take it too, in the merge phase even without the text-key segment)
-        if (p.q_prescaled && (p.Nq >= 1024 || ((p.kx || TP == 2) && p.Nq >= 192))) {
-            const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_pp64_kernel<0, TP>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    const int QB = p.Nq >= 512 ? 2 : 1;
-    const int nqb = (p.Nq + 64 * QB - 1) / (64 * QB);
-    dim3 grid(nqb * p.heads * p.BF), block(256);
-    if constexpr (DPAD >= 96) {
-        if (p.q_prescaled) {
-            if (QB == 2) {
-                if constexpr (DPAD == 96) hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2, true, TP>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 2, true, TP>), grid, block, 0, stream, p);
-            } else {
-                hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 1, true, TP>), grid, block, 0, stream, p);
-            }
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    if (QB == 2) {
-        if constexpr (DPAD <= 96) hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2, false, TP>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 2, false, TP>), grid, block, 0, stream, p);
-    } else {
-        hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 1, false, TP>), grid, block, 0, stream, p);
-    }
-    UV_LAUNCH_CHECK();
-    return UV_OK;
-}
-
-template <int DPAD, int DV16>
-int launch_attn(const AttnParams& p, hipStream_t stream) {
-    if (p.state_out) return launch_attn_tp<DPAD, DV16, 1>(p, stream);
-    if (p.state_in) return launch_attn_tp<DPAD, DV16, 2>(p, stream);
-    if constexpr (DPAD == 64 && DV16 == 3) {
-        // head_dim 40 with prescaled q: the software-pipelined kernel with scale / max folded into the MFMA (plain q takes attn_body)
-        if (!p.kx && p.Nq >= 2048 && p.q_prescaled) {
-            const int nqb4 = (p.Nq + 255) / 256;
-            // one short source (81..128 keys, or weighted by src_logw: what attn_text_kernel declines): the register-staged ring under its own symbol;
-            // otherwise the K/V ring filled by LDS-DMA + one wave-wide reference test + 16-wide second k step
-            if (p.nsrc == 1 && p.Nkv <= 128) hipLaunchKernelGGL((attn_pp40_kernel<1>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            else hipLaunchKernelGGL((attn_pp40_kernel<0, 1, true>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    if constexpr (DPAD == 64 && DV16 == 4) {
-        // head_dim 64 with prescaled q (the SD3 joint attention folds the factor into the q RMSNorm weight): software-pipelined kernel,
-        // also for the text queries of a joint attention — 333 rows over 12 621 keys — which otherwise take the generic body
-        // (round 4: SD3.5 step 944 / 947 -> 934 / 943 ms, same box)
-        if (p.q_prescaled && (p.Nq >= 1024 || (p.kx && p.Nq >= 192))) {
-            const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_pp64_kernel<0>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    // (head_dim 80 keeps the generic body: round 5 measured the pipelined kernel at 32 query rows per wave there — two waves per SIMD
-    // where attn_kernel_occ3 runs three, and with 44 MFMAs per wave between two tile barriers the third wave hides more than the leaner
-    // instruction stream saves: the 32x32-level attention of the full step 2.18 -> 2.27 ms.)
-    if constexpr (DPAD <= 64) {
-        if (p.Nq >= 2048) {         // 64 query rows per wave for long sequences
-            const int nqb4 = (p.Nq + 255) / 256;
-            hipLaunchKernelGGL((attn_kernel_occ2<DPAD, DV16, 4>), dim3(nqb4 * p.heads * p.BF), dim3(256), 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    const int QB = p.Nq >= 512 ? 2 : 1;
-    const int nqb = (p.Nq + 64 * QB - 1) / (64 * QB);
-    dim3 grid(nqb * p.heads * p.BF), block(256);
-    if constexpr (DPAD >= 96) {
-        // prescaled q on the wide heads (80, 160: the 32x32 / 16x16 levels of SD-v1.5): the reference rides in the MFMA accumulator, row sums by
-        // v_dot2 (attn_body CF)
-        if (p.q_prescaled) {
-            if constexpr (DPAD == 96) {
-                if (QB == 2) hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 1, true>), grid, block, 0, stream, p);
-            } else {
-                if (QB == 2) hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 2, true>), grid, block, 0, stream, p);
-                else hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 1, true>), grid, block, 0, stream, p);
-            }
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    if constexpr (DPAD <= 96) {           // (not instantiated for wider heads: at 168 VGPRs they spill, and a spilled prefetch
-        if (QB == 2) {                    //  register is read before its asm load has landed — tests/test_asm_hazards.py)
-            hipLaunchKernelGGL((attn_kernel_occ3<DPAD, DV16, 2>), grid, block, 0, stream, p);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
-    }
-    if (QB == 2) hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 2>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((attn_kernel<DPAD, DV16, 1>), grid, block, 0, stream, p);
-    UV_LAUNCH_CHECK();
-    return UV_OK;
-}
+// Instantiated and never launched: for heads up to 80 wide a 128-query block goes to attn_kernel_occ3, so the two-query-block attn_kernel
+// of these widths has no way in.  Kept (and kept out of the launch table) so that the code object holds the kernels it always held.
+template __global__ void attn_kernel<32, 1, 2>(AttnParams);
+template __global__ void attn_kernel<32, 2, 2>(AttnParams);
+template __global__ void attn_kernel<64, 3, 2>(AttnParams);
+template __global__ void attn_kernel<64, 4, 2>(AttnParams);
+template __global__ void attn_kernel<96, 5, 2>(AttnParams);
 
 }  // namespace
 
-static int attn_dispatch(const AttnParams& p, hipStream_t stream);
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The launch table: every kernel instantiation uv_attention_plan can name, ONCE.  The key is the symbol as a kernel trace spells it
+// (template arguments in full, no spaces); the plan composes that string and the launcher looks it up here.
+// attn_kernel / attn_kernel_occ3<DPAD, DV16, QB (64-query blocks per thread block), CF (prescaled q: reference in the MFMA accumulator), TP (phase)>
+struct AttnKernel {
+    void (*fn)(AttnParams);
+    const char* sym;
+};
+#define UV_KERNEL(...) {__VA_ARGS__, #__VA_ARGS__}
+#define UV_GENERIC(D, V, CF, TP) UV_KERNEL(attn_kernel<D,V,1,CF,TP>), UV_KERNEL(attn_kernel_occ3<D,V,2,CF,TP>)      /* heads up to 80 wide: three blocks per CU at QB = 2 */
+#define UV_GENERIC_160(CF, TP) UV_KERNEL(attn_kernel<160,10,1,CF,TP>), UV_KERNEL(attn_kernel<160,10,2,CF,TP>)       /* (at 168 VGPRs occ3 would spill, and a spilled prefetch register is read before its asm load has landed — tests/test_asm_hazards.py) */
+#define UV_PHASE(TP)                                                                                                              \
+    UV_GENERIC(32, 1, false, TP), UV_GENERIC(32, 2, false, TP), UV_GENERIC(64, 3, false, TP), UV_GENERIC(64, 4, false, TP),      \
+    UV_GENERIC(96, 5, false, TP), UV_GENERIC(96, 5, true, TP), UV_GENERIC_160(false, TP), UV_GENERIC_160(true, TP),              \
+    UV_KERNEL(attn_pp40_kernel<0,1,true,TP>), UV_KERNEL(attn_pp64_kernel<0,TP>)
+static const AttnKernel ATTN_KERNELS[] = {
+    UV_PHASE(0), UV_PHASE(1), UV_PHASE(2),
+    // one-launch attention only
+    UV_KERNEL(attn_text_kernel<40>), UV_KERNEL(attn_text_kernel<80>), UV_KERNEL(attn_pp40_kernel<1,0,false,0>),
+    UV_KERNEL(attn_kernel_occ2<32,1,4>), UV_KERNEL(attn_kernel_occ2<32,2,4>), UV_KERNEL(attn_kernel_occ2<64,3,4>), UV_KERNEL(attn_kernel_occ2<64,4,4>),
+};
+#undef UV_PHASE
+#undef UV_GENERIC_160
+#undef UV_GENERIC
+#undef UV_KERNEL
 
-int uv_launch_attention(const AttnParams& p0, hipStream_t stream) {
-    AttnParams p = p0;
-    p.order = 1;                          // head-major block order (the kernels read it)
-    UV_REQUIRE(p.d % 8 == 0, "attention: head_dim=%d must be a multiple of 8", p.d);
-    UV_REQUIRE(p.nsrc >= 1 && p.Nkv >= 1 && p.Nq >= 1, "attention: empty problem");
-    UV_REQUIRE(p.ldq % 8 == 0 && p.ldkv % 8 == 0 && p.ldo % 4 == 0, "attention: row strides must be multiples of 8");
-    UV_REQUIRE(!p.kx || (p.vx && p.x_idx && p.Nkv_x >= 1 && p.ldkv_x % 8 == 0), "attention: extra key segment needs vx, x_idx, Nkv_x >= 1 and a row stride that is a multiple of 8");
-    UV_REQUIRE(!(p.state_out && p.state_in), "attention: a launch is the first phase (state_out) or the merge phase (state_in) of a two-phase attention, not both");
+// THE selection policy of the attention kernels, one tree for one-launch attention (phase 0) and the two launches of a two-phase attention
+// (1: state_out, 2: state_in / merge).  Plain host code: no HIP call, pointers looked at for null only.
+AttnPlan uv_attention_plan(const AttnParams& p) {
+    AttnPlan pl;
+    UV_PLAN_REQUIRE(pl, p.d % 8 == 0, "attention: head_dim=%d must be a multiple of 8", p.d);
+    UV_PLAN_REQUIRE(pl, p.nsrc >= 1 && p.Nkv >= 1 && p.Nq >= 1, "attention: empty problem");
+    UV_PLAN_REQUIRE(pl, p.ldq % 8 == 0 && p.ldkv % 8 == 0 && p.ldo % 4 == 0, "attention: row strides must be multiples of 8");
+    UV_PLAN_REQUIRE(pl, !p.kx || (p.vx && p.x_idx && p.Nkv_x >= 1 && p.ldkv_x % 8 == 0), "attention: extra key segment needs vx, x_idx, Nkv_x >= 1 and a row stride that is a multiple of 8");
+    UV_PLAN_REQUIRE(pl, !(p.state_out && p.state_in), "attention: a launch is the first phase (state_out) or the merge phase (state_in) of a two-phase attention, not both");
+    const int tp = p.state_out ? 1 : (p.state_in ? 2 : 0);
+    const bool short_src = p.nsrc == 1 && p.Nkv <= 128;        // one short source: the text cross-attention
     const double nkv = (double)p.nsrc * p.Nkv;
-    const int cls = (p.nsrc == 1 && p.Nkv <= 128) ? UV_CLS_ATTN_TEXT
-                    : (p.d == 40 && p.Nq >= 2048) ? UV_CLS_ATTN_D40 : (p.d == 80 ? UV_CLS_ATTN_D80 : UV_CLS_ATTN_OTHER);
+    pl.cls = short_src ? UV_CLS_ATTN_TEXT : (p.d == 40 && p.Nq >= 2048) ? UV_CLS_ATTN_D40 : (p.d == 80 ? UV_CLS_ATTN_D80 : UV_CLS_ATTN_OTHER);
     // (a two-phase attention is ONE algorithmic attention over the reference's key set: the first phase is charged its flops, the merge phase none —
     // the host does not know how the sources split between the two)
-    uv_prof_begin(cls, p.state_in ? 0.0 : 4.0 * p.BF * p.heads * (double)p.Nq * nkv * p.d,
-                  2.0 * p.BF * p.heads * p.d * (2.0 * p.Nq + (p.state_in ? 0.0 : 2.0 * nkv)), stream);
-    int rc = attn_dispatch(p, stream);
-    uv_prof_end(stream);
-    return rc;
+    pl.flops = tp == 2 ? 0.0 : 4.0 * p.BF * p.heads * (double)p.Nq * nkv * p.d;
+    pl.bytes = 2.0 * p.BF * p.heads * p.d * (2.0 * p.Nq + (tp == 2 ? 0.0 : 2.0 * nkv));
+    const unsigned per_q = (unsigned)(p.heads * p.BF);          // blocks per block of queries
+    // text cross-attention: one short source, K/V held in registers (attn_text_kernel)
+    if (!p.kx && tp == 0 && p.nsrc == 1 && p.Nkv <= 80 && !p.src_logw && (p.d == 40 || p.d == 80) && p.Nq >= 256) {
+        snprintf(pl.sym, sizeof pl.sym, "attn_text_kernel<%d>", p.d);
+        pl.grid = (unsigned)((p.Nq + 1023) / 1024) * per_q;
+        return pl;
+    }
+    int dpad = 0;          // head_dim padded to what the generic body is instantiated for; DV16 = d / 16 rounded up
+    switch (p.d) {
+        case 16: case 32: dpad = 32; break;
+        case 40: case 64: dpad = 64; break;
+        case 80: dpad = 96; break;
+        case 160: dpad = 160; break;
+        default:
+            snprintf(pl.err, sizeof pl.err, "attention: head_dim=%d not instantiated (16,32,40,64,80,160)", p.d);
+            pl.rc = UV_ERR_UNSUPPORTED;
+            return pl;
+    }
+    const int dv16 = (p.d + 15) / 16;
+    pl.grid = (unsigned)((p.Nq + 255) / 256) * per_q;           // the pipelined and occ2 kernels: 256 queries per block
+    // head_dim 40 with prescaled q, long sequences: the software-pipelined kernel with scale / max folded into the MFMA (plain q takes attn_body)
+    if (p.d == 40 && p.q_prescaled && p.Nq >= 2048 &&
+        (tp != 0 || !p.kx)) {                   // one-launch only: the extra key segment keeps the generic body (the two-phase test never asked)
+        // one short source (81..128 keys, or weighted by src_logw: what attn_text_kernel declines): the register-staged ring under its own symbol;
+        // otherwise the K/V ring filled by LDS-DMA + one wave-wide reference test + 16-wide second k step
+        if (tp == 0 && short_src) snprintf(pl.sym, sizeof pl.sym, "attn_pp40_kernel<1,0,false,0>");       // one-launch only: it has no two-phase instantiation
+        else snprintf(pl.sym, sizeof pl.sym, "attn_pp40_kernel<0,1,true,%d>", tp);
+        return pl;
+    }
+    // head_dim 64 with prescaled q (the SD3 joint attention folds the factor into the q RMSNorm weight): software-pipelined kernel,
+    // also for the text queries of a joint attention — 333 rows over 12 621 keys — which otherwise take the generic body
+    if (p.d == 64 && p.q_prescaled &&
+        (p.Nq >= 1024 || ((p.kx || tp == 2) && p.Nq >= 192))) {      // merge phase only: short query blocks take it even without the text-key segment
+        snprintf(pl.sym, sizeof pl.sym, "attn_pp64_kernel<0,%d>", tp);
+        return pl;
+    }
+    // (head_dim 80 keeps the generic body: the pipelined kernel at 32 query rows per wave runs two waves per SIMD
+    // where attn_kernel_occ3 runs three, and with 44 MFMAs per wave between two tile barriers the third wave hides more than the leaner
+    // instruction stream saves: the 32x32-level attention of the full step 2.18 -> 2.27 ms.)
+    if (tp == 0 && dpad <= 64 && p.Nq >= 2048) {        // 64 query rows per wave for long sequences.  One-launch only: no two-phase instantiation
+        snprintf(pl.sym, sizeof pl.sym, "attn_kernel_occ2<%d,%d,4>", dpad, dv16);
+        return pl;
+    }
+    const int qb = p.Nq >= 512 ? 2 : 1;
+    // prescaled q on the wide heads (80, 160: the 32x32 / 16x16 levels of SD-v1.5): the reference rides in the MFMA accumulator, row sums by
+    // v_dot2 (attn_body CF)
+    const bool cf = dpad >= 96 && p.q_prescaled;
+    snprintf(pl.sym, sizeof pl.sym, "%s<%d,%d,%d,%s,%d>", qb == 2 && dpad <= 96 ? "attn_kernel_occ3" : "attn_kernel", dpad, dv16, qb, cf ? "true" : "false", tp);
+    pl.grid = (unsigned)((p.Nq + 64 * qb - 1) / (64 * qb)) * per_q;
+    return pl;
 }
 
-static int attn_dispatch(const AttnParams& p, hipStream_t stream) {
-    // text cross-attention: one short source, K/V held in registers (attn_text_kernel)
-    if (!p.kx && !p.state_out && !p.state_in && p.nsrc == 1 && p.Nkv <= 80 && !p.src_logw && (p.d == 40 || p.d == 80) && p.Nq >= 256) {
-        const int nchunk = (p.Nq + 1023) / 1024;
-        const dim3 grid((unsigned)(nchunk * p.heads * p.BF));
-        if (p.d == 40) hipLaunchKernelGGL((attn_text_kernel<40>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((attn_text_kernel<80>), grid, dim3(256), 0, stream, p);
-        UV_LAUNCH_CHECK();
-        return UV_OK;
+int uv_launch_attention(const AttnParams& p0, hipStream_t stream) {
+    const AttnPlan pl = uv_attention_plan(p0);
+    if (pl.rc != UV_OK) {
+        uv_set_error("%s", pl.err);
+        return pl.rc;
     }
-    switch (p.d) {
+    const AttnKernel* kern = nullptr;
+    for (const AttnKernel& k : ATTN_KERNELS)
+        if (!strcmp(k.sym, pl.sym)) kern = &k;
+    if (!kern) {
+        uv_set_error("attention: the plan names %s, which the launch table does not hold", pl.sym);
+        return UV_ERR_STATE;
+    }
+    AttnParams p = p0;
+    p.order = 1;                          // head-major block order (the kernels read it)
+    uv_prof_begin(pl.cls, pl.flops, pl.bytes, stream);
+    hipLaunchKernelGGL(kern->fn, dim3(pl.grid), dim3(pl.block), 0, stream, p);
+    uv_prof_end(stream);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
 
-        case 16: return launch_attn<32, 1>(p, stream);
-        case 32: return launch_attn<32, 2>(p, stream);
-        case 40: return launch_attn<64, 3>(p, stream);
-        case 64: return launch_attn<64, 4>(p, stream);
-        case 80: return launch_attn<96, 5>(p, stream);
-        case 160: return launch_attn<160, 10>(p, stream);
-        default:
-            uv_set_error("attention: head_dim=%d not instantiated (16,32,40,64,80,160)", p.d);
-            return UV_ERR_UNSUPPORTED;
+// ---- host-only read-out of the plan (univst_debug_attention_plan)
+std::string uv_attention_plan_symbols() {
+    std::string out;
+    for (const AttnKernel& k : ATTN_KERNELS) out += (out.empty() ? "" : ";") + std::string(k.sym);
+    return out;
+}
+int uv_attention_plan_text(const AttnParams& p, char* buf, int n) {
+    const AttnPlan pl = uv_attention_plan(p);
+    if (pl.rc != UV_OK) {
+        snprintf(buf, (size_t)n, "%s", pl.err);
+        uv_set_error("%s", pl.err);
+        return pl.rc;
     }
+    snprintf(buf, (size_t)n, "%s grid=%u block=%u splits=1", pl.sym, pl.grid, pl.block);
+    return UV_OK;
 }
 
 int uv_launch_tr16_probe(float* out, hipStream_t stream) {

@@ -38,7 +38,17 @@ const char* uv_get_error();
         }                                     \
     } while (0)
 
-#define UV_LAUNCH_CHECK()                                                                         \
+// UV_REQUIRE inside a plan function (kernels.h: UvLaunchPlan): the error stays in the plan, which is returned
+#define UV_PLAN_REQUIRE(pl, cond, ...)                            \
+    do {                                                          \
+        if (!(cond)) {                                            \
+            snprintf((pl).err, sizeof((pl).err), __VA_ARGS__);    \
+            (pl).rc = UV_ERR_ARG;                                 \
+            return (pl);                                          \
+        }                                                         \
+    } while (0)
+
+#define UV_LAUNCH_CHECK()                                                                       \
     do {                                                                                          \
         hipError_t _e = hipGetLastError();                                                        \
         if (_e != hipSuccess) {                                                                   \

@@ -19,8 +19,9 @@
 // Replaces (reference call sites): resnet.py:64 (PseudoConv3d 2-D conv), attention.py:123,141 (proj_in /
 // proj_out), attention.py:375-377,425 + pnp_utils.py:39-43,97 (to_q/k/v/out), diffusers FeedForward/GEGLU,
 // diffusers Attention projections, unet_3d_blocks.py:523,618 (torch.cat skip), resnet.py:145 (nearest x2).
-#include "common.h"
+#include <string.h>
 
+#include "common.h"
 #include "kernels.h"
 
 namespace {
@@ -1387,6 +1388,33 @@ static int uv_num_cus() {
     return n;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The launch table: every kernel instantiation uv_gemm_plan can name, ONCE.  The key is the symbol as the profiler and a kernel trace
+// spell it (template arguments in full, no spaces); the plan composes that string and the launcher looks it up here.
+// (splitk_reduce_kernel is not in it: it is the tail of a split launch, never a plan's kernel.)
+struct GemmKernel {
+    void (*fn)(GemmParams);
+    const char* sym;
+};
+#define UV_KERNEL(...) {__VA_ARGS__, #__VA_ARGS__}
+static const GemmKernel GEMM_KERNELS[] = {
+    UV_KERNEL(geglu_xres_kernel<0>),   UV_KERNEL(geglu_xres_kernel<2>),
+    UV_KERNEL(conv_patch_kernel<3>),   UV_KERNEL(conv_patch_kernel<4>),
+    // gemm_big_kernel<MODE, MJ (16-row fragments per wave: 192 / 256 rows), LNF (1: row statistics out, 2: LayerNorm folded, 3: MM-DiT act / gate)>
+    UV_KERNEL(gemm_big_kernel<0,3,0>), UV_KERNEL(gemm_big_kernel<0,4,0>), UV_KERNEL(gemm_big_kernel<1,3,0>), UV_KERNEL(gemm_big_kernel<1,4,0>),
+    UV_KERNEL(gemm_big_kernel<0,3,1>), UV_KERNEL(gemm_big_kernel<0,4,1>), UV_KERNEL(gemm_big_kernel<0,3,2>), UV_KERNEL(gemm_big_kernel<0,4,2>),
+    UV_KERNEL(gemm_big_kernel<0,3,3>),     // (the MM-DiT epilogue fits the 256-VGPR budget only with the 192-row tile: 223 registers; 256 rows spill 48)
+    // gemm_kernel<NF (32-column fragments: 128 / 160 columns), MODE, MF (2: 64-row tiles), LNF>
+    UV_KERNEL(gemm_kernel<4,0,4,0>),   UV_KERNEL(gemm_kernel<5,0,4,0>),   UV_KERNEL(gemm_kernel<4,1,4,0>),   UV_KERNEL(gemm_kernel<5,1,4,0>),
+    UV_KERNEL(gemm_kernel<4,0,2,0>),   UV_KERNEL(gemm_kernel<4,1,2,0>),   UV_KERNEL(gemm_kernel<5,0,4,1>),
+    UV_KERNEL(gemm_kernel<4,0,4,2>),   UV_KERNEL(gemm_kernel<5,0,4,2>),   UV_KERNEL(gemm_kernel<4,0,2,2>),
+};
+#undef UV_KERNEL
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Pieces of the selection policy.  uv_gemm_plan below and the predicates the UNet graph consults are both written in terms of these, so the
+// arithmetic exists once.
+
 // Split-K factor for `ntiles` output tiles, `nk` k tiles each, on `slots` concurrently resident blocks: minimise
 //   ceil(ntiles * s / slots) rounds x ceil(nk / s) k tiles (us_per_ktile each)  +  the fp32 partial traffic (s writes + s reads)
 // — rounds, not raw block counts: 48 tiles x 6 splits = 288 blocks is TWO rounds on 256 CUs, 48 x 5 = 240 is one.
@@ -1411,8 +1439,7 @@ static bool uv_conv_patch_eligible(const GemmParams& p, int bmb) {
 // fewest 256x320 tiles a problem needs to take the big tile without split-K: measured cross-over (tools/bench_gemm_mid.py)
 constexpr long BIG_MIN_TILES = 150;
 
-// ONE copy of what the 256x320 path requires of a problem's shape: used by the launcher below and by the predicate the
-// UNet graph consults before it decides to fold a LayerNorm (the two used to be separate copies that could drift apart).
+// What the 256x320 path requires of a problem's shape.
 // ragged: a plain linear (no GEGLU, no LayerNorm fold / statistics, no split-K) may end in a partly filled column tile (N % 8 == 0):
 // the MM-DiT widths of the SD3 path (1536, 4608, 6144 = 4.8 / 14.4 / 19.2 tiles) lose 4 % of the MFMA work to padding and still run
 // 1.4x faster than on the 128 x 128 tile.  Weight rows >= N come from the zero page; both epilogues skip columns >= N.
@@ -1421,38 +1448,18 @@ constexpr long BIG_MIN_TILES = 150;
 static bool big_shape_ok(int N, int K, long x_elems, bool ragged = false, int ragged_min = 640) {      // x_elems: extent of the activation operand in elements (32-bit DMA offsets)
     return (N % 320 == 0 || (ragged && N % 8 == 0 && N >= ragged_min)) && (long)N * K < (1L << 31) && x_elems < (1L << 31);
 }
+// tiles of `rows` x 320 that cover an M x N output
+static long big_tiles(long M, int N, int rows) { return ((M + rows - 1) / rows) * ((N + 319) / 320); }
+// few tiles but a long reduction (the 8x8-level convs; most convs of a frame shard): the big tile would run with split-K — fp32 partials
+// cost ~35 us, so long reductions only — and its epilogue then lives in the reduction kernel
+static bool big_would_split(long ntiles, int K) { return ntiles < BIG_MIN_TILES && ntiles >= 8 && K >= 128 * 64; }
 
-// Does a plain linear [M, K] (row stride ldx, 0 = K) x [N, K]^T take the direct (no split-K) 256x320 path whose epilogue can fold a
-// LayerNorm / emit row statistics?  Same conditions as the launcher (which still re-checks and fails loudly on a mismatch);
-// pointer alignment is the caller's business (the UNet arena is 256-byte aligned).
-bool uv_linear_takes_big_direct(long M, int N, int K, long ldx) {
-    if (!big_shape_ok(N, K, M * (ldx ? ldx : (long)K))) return false;
-    const long n256 = ((M + 255) / 256) * (N / 320), n192 = ((M + 191) / 192) * (N / 320);
-    return n256 >= BIG_MIN_TILES && n192 >= BIG_MIN_TILES;      // whichever tile height the launcher picks
-}
-
-int uv_launch_geglu_xres_permute(const half_t* in, half_t* out, int rows, int cols, hipStream_t stream) {
-    UV_REQUIRE(rows % 256 == 0 && cols >= 1, "geglu_xres_permute: %d rows must be a multiple of 256", rows);
-    hipLaunchKernelGGL(geglu_xres_permute_kernel, dim3((unsigned)(((long)rows * cols + 255) / 256)), dim3(256), 0, stream, in, out, rows, cols);
-    UV_LAUNCH_CHECK();
-    return UV_OK;
-}
-// M = 0: the shape alone (weight preparation).  With M: a block walks ALL column tiles of its 128 rows (74 us at N = 2 560), so the grid
-// has to fill whole rounds of the CUs: at least two rounds, the last one >= 80 % full — one rank of an 8-GPU job (192 blocks) and a 1.5-round
-// grid stay on the 256x320 tile (emulated rank: 1.34 vs 1.41 ms for the class).
-bool uv_geglu_xres_ok(int N, int K, long M) {
-    if (K != XR_K || N % XR_BN != 0) return false;
-    if (M <= 0) return true;
-    const long blocks = (M + XR_BM - 1) / XR_BM, ncu = uv_num_cus(), rounds = (blocks + ncu - 1) / ncu;
-    return blocks >= 2 * ncu && blocks * 10 >= rounds * ncu * 8;
-}
-
-// ONE copy of how the 128-wide path tiles a problem and whether it would split K (used by the launcher and by the fold predicates).
+// How the 128-wide path tiles a problem and whether it would split K.
 struct SmallPlan {
     bool nf5, small_m;
     int bn, nt, splits;
 };
-static SmallPlan small_plan(long M, int N, int K, bool geglu, int mode, bool want_stats) {
+static SmallPlan small_plan(long M, int N, int K, bool geglu, int mode, bool want_stats, int ncu) {
     SmallPlan sp;
     // NF = 5 (160-column tiles) for widths that 160 divides and 128 does not — and for every producer of row statistics: the
     // block's 160 columns are then exactly one statistics slot
@@ -1462,40 +1469,72 @@ static SmallPlan small_plan(long M, int N, int K, bool geglu, int mode, bool wan
     // small-M problems (deepest UNet level: 3072 rows): 64-row tiles double the block count so the chip is filled when the
     // 128-row tiles are < 2 per CU — linears always, convs only when split-K cannot supply the parallelism instead (short K;
     // measured: tools/bench_gemm_mid.py)
-    sp.small_m = !sp.nf5 && sp.nt < 2 * uv_num_cus() && M > 64 && (mode == 0 || geglu || (K + 63) / 64 < 16);
+    sp.small_m = !sp.nf5 && sp.nt < 2 * ncu && M > 64 && (mode == 0 || geglu || (K + 63) / 64 < 16);
     if (sp.small_m) sp.nt = (int)(((M + 63) / 64) * ((N + sp.bn - 1) / sp.bn));
     // split-K when the tiles alone leave most CUs idle and K is long (deep levels; every level of a frame shard)
     sp.splits = 1;
     if (!geglu && N % 4 == 0 && sp.nt < 384) {
         const int nk = (K + 63) / 64;
-        const int s = uv_pick_splits(sp.nt, nk, 2L * uv_num_cus(), 4, 16, 1.0, (double)M * N * 4.0);     // two resident blocks per CU
+        const int s = uv_pick_splits(sp.nt, nk, 2L * ncu, 4, 16, 1.0, (double)M * N * 4.0);     // two resident blocks per CU
         if (s >= 2) sp.splits = s;
     }
     return sp;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The predicates of the UNet graph (unet.hip asks them before it folds a LayerNorm / GroupNorm into a linear) and of the C ABI.  They are
+// NOT plan queries: they see a shape only — no pointers, strides or epilogue — and answer for every launch of that shape, so they are
+// deliberately stricter than uv_gemm_plan in two places:
+//   - uv_linear_takes_big_direct wants BOTH tile heights to reach BIG_MIN_TILES ("whichever tile height the launcher picks"), the plan
+//     only the height it picks;
+//   - the fold predicates refuse a problem as soon as its 256-ROW tile count would split K on the big tile, whatever height the plan
+//     would pick, and then ask the 128-wide plan of a plain linear on the current device.
+// A yes is a promise the plan keeps (tests/test_dispatch_plan.py sweeps it); a no may be a problem the plan would still have taken.
+// Pointer alignment is the caller's business (the UNet arena is 256-byte aligned); the launcher re-checks and fails loudly.
+
+// Does a plain linear [M, K] (row stride ldx, 0 = K) x [N, K]^T take the direct (no split-K) 256x320 path, whose epilogue can fold a
+// LayerNorm / emit row statistics / take weight sets?
+static bool takes_big_direct(long M, int N, int K, long ldx) {
+    return big_shape_ok(N, K, M * (ldx ? ldx : (long)K)) && big_tiles(M, N, 256) >= BIG_MIN_TILES && big_tiles(M, N, 192) >= BIG_MIN_TILES;
+}
+bool uv_linear_takes_big_direct(long M, int N, int K, long ldx) { return takes_big_direct(M, N, K, ldx); }
+
 // May a LayerNorm be folded around a plain linear [M, K] x [N, K]^T?  As the PRODUCER of the normalised tensor it has to leave the row
 // statistics of its output (one slot per 160 columns), as the CONSUMER it applies them in its epilogue.  Both exist in the direct
-// 256x320 kernel and, since round 4, in the 128-wide kernel when that runs the problem without split-K (the epilogue of a split
-// problem lives in the reduction kernel).  The GEGLU consumer exists in the 256x320 kernel only.
-bool uv_linear_fold_producer_ok(long M, int N, int K) {
-    if (uv_linear_takes_big_direct(M, N, K)) return true;
-    if (N % 160 != 0 || K % 8 != 0) return false;
-    if (big_shape_ok(N, K, M * (long)K)) {      // the 256x320 path with split-K would take it (long reductions): no epilogue there
-        const long n256 = ((M + 255) / 256) * (N / 320);
-        if (n256 >= 8 && K >= 128 * 64) return false;
-    }
-    return small_plan(M, N, K, false, 0, true).splits == 1;
+// 256x320 kernel and in the 128-wide kernel when that runs the problem without split-K (the epilogue of a split problem lives in the
+// reduction kernel).  The GEGLU consumer exists in the 256x320 kernel only.
+static bool fold_small_ok(long M, int N, int K, bool want_stats, int ncu) {
+    if (big_shape_ok(N, K, M * (long)K) && big_would_split(big_tiles(M, N, 256), K)) return false;
+    return small_plan(M, N, K, false, 0, want_stats, ncu).splits == 1;
 }
-bool uv_linear_fold_consumer_ok(long M, int N, int K, bool geglu) {
-    if (uv_linear_takes_big_direct(M, N, K)) return true;
-    if (geglu || N % 4 != 0 || K % 160 != 0) return false;
-    if (big_shape_ok(N, K, M * (long)K)) {
-        const long n256 = ((M + 255) / 256) * (N / 320);
-        if (n256 >= 8 && K >= 128 * 64) return false;
-    }
-    return small_plan(M, N, K, false, 0, false).splits == 1;
+static bool fold_producer_ok(long M, int N, int K, int ncu) {
+    if (takes_big_direct(M, N, K, 0)) return true;
+    return N % 160 == 0 && K % 8 == 0 && fold_small_ok(M, N, K, true, ncu);
 }
+static bool fold_consumer_ok(long M, int N, int K, bool geglu, int ncu) {
+    if (takes_big_direct(M, N, K, 0)) return true;
+    return !geglu && N % 4 == 0 && K % 160 == 0 && fold_small_ok(M, N, K, false, ncu);
+}
+bool uv_linear_fold_producer_ok(long M, int N, int K) { return fold_producer_ok(M, N, K, uv_num_cus()); }
+bool uv_linear_fold_consumer_ok(long M, int N, int K, bool geglu) { return fold_consumer_ok(M, N, K, geglu, uv_num_cus()); }
+
+int uv_launch_geglu_xres_permute(const half_t* in, half_t* out, int rows, int cols, hipStream_t stream) {
+    UV_REQUIRE(rows % 256 == 0 && cols >= 1, "geglu_xres_permute: %d rows must be a multiple of 256", rows);
+    hipLaunchKernelGGL(geglu_xres_permute_kernel, dim3((unsigned)(((long)rows * cols + 255) / 256)), dim3(256), 0, stream, in, out, rows, cols);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+// M = 0: the shape alone (weight preparation).  With M: a block walks ALL column tiles of its 128 rows (74 us at N = 2 560), so the grid
+// has to fill whole rounds of the CUs: at least two rounds, the last one >= 80 % full — one rank of an 8-GPU job (192 blocks) and a 1.5-round
+// grid stay on the 256x320 tile (emulated rank: 1.34 vs 1.41 ms for the class).  This one IS what the graph acts on: a yes makes it pass
+// geglu = 2, which the plan takes or refuses by its own requirement.
+static bool geglu_xres_ok(int N, int K, long M, long ncu) {
+    if (K != XR_K || N % XR_BN != 0) return false;
+    if (M <= 0) return true;
+    const long blocks = (M + XR_BM - 1) / XR_BM, rounds = (blocks + ncu - 1) / ncu;
+    return blocks >= 2 * ncu && blocks * 10 >= rounds * ncu * 8;
+}
+bool uv_geglu_xres_ok(int N, int K, long M) { return geglu_xres_ok(N, K, M, uv_num_cus()); }
 
 // algorithmic (compulsory) bytes of a launch for the roofline leg: A operand + weights + output (+ the residual it reads).  A 3x3 conv reads its INPUT
 // tensor once — the im2col-expanded operand M x 9Cin (what the matrix pipe consumes, served from LDS / L2 re-reads) is reported beside it as `aux`.
@@ -1508,228 +1547,213 @@ static inline void uv_gemm_bytes(const GemmParams& p, int mode, double* compulso
     *expanded = 2.0 * (a_exp + w + out + res);
 }
 
-
-int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
-    GemmParams p = p0;
-    if (mode == 1 && p.tapw == 0) {       // kernel geometry defaults: 3x3 with padding 1, 1x1 without
+// kernel geometry defaults of a conv: 3x3 with padding 1, 1x1 without
+static GemmParams with_conv_defaults(GemmParams p, int mode) {
+    if (mode == 1 && p.tapw == 0) {
         p.tapw = p.taps == 9 ? 3 : 1;
         p.pady = p.padx = p.taps == 9 ? 1 : 0;
     }
-    UV_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// THE selection policy: X-resident GEGLU, 256x320 (direct, LDS-patch, split-K; 256 or 192 rows) or 128-wide, with every requirement
+// in the order the errors have always come.  Plain host code: no HIP call, pointers looked at for null and 16-byte alignment only.
+// p: conv geometry defaults already filled in (with_conv_defaults).
+#define PLAN_REQUIRE(cond, ...) UV_PLAN_REQUIRE(pl, cond, __VA_ARGS__)
+GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu) {
+    GemmPlan pl;
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    PLAN_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+    pl.block = 512;
+    pl.flops = 2.0 * p.M * (double)p.N * p.K;
     if (p.geglu == 2) {                  // weights in the X-resident kernel's row order (geglu_xres_kernel)
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        UV_REQUIRE(mode == 0 && p.K == XR_K && p.N % XR_BN == 0 && p.ldx % 8 == 0 && p.ldy % 8 == 0 && al16(p.X) && al16(p.W) && al16(p.Y) && al16(p.bias) &&
-                   !p.R && !p.rowbias && !p.bias2 && !p.stats_out && !p.act && !p.gate && !p.gn_out && (long)p.M * p.ldx < (1L << 31) &&
-                   (!p.ln_stats || (p.ln_wsum && p.ln_bias && p.ln_slots > 0 && !p.bias)),
-                   "geglu (X-resident order): needs K = 320, N %% 256 == 0, 16-byte aligned rows, no residual / second bias (M=%d N=%d K=%d)", p.M, p.N, p.K);
-        uv_prof_begin(UV_CLS_GEMM_BIG, 2.0 * p.M * (double)p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * (p.N / 2)), stream,
-                      p.ln_stats ? "geglu_xres_kernel<2>" : "geglu_xres_kernel<0>");
-        const dim3 grid((p.M + XR_BM - 1) / XR_BM);
-        if (p.ln_stats) hipLaunchKernelGGL((geglu_xres_kernel<2>), grid, dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL((geglu_xres_kernel<0>), grid, dim3(512), 0, stream, p);
-        uv_prof_end(stream);
-        UV_LAUNCH_CHECK();
-        return UV_OK;
+        PLAN_REQUIRE(mode == 0 && p.K == XR_K && p.N % XR_BN == 0 && p.ldx % 8 == 0 && p.ldy % 8 == 0 && al16(p.X) && al16(p.W) && al16(p.Y) && al16(p.bias) &&
+                     !p.R && !p.rowbias && !p.bias2 && !p.stats_out && !p.act && !p.gate && !p.gn_out && (long)p.M * p.ldx < (1L << 31) &&
+                     (!p.ln_stats || (p.ln_wsum && p.ln_bias && p.ln_slots > 0 && !p.bias)),
+                     "geglu (X-resident order): needs K = 320, N %% 256 == 0, 16-byte aligned rows, no residual / second bias (M=%d N=%d K=%d)", p.M, p.N, p.K);
+        pl.cls = UV_CLS_GEMM_BIG;
+        pl.bytes = 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * (p.N / 2));
+        pl.prof_sym = true;
+        snprintf(pl.sym, sizeof pl.sym, "geglu_xres_kernel<%d>", p.ln_stats ? 2 : 0);
+        pl.grid = (p.M + XR_BM - 1) / XR_BM;
+        return pl;
     }
     const bool lnf = p.ln_stats || p.stats_out;
-    UV_REQUIRE(p.K % 8 == 0, "gemm: K=%d must be a multiple of 8", p.K);
-    UV_REQUIRE(!(p.act || p.gate) || (!p.geglu && !lnf && mode == 0), "gemm: the activation / gate epilogue is for plain linears (no GEGLU, LayerNorm fold, conv)");
-    UV_REQUIRE(!p.gate || (p.rows_per_gate >= 1 && p.ld_gate % 8 == 0 && p.N % 8 == 0 && (reinterpret_cast<uintptr_t>(p.gate) & 15) == 0),
-               "gemm: gate rows must be 16-byte aligned (ld_gate %% 8 == 0, N %% 8 == 0)");
+    PLAN_REQUIRE(p.K % 8 == 0, "gemm: K=%d must be a multiple of 8", p.K);
+    PLAN_REQUIRE(!(p.act || p.gate) || (!p.geglu && !lnf && mode == 0), "gemm: the activation / gate epilogue is for plain linears (no GEGLU, LayerNorm fold, conv)");
+    PLAN_REQUIRE(!p.gate || (p.rows_per_gate >= 1 && p.ld_gate % 8 == 0 && p.N % 8 == 0 && al16(p.gate)),
+                 "gemm: gate rows must be 16-byte aligned (ld_gate %% 8 == 0, N %% 8 == 0)");
     if (mode == 0) {
-        UV_REQUIRE(p.ldx % 8 == 0, "gemm: ldx=%ld must be a multiple of 8", p.ldx);
+        PLAN_REQUIRE(p.ldx % 8 == 0, "gemm: ldx=%ld must be a multiple of 8", p.ldx);
     } else {
-        UV_REQUIRE(p.C1 % 8 == 0 && p.C2 % 8 == 0, "conv: channel counts must be multiples of 8 (C1=%d C2=%d)", p.C1, p.C2);
-        UV_REQUIRE((p.taps == 1 && p.tapw == 1) || (p.taps == 9 && p.tapw == 3) || (p.taps == 3 && p.tapw == 1), "conv: taps=%d with %d per row (1x1, 3x3 or the 3x1 frame conv)", p.taps, p.tapw);
-        UV_REQUIRE(p.K == p.taps * (p.C1 + p.C2), "conv: K=%d != taps*(C1+C2)", p.K);
+        PLAN_REQUIRE(p.C1 % 8 == 0 && p.C2 % 8 == 0, "conv: channel counts must be multiples of 8 (C1=%d C2=%d)", p.C1, p.C2);
+        PLAN_REQUIRE((p.taps == 1 && p.tapw == 1) || (p.taps == 9 && p.tapw == 3) || (p.taps == 3 && p.tapw == 1), "conv: taps=%d with %d per row (1x1, 3x3 or the 3x1 frame conv)", p.taps, p.tapw);
+        PLAN_REQUIRE(p.K == p.taps * (p.C1 + p.C2), "conv: K=%d != taps*(C1+C2)", p.K);
         const bool sym3 = p.taps == 9 && p.pady == 1 && p.padx == 1;
-        UV_REQUIRE(!p.korder || (sym3 && p.C1 % 64 == 0 && p.C2 % 64 == 0), "conv: tap-inner k order needs the 3x3 / padding-1 kernel and 64-channel slabs");
-        UV_REQUIRE(!p.W32 || sym3, "conv: the LDS-patch weight copy is for the 3x3 / padding-1 kernel");
+        PLAN_REQUIRE(!p.korder || (sym3 && p.C1 % 64 == 0 && p.C2 % 64 == 0), "conv: tap-inner k order needs the 3x3 / padding-1 kernel and 64-channel slabs");
+        PLAN_REQUIRE(!p.W32 || sym3, "conv: the LDS-patch weight copy is for the 3x3 / padding-1 kernel");
     }
-    {   // large-M path: 256x320 tiles when they tile N exactly and fill the chip (>= 2 blocks per CU)
-        // tile height: 256 rows, or 192 when that fills whole rounds of the CUs better (49152 x 640 is 384 tiles of 256 = 1.5
-        // rounds but 512 tiles of 192 = 2 exact ones; 12288 x 1280 is 192 vs 256 tiles)
-        const long ncu = uv_num_cus();
-        // a ragged last column tile: plain linears (N >= 640) and, since round 5, plain convs whose width fills a whole number of 64-column wave halves
-        // and at least 80 % of one tile (256, 512, 576, ...: not the UNet's widths, which are multiples of 320)
-        const bool conv_rag = mode == 1 && !p.gn_out && p.N % 64 == 0 && p.N >= 256 && (p.N % 320 == 0 || p.N % 320 >= 192);
-        const bool ragged = (mode == 0 && !p.geglu && !lnf) || conv_rag;
-        const int ntn_c = (p.N + 319) / 320;
-        const long n256 = (long)((p.M + 255) / 256) * ntn_c, n192 = (long)((p.M + 191) / 192) * ntn_c;
-        // per-row cost of the 192-row tile relative to the 256-row one, measured at equal round counts: convs 0.96-1.0, linears 1.02-1.07
-        // (round 5: the conv factor was 0.99, which at the 64x64 level — 768 tiles of 256 rows = 3 full rounds against 1 024 of 192 = 4 — picked 192
-        // by a hair; measured on the LDS-patch kernel the 256-row tile is 2.5 - 4 % faster there (0.357 / 0.936 / 0.585 ms against 0.366 / 0.973 /
-        // 0.609 for 320->320, 960->320, 640->320 at 64 x 64), while the 32x32 and 16x16 levels keep 192: fewer rounds)
-        const double c256 = (double)((n256 + ncu - 1) / ncu) * 256.0, c192 = (double)((n192 + ncu - 1) / ncu) * 192.0 * (mode == 1 ? 1.03 : 1.05);
-        // (the MM-DiT epilogue instantiation fits the 256-VGPR budget only with the 192-row tile: 223 registers; 256 rows spill 48)
-        const bool mmdit_epi = mode == 0 && (p.act || p.gate);
-        bool use192 = mmdit_epi || (c192 < c256 && n192 >= BIG_MIN_TILES);
-        if (p.w_rows_per_set) {           // weight sets per row range: a tile must lie inside one set
-            UV_REQUIRE(mode == 0 && p.bias32 && !p.geglu && !p.ln_stats && !mmdit_epi && p.M % p.w_rows_per_set == 0 && (p.w_rows_per_set % 256 == 0 || p.w_rows_per_set % 192 == 0) &&
-                       (long)(p.M / p.w_rows_per_set) * p.N * p.K + (long)p.N * p.K < (1L << 31),
-                       "linear: weight sets need a plain linear, an fp32 bias per set and %d rows per set that a 256- or 192-row tile divides", p.w_rows_per_set);
-            if (p.w_rows_per_set % (use192 ? 192 : 256) != 0) use192 = !use192;
-        }
-        const long nblk = use192 ? n192 : n256;
-        const long xmax = (mode == 0) ? (long)p.M * p.ldx : (long)p.M * (p.C1 > p.C2 ? p.C1 : p.C2) * 4;
-        // few tiles but a long reduction (the 8x8-level convs; most convs of a frame shard): the big tile with split-K
-        int bsplits = 1;
-        if (!p.geglu && p.N % 320 == 0 && nblk < BIG_MIN_TILES && nblk >= 8 && p.K >= 128 * 64) {   // fp32 partials cost ~35 us: long reductions only
-            const int nk = (p.K + 63) / 64;
-            int sp = uv_pick_splits(nblk, nk, uv_num_cus(), 24, 8, 2.2, (double)p.M * p.N * 4.0);
-            while (sp >= 2 && (size_t)sp * p.M * p.N * sizeof(float) > UV_SPLITK_WS_BYTES) --sp;     // what the partial workspace holds
-            if (sp >= 2 && nblk * sp >= 128) bsplits = sp;
-        }
-        const bool use_patch = mode == 1 && (nblk >= BIG_MIN_TILES || bsplits > 1) && uv_conv_patch_eligible(p, use192 ? 192 : 256);
-        UV_REQUIRE(p.W || use_patch, "conv: only the [Cin/32][9][32] weight copy was given but the problem is not eligible for the LDS-patch kernel "
-                   "(3x3, stride 1, whole image rows per 256/192-row tile, >= 150 tiles or a reduction long enough for split-K)");
-        if (big_shape_ok(p.N, p.K, xmax, ragged, conv_rag ? 256 : 640) && (nblk >= BIG_MIN_TILES || bsplits > 1)) {
-            char sym[48];
-            if (use_patch) snprintf(sym, sizeof sym, "conv_patch_kernel<%d>", use192 ? 3 : 4);
-            else snprintf(sym, sizeof sym, "gemm_big_kernel<%d,%d,%d>", mode, use192 ? 3 : 4, mode == 0 ? (p.ln_stats ? 2 : (p.stats_out ? 1 : (mmdit_epi ? 3 : 0))) : 0);
-            double by, byx;
-            uv_gemm_bytes(p, mode, &by, &byx);
-            uv_prof_begin(mode == 0 ? UV_CLS_GEMM_BIG : (use_patch ? UV_CLS_CONV_PATCH : UV_CLS_CONV_BIG), 2.0 * p.M * (double)p.N * p.K, by, stream, sym, byx);
-            // row-contiguous epilogue through LDS needs 16-byte aligned rows everywhere it touches; it pays for the plain
-            // and residual epilogues (-12..19 % at K=320) but not for GEGLU, whose stores are half as many
-            auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-            GemmParams q = p;
-            // row-group x column-block tile order for wide outputs (see gemm_big_kernel); otherwise column-fastest
-            q.tile_gn = 0;
-            if (mode == 0 && ntn_c > 4 && (long)p.N * p.K * 2 > (3L << 20)) {      // W larger than ~3 MB: it cannot stay in L2 as a whole
-                q.tile_gn = ntn_c % 2 == 0 ? 2 : 0;     // 8 x 2 measured best of 8x4 / 16x2 / 4x8 / 16x4 / 32x4 (all within 2 %); 10 x 3 was a loss
-                q.tile_gm = 8;
-            }
-            q.epi_lds = !p.geglu && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && al16(p.bias2) && al16(p.rowbias) && p.ldrb % 8 == 0 &&
-                        (!p.R || (p.ldr % 8 == 0 && al16(p.R)));
-            // GEGLU (round 4): register math + fp16 slab + row-contiguous 16-byte stores (epi_lds = 3)
-            const bool geglu_slab = p.geglu && mode == 0 && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && p.N % 16 == 0;
-            if (geglu_slab) q.epi_lds = 3;
-            // the fp32 bias (GroupNorm folded into the linear) exists in the row epilogue through LDS only: a launch that would land on the register
-            // epilogue (misaligned Y / R) or on split-K must not drop it silently
-            UV_REQUIRE(!p.bias32 || (q.epi_lds == 1 && bsplits <= 1), "linear: the fp32 bias needs the LDS row epilogue of the direct path (16-byte aligned Y / R / bias rows, no split-K)");
-            // (Measured and rejected on this tile, DESIGN.md §4: a 32-wide-k 4-stage DMA ring with counted vmcnt (-10 %), the same
-            // with two wave groups staggered by half a k tile + s_setprio (-0..18 %), and a five-phase / two-barriers-per-phase
-            // schedule with in-place restaging two k tiles ahead (the guide's 8-phase template on this shape: -3 % linears,
-            // -20 % convs).)
-            bool own_ws = false;
-            q.splits = 1;
-            if (bsplits > 1) {
-                const int nk = (p.K + 63) / 64;
-                q.ktps = (nk + bsplits - 1) / bsplits;
-                if (use_patch) q.ktps = (q.ktps + 8) / 9 * 9;      // a split starts at a 64-channel slab pair (9 k tiles)
-                q.splits = (nk + q.ktps - 1) / q.ktps;
-                const size_t need = (size_t)q.splits * p.M * p.N * sizeof(float);
-                if (!(q.partial && q.partial_bytes >= need)) {
-                    UV_HIP(hipMallocAsync((void**)&q.partial, need, stream));
-                    own_ws = true;
-                }
-            }
-            UV_REQUIRE(!p.w_rows_per_set || (q.epi_lds == 1 && q.splits == 1), "linear: weight sets run on the direct 256x320 path with the LDS epilogue only");
-            if (p.gn_out) {       // GroupNorm statistics from this epilogue: LDS epilogue, whole 160-column halves of 10 / 20 / 40-channel groups, no split-K
-                const bool ok = q.epi_lds == 1 && q.splits == 1 && !p.geglu && !p.stats_out && !p.act && !p.gate && p.N % 320 == 0 && p.M % 16 == 0 &&
-                                p.gn_G > 0 && p.gn_gw * p.gn_G == p.N && (p.gn_gw == 10 || p.gn_gw == 20 || p.gn_gw == 40);
-                if (!ok) q.gn_out = nullptr;
-                else if (p.gn_emitted) *p.gn_emitted = 1;
-            }
-            const dim3 bgrid((unsigned)(nblk * q.splits));
-            if (use_patch) {          // 3x3 / stride 1 on whole image rows: input patch in LDS, k order [Cin/32][9][32] (p.W32)
-                if (use192) hipLaunchKernelGGL((conv_patch_kernel<3>), bgrid, dim3(512), 0, stream, q);
-                else hipLaunchKernelGGL((conv_patch_kernel<4>), bgrid, dim3(512), 0, stream, q);
-                if (q.splits > 1) {
-                    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)p.M * (p.N / 4) + 255) / 256)), dim3(256), 0, stream, q);
-                    if (own_ws) UV_HIP(hipFreeAsync(q.partial, stream));
-                }
-                uv_prof_end(stream);
-                UV_LAUNCH_CHECK();
-                return UV_OK;
-            }
-            // (Round 4, measured and removed: a PERSISTENT form of this tile for the GEGLU projections — one block per CU walking its tiles, the next
-            // tile's first k tile DMA'd into the free buffer before the epilogue — 22.8 vs 22.6 us per K = 320 tile, -2.5 % at K >= 640
-            // (256 VGPRs + 8 spilled dwords): block relaunch and prologue latency are not what the 13 us of fixed cost are made of.  The
-            // kernel is kept as tools/probes/gemm_big_persist_kernel.inc for the record.)
-            if (lnf) {                // LayerNorm folded into this linear / row statistics emitted for the next one
-                if (p.geglu && !geglu_slab) q.epi_lds = 0;
-                UV_REQUIRE(mode == 0 && q.splits == 1 && (q.epi_lds || !p.stats_out) && (!p.ln_stats || (p.ln_wsum && p.ln_bias && p.ln_slots > 0)) &&
-                           (!p.stats_out || (!p.geglu && p.N % 160 == 0)), "linear: LayerNorm fold on a problem the direct 256x320 path does not take");
-                UV_REQUIRE(!(p.ln_stats && p.stats_out), "linear: a LayerNorm-folded linear cannot also emit row statistics");
-                if (p.ln_stats) {
-                    if (use192) hipLaunchKernelGGL((gemm_big_kernel<0, 3, 2>), bgrid, dim3(512), 0, stream, q);
-                    else hipLaunchKernelGGL((gemm_big_kernel<0, 4, 2>), bgrid, dim3(512), 0, stream, q);
-                } else {
-                    if (use192) hipLaunchKernelGGL((gemm_big_kernel<0, 3, 1>), bgrid, dim3(512), 0, stream, q);
-                    else hipLaunchKernelGGL((gemm_big_kernel<0, 4, 1>), bgrid, dim3(512), 0, stream, q);
-                }
-            } else if (mmdit_epi) {                            // MM-DiT epilogue: GELU(tanh) / gate (.) + residual
-                hipLaunchKernelGGL((gemm_big_kernel<0, 3, 3>), bgrid, dim3(512), 0, stream, q);
-            } else if (use192) {
-                if (mode == 0) hipLaunchKernelGGL((gemm_big_kernel<0, 3>), bgrid, dim3(512), 0, stream, q);
-                else hipLaunchKernelGGL((gemm_big_kernel<1, 3>), bgrid, dim3(512), 0, stream, q);
-            } else if (mode == 0) hipLaunchKernelGGL((gemm_big_kernel<0, 4>), bgrid, dim3(512), 0, stream, q);
-            else hipLaunchKernelGGL((gemm_big_kernel<1, 4>), bgrid, dim3(512), 0, stream, q);
-            if (q.splits > 1) {
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)p.M * (p.N / 4) + 255) / 256)), dim3(256), 0, stream, q);
-                if (own_ws) UV_HIP(hipFreeAsync(q.partial, stream));
-            }
-            uv_prof_end(stream);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
-        }
+    uv_gemm_bytes(p, mode, &pl.bytes, &pl.aux_bytes);
+    const int nk = (p.K + 63) / 64;
+    const size_t mn_f32 = (size_t)p.M * p.N * sizeof(float);          // one split's fp32 partials
+    const unsigned reduce_grid = (unsigned)(((long)p.M * (p.N / 4) + 255) / 256);
+
+    // ---- large-M path: 256x320 tiles when they tile N (a ragged last tile for plain problems) and fill the chip, or reduce long enough for split-K
+    // a ragged last column tile: plain linears (N >= 640) and plain convs whose width fills a whole number of 64-column wave halves
+    // and at least 60 % of one tile (256, 512, 576, ...: not the UNet's widths, which are multiples of 320)
+    const bool conv_rag = mode == 1 && !p.gn_out && p.N % 64 == 0 && p.N >= 256 && (p.N % 320 == 0 || p.N % 320 >= 192);
+    const bool ragged = (mode == 0 && !p.geglu && !lnf) || conv_rag;
+    const long n256 = big_tiles(p.M, p.N, 256), n192 = big_tiles(p.M, p.N, 192);
+    // tile height: 256 rows, or 192 when that fills whole rounds of the CUs better (49152 x 640 is 384 tiles of 256 = 1.5
+    // rounds but 512 tiles of 192 = 2 exact ones; 12288 x 1280 is 192 vs 256 tiles).
+    // per-row cost of the 192-row tile relative to the 256-row one, measured at equal round counts: convs 0.96-1.0, linears 1.02-1.07
+    // (the conv factor was 0.99, which at the 64x64 level — 768 tiles of 256 rows = 3 full rounds against 1 024 of 192 = 4 — picked 192
+    // by a hair; measured on the LDS-patch kernel the 256-row tile is 2.5 - 4 % faster there (0.357 / 0.936 / 0.585 ms against 0.366 / 0.973 /
+    // 0.609 for 320->320, 960->320, 640->320 at 64 x 64), while the 32x32 and 16x16 levels keep 192: fewer rounds)
+    const double c256 = (double)((n256 + ncu - 1) / ncu) * 256.0, c192 = (double)((n192 + ncu - 1) / ncu) * 192.0 * (mode == 1 ? 1.03 : 1.05);
+    const bool mmdit_epi = mode == 0 && (p.act || p.gate);      // its instantiation exists for the 192-row tile only (see the table)
+    bool use192 = mmdit_epi || (c192 < c256 && n192 >= BIG_MIN_TILES);
+    if (p.w_rows_per_set) {           // weight sets per row range: a tile must lie inside one set
+        PLAN_REQUIRE(mode == 0 && p.bias32 && !p.geglu && !p.ln_stats && !mmdit_epi && p.M % p.w_rows_per_set == 0 && (p.w_rows_per_set % 256 == 0 || p.w_rows_per_set % 192 == 0) &&
+                     (long)(p.M / p.w_rows_per_set) * p.N * p.K + (long)p.N * p.K < (1L << 31),
+                     "linear: weight sets need a plain linear, an fp32 bias per set and %d rows per set that a 256- or 192-row tile divides", p.w_rows_per_set);
+        if (p.w_rows_per_set % (use192 ? 192 : 256) != 0) use192 = !use192;
     }
-    UV_REQUIRE(!p.w_rows_per_set && !p.bias32, "linear: weight sets / an fp32 bias exist on the direct 256x320 path only (M=%d N=%d K=%d does not take it)", p.M, p.N, p.K);
-    const SmallPlan plan = small_plan(p.M, p.N, p.K, p.geglu != 0, mode, p.stats_out != nullptr);
+    const long nblk = use192 ? n192 : n256;
+    const long xmax = (mode == 0) ? (long)p.M * p.ldx : (long)p.M * (p.C1 > p.C2 ? p.C1 : p.C2) * 4;
+    int bsplits = 1;
+    if (!p.geglu && p.N % 320 == 0 && big_would_split(nblk, p.K)) {
+        int sp = uv_pick_splits(nblk, nk, ncu, 24, 8, 2.2, (double)p.M * p.N * 4.0);
+        while (sp >= 2 && sp * mn_f32 > UV_SPLITK_WS_BYTES) --sp;     // what the partial workspace holds
+        if (sp >= 2 && nblk * sp >= 128) bsplits = sp;
+    }
+    const bool fills = nblk >= BIG_MIN_TILES || bsplits > 1;
+    const bool use_patch = mode == 1 && fills && uv_conv_patch_eligible(p, use192 ? 192 : 256);
+    PLAN_REQUIRE(p.W || use_patch, "conv: only the [Cin/32][9][32] weight copy was given but the problem is not eligible for the LDS-patch kernel "
+                 "(3x3, stride 1, whole image rows per 256/192-row tile, >= 150 tiles or a reduction long enough for split-K)");
+    if (fills && big_shape_ok(p.N, p.K, xmax, ragged, conv_rag ? 256 : 640)) {
+        const int mj = use192 ? 3 : 4;
+        // row-group x column-block tile order for wide outputs (see gemm_big_kernel); otherwise column-fastest
+        const int ntn = (p.N + 319) / 320;
+        if (mode == 0 && ntn > 4 && (long)p.N * p.K * 2 > (3L << 20)) {      // W larger than ~3 MB: it cannot stay in L2 as a whole
+            pl.tile_gn = ntn % 2 == 0 ? 2 : 0;     // 8 x 2 measured best of 8x4 / 16x2 / 4x8 / 16x4 / 32x4 (all within 2 %); 10 x 3 was a loss
+            pl.tile_gm = 8;
+        }
+        // row-contiguous epilogue through LDS needs 16-byte aligned rows everywhere it touches; it pays for the plain
+        // and residual epilogues (-12..19 % at K=320) but not for GEGLU, whose stores are half as many ...
+        pl.epi_lds = !p.geglu && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && al16(p.bias2) && al16(p.rowbias) && p.ldrb % 8 == 0 &&
+                     (!p.R || (p.ldr % 8 == 0 && al16(p.R)));
+        // ... GEGLU: register math + fp16 slab + row-contiguous 16-byte stores (epi_lds = 3)
+        if (p.geglu && mode == 0 && p.ldy % 8 == 0 && al16(p.Y) && al16(p.bias) && p.N % 16 == 0) pl.epi_lds = 3;
+        // the fp32 bias (GroupNorm folded into the linear) exists in the row epilogue through LDS only: a launch that would land on the register
+        // epilogue (misaligned Y / R) or on split-K must not drop it silently
+        PLAN_REQUIRE(!p.bias32 || (pl.epi_lds == 1 && bsplits <= 1), "linear: the fp32 bias needs the LDS row epilogue of the direct path (16-byte aligned Y / R / bias rows, no split-K)");
+        if (bsplits > 1) {
+            pl.ktps = (nk + bsplits - 1) / bsplits;
+            if (use_patch) pl.ktps = (pl.ktps + 8) / 9 * 9;      // a split starts at a 64-channel slab pair (9 k tiles)
+            pl.splits = (nk + pl.ktps - 1) / pl.ktps;
+            pl.ws_bytes = pl.splits * mn_f32;
+        }
+        PLAN_REQUIRE(!p.w_rows_per_set || (pl.epi_lds == 1 && pl.splits == 1), "linear: weight sets run on the direct 256x320 path with the LDS epilogue only");
+        // GroupNorm statistics from this epilogue: LDS epilogue, whole 160-column halves of 10 / 20 / 40-channel groups, no split-K
+        pl.gn_emit = p.gn_out && pl.epi_lds == 1 && pl.splits == 1 && !p.geglu && !p.stats_out && !p.act && !p.gate && p.N % 320 == 0 && p.M % 16 == 0 &&
+                     p.gn_G > 0 && p.gn_gw * p.gn_G == p.N && (p.gn_gw == 10 || p.gn_gw == 20 || p.gn_gw == 40);
+        if (lnf && !use_patch) {    // LayerNorm folded into this linear / row statistics emitted for the next one
+            PLAN_REQUIRE(mode == 0 && pl.splits == 1 && (pl.epi_lds || !p.stats_out) && (!p.ln_stats || (p.ln_wsum && p.ln_bias && p.ln_slots > 0)) &&
+                         (!p.stats_out || (!p.geglu && p.N % 160 == 0)), "linear: LayerNorm fold on a problem the direct 256x320 path does not take");
+            PLAN_REQUIRE(!(p.ln_stats && p.stats_out), "linear: a LayerNorm-folded linear cannot also emit row statistics");
+        }
+        pl.cls = mode == 0 ? UV_CLS_GEMM_BIG : (use_patch ? UV_CLS_CONV_PATCH : UV_CLS_CONV_BIG);
+        pl.prof_sym = true;
+        // 3x3 / stride 1 on whole image rows: input patch in LDS, k order [Cin/32][9][32] (p.W32)
+        if (use_patch) snprintf(pl.sym, sizeof pl.sym, "conv_patch_kernel<%d>", mj);
+        else snprintf(pl.sym, sizeof pl.sym, "gemm_big_kernel<%d,%d,%d>", mode, mj, p.ln_stats ? 2 : (p.stats_out ? 1 : (mmdit_epi ? 3 : 0)));
+        pl.grid = (unsigned)(nblk * pl.splits);
+        pl.reduce_grid = pl.splits > 1 ? reduce_grid : 0;
+        return pl;
+    }
+
+    // ---- the 128-wide path
+    PLAN_REQUIRE(!p.w_rows_per_set && !p.bias32, "linear: weight sets / an fp32 bias exist on the direct 256x320 path only (M=%d N=%d K=%d does not take it)", p.M, p.N, p.K);
+    const SmallPlan sp = small_plan(p.M, p.N, p.K, p.geglu != 0, mode, p.stats_out != nullptr, ncu);
     if (lnf) {
-        UV_REQUIRE(mode == 0 && !p.geglu && !p.act && !p.gate && plan.splits == 1 && !(p.ln_stats && p.stats_out) &&
-                   (!p.stats_out || (plan.nf5 && p.N % 160 == 0)) &&
-                   (!p.ln_stats || (p.ln_wsum && p.ln_bias && p.ln_slots > 0 && p.N % 4 == 0)),
-                   "linear: LayerNorm fold requested for M=%d N=%d K=%d, which neither the direct 256x320 path nor the 128-wide path without split-K takes "
-                   "(uv_linear_fold_producer_ok / uv_linear_fold_consumer_ok)", p.M, p.N, p.K);
+        PLAN_REQUIRE(mode == 0 && !p.geglu && !p.act && !p.gate && sp.splits == 1 && !(p.ln_stats && p.stats_out) &&
+                     (!p.stats_out || (sp.nf5 && p.N % 160 == 0)) &&
+                     (!p.ln_stats || (p.ln_wsum && p.ln_bias && p.ln_slots > 0 && p.N % 4 == 0)),
+                     "linear: LayerNorm fold requested for M=%d N=%d K=%d, which neither the direct 256x320 path nor the 128-wide path without split-K takes "
+                     "(uv_linear_fold_producer_ok / uv_linear_fold_consumer_ok)", p.M, p.N, p.K);
     }
-    const bool nf5 = plan.nf5, small_m = plan.small_m;
-    int nt = plan.nt;
-    if (p.geglu) UV_REQUIRE(p.N % 32 == 0, "geglu: N=%d must be a multiple of 32", p.N);
-    GemmParams q = p;
-    q.splits = 1;
-    bool own_ws = false;
-    if (plan.splits >= 2) {
-        const int nk = (p.K + 63) / 64;
-        q.ktps = (nk + plan.splits - 1) / plan.splits;
-        q.splits = (nk + q.ktps - 1) / q.ktps;
-        const size_t need = (size_t)q.splits * p.M * p.N * sizeof(float);
-        if (q.partial && q.partial_bytes >= need) {
-        } else if (need <= UV_SPLITK_WS_BYTES) {   // stand-alone operator call: stream-ordered scratch
-            UV_HIP(hipMallocAsync((void**)&q.partial, need, stream));
-            own_ws = true;
-        } else {
-            q.splits = 1;
+    if (p.geglu) PLAN_REQUIRE(p.N % 32 == 0, "geglu: N=%d must be a multiple of 32", p.N);
+    if (sp.splits >= 2) {
+        pl.ktps = (nk + sp.splits - 1) / sp.splits;
+        pl.splits = (nk + pl.ktps - 1) / pl.ktps;
+        pl.ws_bytes = pl.splits * mn_f32;
+        // a stand-alone operator call gets stream-ordered scratch up to the size of the graph's workspace; beyond that the problem runs unsplit
+        if (!(p.partial && p.partial_bytes >= pl.ws_bytes) && pl.ws_bytes > UV_SPLITK_WS_BYTES) {
+            pl.splits = 1;
+            pl.ktps = 0;
+            pl.ws_bytes = 0;
         }
     }
-    dim3 grid(nt * q.splits), block(256);
-    double by, byx;
-    uv_gemm_bytes(p, mode, &by, &byx);
-    uv_prof_begin(mode == 0 ? UV_CLS_GEMM : UV_CLS_CONV, 2.0 * p.M * (double)p.N * p.K, by, stream, nullptr, byx);
-    if (p.stats_out) {
-        hipLaunchKernelGGL((gemm_kernel<5, 0, 4, 1>), grid, block, 0, stream, q);
-    } else if (p.ln_stats) {
-        if (small_m) hipLaunchKernelGGL((gemm_kernel<4, 0, 2, 2>), grid, block, 0, stream, q);
-        else if (nf5) hipLaunchKernelGGL((gemm_kernel<5, 0, 4, 2>), grid, block, 0, stream, q);
-        else hipLaunchKernelGGL((gemm_kernel<4, 0, 4, 2>), grid, block, 0, stream, q);
-    } else if (small_m) {
-        if (mode == 0) hipLaunchKernelGGL((gemm_kernel<4, 0, 2>), grid, block, 0, stream, q);
-        else hipLaunchKernelGGL((gemm_kernel<4, 1, 2>), grid, block, 0, stream, q);
-    } else if (mode == 0) {
-        if (nf5) hipLaunchKernelGGL((gemm_kernel<5, 0>), grid, block, 0, stream, q);
-        else hipLaunchKernelGGL((gemm_kernel<4, 0>), grid, block, 0, stream, q);
-    } else {
-        if (nf5) hipLaunchKernelGGL((gemm_kernel<5, 1>), grid, block, 0, stream, q);
-        else hipLaunchKernelGGL((gemm_kernel<4, 1>), grid, block, 0, stream, q);
+    pl.cls = mode == 0 ? UV_CLS_GEMM : UV_CLS_CONV;
+    snprintf(pl.sym, sizeof pl.sym, "gemm_kernel<%d,%d,%d,%d>", sp.nf5 ? 5 : 4, mode, sp.small_m ? 2 : 4, p.stats_out ? 1 : (p.ln_stats ? 2 : 0));
+    pl.grid = (unsigned)(sp.nt * pl.splits);
+    pl.block = 256;
+    pl.reduce_grid = pl.splits > 1 ? reduce_grid : 0;
+    return pl;
+}
+#undef PLAN_REQUIRE
+
+int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
+    GemmParams q = with_conv_defaults(p0, mode);
+    const GemmPlan pl = uv_gemm_plan(q, mode, uv_num_cus());
+    if (pl.rc != UV_OK) {               // every requirement is checked before the first allocation
+        uv_set_error("%s", pl.err);
+        return pl.rc;
     }
-    if (q.splits > 1) {
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((long)p.M * (p.N / 4) + 255) / 256)), dim3(256), 0, stream, q);
-        if (own_ws) UV_HIP(hipFreeAsync(q.partial, stream));
+    const GemmKernel* kern = nullptr;
+    for (const GemmKernel& k : GEMM_KERNELS)
+        if (!strcmp(k.sym, pl.sym)) kern = &k;
+    if (!kern) {
+        uv_set_error("gemm: the plan names %s, which the launch table does not hold", pl.sym);
+        return UV_ERR_STATE;
     }
+    q.splits = pl.splits;
+    q.ktps = pl.ktps;
+    q.epi_lds = pl.epi_lds;
+    q.tile_gn = pl.tile_gn;
+    q.tile_gm = pl.tile_gm;
+    if (!pl.gn_emit) q.gn_out = nullptr;
+    else if (q.gn_emitted) *q.gn_emitted = 1;
+    const bool own_ws = pl.ws_bytes && !(q.partial && q.partial_bytes >= pl.ws_bytes);      // no caller workspace (UNet arena) that holds the partials
+    if (own_ws) UV_HIP(hipMallocAsync((void**)&q.partial, pl.ws_bytes, stream));
+    uv_prof_begin(pl.cls, pl.flops, pl.bytes, stream, pl.prof_sym ? pl.sym : nullptr, pl.aux_bytes);
+    hipLaunchKernelGGL(kern->fn, dim3(pl.grid), dim3(pl.block), 0, stream, q);
+    if (pl.reduce_grid) hipLaunchKernelGGL(splitk_reduce_kernel, dim3(pl.reduce_grid), dim3(256), 0, stream, q);
+    if (own_ws) UV_HIP(hipFreeAsync(q.partial, stream));
     uv_prof_end(stream);
     UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+
+// ---- host-only read-out of the plan and of the predicates (univst_debug_gemm_plan): one line of text, or the plan's error
+std::string uv_gemm_plan_symbols() {
+    std::string out;
+    for (const GemmKernel& k : GEMM_KERNELS) out += (out.empty() ? "" : ";") + std::string(k.sym);
+    return out;
+}
+int uv_gemm_plan_text(const GemmParams& p0, int mode, int ncu, char* buf, int n) {
+    const GemmParams p = with_conv_defaults(p0, mode);
+    const GemmPlan pl = uv_gemm_plan(p, mode, ncu);
+    if (pl.rc != UV_OK) {
+        snprintf(buf, (size_t)n, "%s", pl.err);
+        uv_set_error("%s", pl.err);
+        return pl.rc;
+    }
+    snprintf(buf, (size_t)n, "%s grid=%u block=%u splits=%d%s big_direct=%d fold_producer=%d fold_consumer=%d geglu_consumer=%d geglu_xres=%d", pl.sym, pl.grid,
+             pl.block, pl.splits, pl.reduce_grid ? " +splitk_reduce" : "", (int)takes_big_direct(p.M, p.N, p.K, p.ldx), (int)fold_producer_ok(p.M, p.N, p.K, ncu),
+             (int)fold_consumer_ok(p.M, p.N, p.K, false, ncu), (int)fold_consumer_ok(p.M, p.N, p.K, true, ncu), (int)geglu_xres_ok(p.N, p.K, p.M, ncu));
     return UV_OK;
 }
 

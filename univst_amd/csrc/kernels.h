@@ -140,6 +140,33 @@ int uv_launch_frag_pack(const half_t* W, half_t* out, int N, int K, hipStream_t 
 int uv_launch_kv_frag_pack(const half_t* kv, half_t* out, int B, int T, int C, int heads, hipStream_t s);
 int uv_launch_attn2_fused(const Attn2Params& p, int C, hipStream_t s);
 
+// What a uv_launch_gemm / uv_launch_attention call will do.  The plan functions are plain host code (no HIP call; pointers are looked at
+// for null and 16-byte alignment only), so the whole selection policy can be read out and tested without a GPU: univst_debug_gemm_plan /
+// univst_debug_attention_plan, tests/test_dispatch_plan.py with the recorded table tests/data/dispatch_plan.txt.
+struct UvLaunchPlan {
+    int rc = UV_OK;                  // UV_OK, or the error code with its message in err: the launcher returns it before it touches the GPU
+    char err[400] = "";
+    char sym[48] = "";               // the kernel instantiation = its key in the translation unit's launch table: template arguments in full, no spaces
+    unsigned grid = 0, block = 256;
+    int cls = 0;                     // profiler input (UV_CLS_*)
+    double flops = 0.0, bytes = 0.0, aux_bytes = 0.0;
+};
+struct GemmPlan : UvLaunchPlan {
+    bool prof_sym = false;           // the profiler is told sym (the 256x320 and X-resident kernels; the 128-wide path passes none)
+    int splits = 1, ktps = 0, epi_lds = 0, tile_gn = 0, tile_gm = 0;     // the GemmParams fields "set by the launcher"
+    bool gn_emit = false;            // gn_out survives and *gn_emitted is set
+    size_t ws_bytes = 0;             // fp32 partials of a split launch: the caller's workspace if it holds them, else stream-ordered scratch
+    unsigned reduce_grid = 0;        // > 0: splitk_reduce_kernel follows
+};
+struct AttnPlan : UvLaunchPlan {};
+GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu);       // p: conv geometry defaults filled in; ncu: compute units of the device
+AttnPlan uv_attention_plan(const AttnParams& p);
+// one line of text, `<symbol> grid=<blocks> block=<threads> splits=<s>[ +splitk_reduce]` (+ the predicates below for the GEMM), or the plan's error
+int uv_gemm_plan_text(const GemmParams& p, int mode, int ncu, char* buf, int n);
+int uv_attention_plan_text(const AttnParams& p, char* buf, int n);
+std::string uv_gemm_plan_symbols();          // ';'-joined keys of the launch tables
+std::string uv_attention_plan_symbols();
+
 int uv_launch_gemm(const GemmParams& p, int mode, hipStream_t stream);
 bool uv_linear_takes_big_direct(long M, int N, int K, long ldx = 0);
 // LayerNorm fold around a plain linear: may it emit the row statistics of its output / apply those of its input?  (256x320 direct path,
@@ -214,7 +241,7 @@ enum {
     UV_CLS_CONV_BIG = 1,    // gemm_big_kernel<1>
     UV_CLS_GEMM = 2,        // gemm_kernel<*,0,...>
     UV_CLS_CONV = 3,        // gemm_kernel<*,1,...>
-    UV_CLS_ATTN_D40 = 4,    // attn_pp40_kernel<true>: head_dim 40 self-attention over >= 2048 queries (the 64x64 level)
+    UV_CLS_ATTN_D40 = 4,    // head_dim 40 self-attention over >= 2048 queries (the 64x64 level): attn_pp40_kernel<0,1,true,*>; plain q: attn_kernel_occ2<64,3,4>
     UV_CLS_ATTN_D80 = 5,    // attn_kernel*<96,5,*>
     UV_CLS_ATTN_OTHER = 6,  // remaining attention instantiations
     UV_CLS_GROUPNORM = 7,

@@ -488,6 +488,20 @@ int univst_debug_gemm_plan(int ncu, int mode, int M, int N, int K, int geglu, in
 /* phase 0: univst_attention; 1 / 2: the first / the merge launch of univst_attention_phase */
 int univst_debug_attention_plan(int BF, int heads, int Nq, int Nkv, int nsrc, int d, int q_prescaled, int flags, int phase, char* buf, int n);
 
+/* What univst_groupnorm_nhwc / univst_groupnorm_fold_linear (and the UNet graph's GroupNorms) would launch, read out on the host like the two plans above.
+ * has_fold: 0, or the output rows N of the linear the normalisation is folded into; world: ranks the statistics are summed over (1: none);
+ * has_producer_stats: every source comes with the statistics its producer's epilogue left.  out_ints receives UNIVST_GN_PLAN_INTS values:
+ *   [0] route: 0 small (one launch of gn_small_kernel), 1 streaming (gn_partial_kernel + gn_reduce_chunks_kernel), 2 streaming from producer statistics
+ *   [1] fold (the tail is gn_fold_linear_kernel, not gn_apply_kernel)     [2] sharded statistics
+ *   [3] block, [4] TR of the streaming kernels: block = (C / 8) * TR threads (0 where none of them runs)
+ *   [5] nchunk, [6] rpc: chunks per stat unit and rows per chunk of the statistics pass
+ *   [7] nblk, [8] rpb: blocks per stat unit and rows per block of the apply pass
+ *   [9], [10] dynamic LDS bytes of the statistics kernel and of the tail
+ *   [11], [12] grid of the statistics kernel; [13] grid of the reduction; [14], [15] grid of the tail (0: not launched)
+ * or, with a non-zero return code, the launcher's error message is in univst_last_error(). */
+#define UNIVST_GN_PLAN_INTS 16
+int univst_debug_groupnorm_plan(int C1, int C2, int64_t rows, int rows_per_stat, int G, int has_fold, int world, int has_producer_stats, int* out_ints);
+
 #ifdef __cplusplus
 }
 #endif

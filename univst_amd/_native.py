@@ -135,6 +135,7 @@ SIGNATURES = {
     "univst_debug_delay_us": (_I, [C.c_double, _P]),
     "univst_debug_gemm_plan": (_I, [_I] * 16 + [C.c_char_p, _I]),
     "univst_debug_attention_plan": (_I, [_I] * 9 + [C.c_char_p, _I]),
+    "univst_debug_groupnorm_plan": (_I, [_I, _I, _L, _I, _I, _I, _I, _I, _P]),
     "univst_profile_enable": (_I, [_I]),
     "univst_profile_symbols": (_I, [_I, C.c_char_p, _I]),
     "univst_profile_collect": (_I, [C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_double), C.POINTER(C.c_double), _I]),

@@ -540,6 +540,18 @@ int univst_debug_attention_plan(int BF, int heads, int Nq, int Nkv, int nsrc, in
     if (phase == 2) a.state_in = arena;
     return uv_attention_plan_text(a, buf, n);
 }
+int univst_debug_groupnorm_plan(int C1, int C2, int64_t rows, int rows_per_stat, int G, int has_fold, int world, int has_producer_stats, int* out_ints) {
+    UV_REQUIRE(out_ints, "debug_groupnorm_plan: null output");
+    const GnPlan pl = uv_groupnorm_plan(C1, C2, rows, rows_per_stat, G, has_fold, world, has_producer_stats != 0);
+    if (pl.rc != UV_OK) {
+        uv_set_error("%s", pl.err);
+        return pl.rc;
+    }
+    const int v[UNIVST_GN_PLAN_INTS] = {pl.route, pl.fold, pl.sharded, pl.block, pl.TR, pl.nchunk, pl.rpc, pl.nblk, pl.rpb, pl.lds_stats, pl.lds_tail,
+                                        (int)pl.stats_grid[0], (int)pl.stats_grid[1], (int)pl.reduce_grid, (int)pl.tail_grid[0], (int)pl.tail_grid[1]};
+    for (int i = 0; i < UNIVST_GN_PLAN_INTS; ++i) out_ints[i] = v[i];
+    return UV_OK;
+}
 int univst_profile_enable(int on) {
     uv_prof_enable(on);
     return UV_OK;

@@ -199,6 +199,25 @@ struct UvGnFold {
     half_t* W_out = nullptr;         // [S][N][C]
     float* bias32 = nullptr;         // [S][N]
 };
+// What a uv_launch_groupnorm call will do: plain host code like uv_gemm_plan (no HIP call, no pointer), read out by univst_debug_groupnorm_plan;
+// tests/test_groupnorm_cases.py holds the route and geometry of every operator-test case to it.
+enum { UV_GN_SMALL = 0, UV_GN_STREAM = 1, UV_GN_STREAM_PRODUCER = 2 };
+struct GnPlan {
+    int rc = UV_OK;                  // UV_OK, or the error code with its message in err: the launcher returns it before it touches the GPU
+    char err[200] = "";
+    int route = UV_GN_STREAM;        // SMALL: gn_small_kernel; STREAM: gn_partial_kernel + gn_reduce_chunks_kernel; STREAM_PRODUCER: gn_reduce_sub_kernel
+    bool fold = false;               // the tail is gn_fold_linear_kernel instead of gn_apply_kernel
+    bool sharded = false;            // statistics are all-reduced over ranks before the tail (SMALL: gn_small_kernel<1>, then gn_apply_kernel)
+    int S = 0;                       // stat units
+    int block = 0, TR = 0;           // block of gn_partial_kernel / gn_apply_kernel = (C / 8) x TR threads; 0 where neither runs
+    int nchunk = 0, rpc = 0;         // statistics pass: chunks per stat unit, rows per chunk
+    int nblk = 0, rpb = 0;           // apply pass: blocks per stat unit, rows per block
+    int lds_stats = 0, lds_tail = 0; // dynamic LDS bytes of the statistics kernel and of the tail
+    unsigned stats_grid[2] = {0, 0}, reduce_grid = 0, tail_grid[2] = {0, 0};     // 0: not launched
+    double bytes = 0.0;              // profiler input
+};
+// fold_N: 0, or the output rows of the linear the normalisation is folded into; producer_stats: every source comes with its producer's statistics
+GnPlan uv_groupnorm_plan(int C1, int C2, long rows, int rows_per_stat, int G, int fold_N, int world, bool producer_stats);
 int uv_launch_groupnorm(const half_t* s1, const half_t* s2, int C1, int C2, long rows, int rows_per_stat, int G, float eps,
                         const half_t* gamma, const half_t* beta, int silu, half_t* out, float* part, hipStream_t stream,
                         const UvGnComm* comm = nullptr, const float* pre_part = nullptr, const float* pre_part2 = nullptr, const UvGnFold* fold = nullptr);

@@ -122,16 +122,18 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ s1, const half_t* __r
     const bool second = c0 >= C1;
     const half_t* src = second ? s2 : s1;
     const int cs = second ? C2 : C1, co = second ? c0 - C1 : c0;
-    float sc[8], sh[8];
+    // y = (x - mean) * sc + beta, not x * sc + (beta - mean * sc): the shift form rounds beta - mean * sc at the size of |mean| * rstd, which is
+    // all of a small |beta| when the group's spread is small (a constant group came out 7 fp16 steps from beta); x - mean is exact for x near mean
+    float sc[8], mu[8], bt[8];
     {
         h8 gv = *reinterpret_cast<const h8*>(gamma + c0);
         h8 bv = *reinterpret_cast<const h8*>(beta + c0);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             int gi = (c0 + e) / cpg;
-            float rs = sm[G + gi], mu = sm[gi];
-            sc[e] = rs * (float)gv[e];
-            sh[e] = (float)bv[e] - mu * sc[e];
+            mu[e] = sm[gi];
+            sc[e] = sm[G + gi] * (float)gv[e];
+            bt[e] = (float)bv[e];
         }
     }
     const long rbase = (long)s * rows_per_stat;
@@ -147,7 +149,7 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ s1, const half_t* __r
             h8 o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float y = (float)v[q][e] * sc[e] + sh[e];
+                float y = ((float)v[q][e] - mu[e]) * sc[e] + bt[e];
                 if (silu) y = silu_f(y);
                 o[e] = (half_t)y;
             }
@@ -159,7 +161,7 @@ __global__ void gn_apply_kernel(const half_t* __restrict__ s1, const half_t* __r
         h8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float y = (float)v[e] * sc[e] + sh[e];
+            float y = ((float)v[e] - mu[e]) * sc[e] + bt[e];
             if (silu) y = silu_f(y);
             o[e] = (half_t)y;
         }
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const half_t* __restrict_
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const float sc = rs * (float)gv[e];
-                float y = (float)v[e] * sc + ((float)bv[e] - mu * sc);
+                float y = ((float)v[e] - mu) * sc + (float)bv[e];             // as in gn_apply_kernel: no beta - mean * sc
                 if (silu) y = silu_f(y);
                 o[e] = (half_t)y;
             }
@@ -414,52 +416,48 @@ static int gn_geometry(int C, int* block) {
 constexpr int GN_MAX_CHUNKS = 512;     // per stat unit; 3 x 512 blocks keep ~6 blocks per CU streaming on the big tensors
 int uv_groupnorm_workspace_floats(int S, int G) { return S * (GN_MAX_CHUNKS + 1) * G * 2; }
 
-int uv_launch_groupnorm(const half_t* s1, const half_t* s2, int C1, int C2, long rows, int rows_per_stat, int G,
-                        float eps, const half_t* gamma, const half_t* beta, int silu, half_t* out, float* part,
-                        hipStream_t stream, const UvGnComm* comm, const float* pre_part, const float* pre_part2, const UvGnFold* fold) {
+// The whole selection policy of uv_launch_groupnorm: route, block geometry, the chunk plan of the statistics pass and the block plan of the apply pass.
+GnPlan uv_groupnorm_plan(int C1, int C2, long rows, int rows_per_stat, int G, int fold_N, int world, bool producer_stats) {
+    GnPlan pl;
     const int C = C1 + C2;
-    UV_REQUIRE(C % 8 == 0 && C1 % 8 == 0, "groupnorm: channels must be multiples of 8 (C1=%d C2=%d)", C1, C2);
-    UV_REQUIRE(C % G == 0, "groupnorm: C=%d not divisible by G=%d", C, G);
-    UV_REQUIRE(C / 8 <= 1024, "groupnorm: C=%d too large", C);
-    UV_REQUIRE(rows % rows_per_stat == 0, "groupnorm: rows=%ld not a multiple of rows_per_stat=%d", rows, rows_per_stat);
+    UV_PLAN_REQUIRE(pl, rows_per_stat > 0 && G > 0, "groupnorm: rows_per_stat=%d and G=%d must be positive", rows_per_stat, G);
+    UV_PLAN_REQUIRE(pl, C % 8 == 0 && C1 % 8 == 0, "groupnorm: channels must be multiples of 8 (C1=%d C2=%d)", C1, C2);
+    UV_PLAN_REQUIRE(pl, C % G == 0, "groupnorm: C=%d not divisible by G=%d", C, G);
+    UV_PLAN_REQUIRE(pl, C / 8 <= 1024, "groupnorm: C=%d too large", C);
+    UV_PLAN_REQUIRE(pl, rows % rows_per_stat == 0, "groupnorm: rows=%ld not a multiple of rows_per_stat=%d", rows, rows_per_stat);
     const int S = (int)(rows / rows_per_stat);
+    pl.S = S;
+    pl.fold = fold_N > 0;
+    pl.sharded = world > 1;
+    // producer statistics are usable when every source has them and the groups are whole runs of 10-channel sub-groups
+    const bool producer = producer_stats && (C / G) % 10 == 0 && C1 % 10 == 0 && C2 % 10 == 0 && rows_per_stat % 16 == 0;
+    const int TR = gn_geometry(C, &pl.block);
+    pl.TR = TR;
+    pl.lds_tail = 2 * G * (int)sizeof(float);
+    // apply pass: 16 rows per thread-row on big tensors, fewer on small ones.  (On the small route the 2048 cap cannot bind:
+    // rows_per_stat * C <= 2 Mi there, TR * C >= 2048 or TR = 1, and rpa >= 2, so nblk <= 512.)
+    int rpa = (int)(((long)rows_per_stat * S) / ((long)TR * 1024));
+    rpa = rpa < 2 ? 2 : (rpa > 16 ? 16 : rpa);
+    int nblk = (rows_per_stat + TR * rpa - 1) / (TR * rpa);
+    if (nblk > 2048) nblk = 2048;
+    if (nblk < 1) nblk = 1;
+    const int rpb = (rows_per_stat + nblk - 1) / nblk;
+    nblk = (rows_per_stat + rpb - 1) / rpb;
     // small tensors: one launch (statistics + apply in the block that owns the (unit, group)), or statistics only when they are summed over ranks
     constexpr long small_bytes = 4L << 20;
-    const bool sharded_stats = comm && comm->world > 1;
-    // producer statistics are usable when every source has them and the groups are whole runs of 10-channel sub-groups
-    if (pre_part && !((!s2 || pre_part2) && (C / G) % 10 == 0 && C1 % 10 == 0 && C2 % 10 == 0 && rows_per_stat % 16 == 0)) pre_part = nullptr;
-    UV_REQUIRE(!fold || (fold->W && fold->W_out && fold->bias32 && fold->N > 0 && !s2 && !silu), "groupnorm: fold needs a weight, its outputs, one source and no SiLU");
-    if (!fold && !pre_part && (C / G) % 2 == 0 && C1 % 2 == 0 && rows * C * 2 <= small_bytes && (long)S * G >= 48) {
-        uv_prof_begin(UV_CLS_GROUPNORM, 0.0, 4.0 * (double)rows * C, stream);      // one read from memory (the block's second read comes out of L2) + one write
-        if (!sharded_stats) {
-            hipLaunchKernelGGL((gn_small_kernel<0>), dim3(G, S), dim3(256), 0, stream, s1, s2, C1, C2, rows_per_stat, G, eps, gamma, beta, silu, out, (float*)nullptr);
-            uv_prof_end(stream);
-            UV_LAUNCH_CHECK();
-            return UV_OK;
+    if (!pl.fold && !producer && (C / G) % 2 == 0 && C1 % 2 == 0 && rows * C * 2 <= small_bytes && (long)S * G >= 48) {
+        pl.route = UV_GN_SMALL;
+        pl.bytes = 4.0 * (double)rows * C;         // one read from memory (the block's second read comes out of L2) + one write
+        pl.stats_grid[0] = G, pl.stats_grid[1] = S;
+        if (!pl.sharded) {
+            pl.block = pl.TR = pl.lds_tail = 0;
+            return pl;
         }
-        hipLaunchKernelGGL((gn_small_kernel<1>), dim3(G, S), dim3(256), 0, stream, s1, s2, C1, C2, rows_per_stat, G, eps, gamma, beta, silu, out, comm->red);
-        UV_LAUNCH_CHECK();
-        int rc = comm->allreduce(comm->user, comm->byte_off, S * G * 2);
-        if (rc) {
-            uv_set_error("groupnorm: all-reduce callback failed (%d)", rc);
-            return UV_ERR_STATE;
-        }
-        int blk;
-        const int TRs = gn_geometry(C, &blk);
-        int rpa_ = (int)(((long)rows_per_stat * S) / ((long)TRs * 1024));
-        rpa_ = rpa_ < 2 ? 2 : (rpa_ > 16 ? 16 : rpa_);
-        int nb_ = (rows_per_stat + TRs * rpa_ - 1) / (TRs * rpa_);
-        if (nb_ < 1) nb_ = 1;
-        const int rpb_ = (rows_per_stat + nb_ - 1) / nb_;
-        nb_ = (rows_per_stat + rpb_ - 1) / rpb_;
-        hipLaunchKernelGGL(gn_apply_kernel, dim3(nb_, S), dim3(blk), 2 * G * sizeof(float), stream, s1, s2, C1, C2, rows_per_stat, rpb_, G, 1, eps,
-                           (long)rows_per_stat * comm->world, comm->red, gamma, beta, silu, out);
-        uv_prof_end(stream);
-        UV_LAUNCH_CHECK();
-        return UV_OK;
+        pl.nblk = nblk, pl.rpb = rpb;
+        pl.tail_grid[0] = nblk, pl.tail_grid[1] = S;
+        return pl;
     }
-    int block;
-    const int TR = gn_geometry(C, &block);
+    pl.route = producer ? UV_GN_STREAM_PRODUCER : UV_GN_STREAM;
     // chunks: <= GN_MAX_CHUNKS per stat unit, 32 rows per thread-row on big tensors; on small ones (frame shards, single-branch calls,
     // the deep levels) fewer rows per block so that the grid still has ~3 blocks per CU — a 2-frame shard of the 64x64 level ran the
     // statistics pass on 129 blocks at 0.9 TB/s (17.5 us for 15.7 MB)
@@ -470,37 +468,78 @@ int uv_launch_groupnorm(const half_t* s1, const half_t* s2, int C1, int C2, long
     if (nchunk < 1) nchunk = 1;
     const int rpc = (rows_per_stat + nchunk - 1) / nchunk;
     nchunk = (rows_per_stat + rpc - 1) / rpc;
-    // what the launches below move: the apply pass reads and writes the tensor; the statistics pass reads it once more unless the producers left them
-    uv_prof_begin(UV_CLS_GROUPNORM, 0.0, ((pre_part ? 0.0 : 2.0) + (fold ? 0.0 : 4.0)) * (double)rows * C, stream);
-    size_t lds1 = (size_t)3 * TR * C * sizeof(float);
-    UV_REQUIRE(lds1 <= 160 * 1024, "groupnorm: LDS %zu too large", lds1);
-    const float* chunk_part = part;
-    if (!pre_part) {
-        hipLaunchKernelGGL(gn_partial_kernel, dim3(nchunk, S), dim3(block), lds1, stream, s1, s2, C1, C2, rows_per_stat, rpc,
+    // what the launches move: the apply pass reads and writes the tensor; the statistics pass reads it once more unless the producers left them
+    pl.bytes = ((producer ? 0.0 : 2.0) + (pl.fold ? 0.0 : 4.0)) * (double)rows * C;
+    const size_t lds1 = (size_t)3 * TR * C * sizeof(float);
+    UV_PLAN_REQUIRE(pl, lds1 <= 160 * 1024, "groupnorm: LDS %zu too large", lds1);
+    if (producer) {       // one block per (stat unit, group) sums the producers' fragments
+        pl.reduce_grid = (unsigned)(S * G);
+    } else {
+        pl.nchunk = nchunk, pl.rpc = rpc;
+        pl.lds_stats = (int)lds1;
+        pl.stats_grid[0] = nchunk, pl.stats_grid[1] = S;
+        pl.reduce_grid = (unsigned)((S * G * 2 + 3) / 4);
+    }
+    if (pl.fold) {
+        pl.tail_grid[0] = (fold_N + 3) / 4, pl.tail_grid[1] = S;
+    } else {
+        pl.nblk = nblk, pl.rpb = rpb;
+        pl.tail_grid[0] = nblk, pl.tail_grid[1] = S;
+    }
+    return pl;
+}
+
+int uv_launch_groupnorm(const half_t* s1, const half_t* s2, int C1, int C2, long rows, int rows_per_stat, int G,
+                        float eps, const half_t* gamma, const half_t* beta, int silu, half_t* out, float* part,
+                        hipStream_t stream, const UvGnComm* comm, const float* pre_part, const float* pre_part2, const UvGnFold* fold) {
+    const GnPlan pl = uv_groupnorm_plan(C1, C2, rows, rows_per_stat, G, fold ? fold->N : 0, comm ? comm->world : 1, pre_part && (!s2 || pre_part2));
+    if (pl.rc != UV_OK) {
+        uv_set_error("%s", pl.err);
+        return pl.rc;
+    }
+    UV_REQUIRE(!fold || (fold->W && fold->W_out && fold->bias32 && fold->N > 0 && !s2 && !silu), "groupnorm: fold needs a weight, its outputs, one source and no SiLU");
+    const int C = C1 + C2, S = pl.S;
+    const dim3 stats_grid(pl.stats_grid[0], pl.stats_grid[1]), tail_grid(pl.tail_grid[0], pl.tail_grid[1]);
+    uv_prof_begin(UV_CLS_GROUPNORM, 0.0, pl.bytes, stream);
+    if (pl.route == UV_GN_SMALL) {
+        if (!pl.sharded) {
+            hipLaunchKernelGGL((gn_small_kernel<0>), stats_grid, dim3(256), 0, stream, s1, s2, C1, C2, rows_per_stat, G, eps, gamma, beta, silu, out, (float*)nullptr);
+            uv_prof_end(stream);
+            UV_LAUNCH_CHECK();
+            return UV_OK;
+        }
+        hipLaunchKernelGGL((gn_small_kernel<1>), stats_grid, dim3(256), 0, stream, s1, s2, C1, C2, rows_per_stat, G, eps, gamma, beta, silu, out, comm->red);
+        UV_LAUNCH_CHECK();
+        int rc = comm->allreduce(comm->user, comm->byte_off, S * G * 2);
+        if (rc) {
+            uv_set_error("groupnorm: all-reduce callback failed (%d)", rc);
+            return UV_ERR_STATE;
+        }
+        hipLaunchKernelGGL(gn_apply_kernel, tail_grid, dim3(pl.block), pl.lds_tail, stream, s1, s2, C1, C2, rows_per_stat, pl.rpb, G, 1, eps,
+                           (long)rows_per_stat * comm->world, comm->red, gamma, beta, silu, out);
+        uv_prof_end(stream);
+        UV_LAUNCH_CHECK();
+        return UV_OK;
+    }
+    if (pl.route == UV_GN_STREAM) {
+        hipLaunchKernelGGL(gn_partial_kernel, stats_grid, dim3(pl.block), pl.lds_stats, stream, s1, s2, C1, C2, rows_per_stat, pl.rpc,
                            G, part);
         UV_LAUNCH_CHECK();
     }
-    int rpa = (int)(((long)rows_per_stat * S) / ((long)TR * 1024));       // rows per thread-row of the apply pass: 16 on big tensors
-    rpa = rpa < 2 ? 2 : (rpa > 16 ? 16 : rpa);
-    int nblk = (rows_per_stat + TR * rpa - 1) / (TR * rpa);
-    if (nblk > 2048 / (S > 0 ? 1 : 1)) nblk = 2048;
-    if (nblk < 1) nblk = 1;
-    const int rpb = (rows_per_stat + nblk - 1) / nblk;
-    nblk = (rows_per_stat + rpb - 1) / rpb;
     long count_rows = rows_per_stat;
     // reduce the chunk partials ONCE ([S,nchunk,G,2] -> [S,G,2], stored right behind them) instead of letting each of
     // the ~2000 apply blocks walk all chunks serially (that prologue was ~1/2 of the apply kernel's time)
-    float* red = part + (size_t)S * (pre_part ? 0 : nchunk) * G * 2;
+    float* red = part + (size_t)S * pl.nchunk * G * 2;
     const int SG2 = S * G * 2;
-    if (comm && comm->world > 1) red = comm->red;
-    if (pre_part) {       // the producing convs / linears left (sum, sumsq) per 16-row fragment and 10-channel sub-group: no pass over the tensor(s)
-        hipLaunchKernelGGL(gn_reduce_sub_kernel, dim3(S * G), dim3(256), 0, stream, reinterpret_cast<const float2*>(pre_part),
+    if (pl.sharded) red = comm->red;
+    if (pl.route == UV_GN_STREAM_PRODUCER) {       // the producing convs / linears left (sum, sumsq) per 16-row fragment and 10-channel sub-group: no pass over the tensor(s)
+        hipLaunchKernelGGL(gn_reduce_sub_kernel, dim3(pl.reduce_grid), dim3(256), 0, stream, reinterpret_cast<const float2*>(pre_part),
                            reinterpret_cast<const float2*>(pre_part2), C1 / 10, C2 / 10, rows_per_stat / 16, (C / G) / 10, G, S * G, red);
     } else {
-        hipLaunchKernelGGL(gn_reduce_chunks_kernel, dim3((SG2 + 3) / 4), dim3(256), 0, stream, chunk_part, red, nchunk, SG2, G * 2);
+        hipLaunchKernelGGL(gn_reduce_chunks_kernel, dim3(pl.reduce_grid), dim3(256), 0, stream, part, red, pl.nchunk, SG2, G * 2);
     }
     UV_LAUNCH_CHECK();
-    if (comm && comm->world > 1) {     // frame shard: sum the partials over ranks (SURVEY §8e coupling 1)
+    if (pl.sharded) {     // frame shard: sum the partials over ranks (SURVEY §8e coupling 1)
         int rc = comm->allreduce(comm->user, comm->byte_off, SG2);
         if (rc) {
             uv_set_error("groupnorm: all-reduce callback failed (%d)", rc);
@@ -508,17 +547,15 @@ int uv_launch_groupnorm(const half_t* s1, const half_t* s2, int C1, int C2, long
         }
         count_rows = (long)rows_per_stat * comm->world;
     }
-    const float* stats = red;
-    if (fold) {
-        hipLaunchKernelGGL(gn_fold_linear_kernel, dim3((fold->N + 3) / 4, S), dim3(256), 2 * G * sizeof(float), stream, stats, gamma, beta, G, C, count_rows, eps,
+    if (pl.fold) {
+        hipLaunchKernelGGL(gn_fold_linear_kernel, tail_grid, dim3(256), pl.lds_tail, stream, red, gamma, beta, G, C, count_rows, eps,
                            fold->W, fold->bias, fold->N, fold->W_out, fold->bias32);
         uv_prof_end(stream);
         UV_LAUNCH_CHECK();
         return UV_OK;
     }
-    const int nch_apply = 1;
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(nblk, S), dim3(block), 2 * G * sizeof(float), stream, s1, s2, C1, C2,
-                       rows_per_stat, rpb, G, nch_apply, eps, count_rows, stats, gamma, beta, silu, out);
+    hipLaunchKernelGGL(gn_apply_kernel, tail_grid, dim3(pl.block), pl.lds_tail, stream, s1, s2, C1, C2,
+                       rows_per_stat, pl.rpb, G, 1, eps, count_rows, red, gamma, beta, silu, out);
     uv_prof_end(stream);
     UV_LAUNCH_CHECK();
     return UV_OK;

@@ -269,3 +269,72 @@ def test_vae_from_pretrained_reads_a_diffusers_directory_without_diffusers(nat, 
     assert torch.equal(v.decode(z, num_frames=4).sample, vae.NativeTemporalVAE(sd, SMALL).decode(z, num_frames=4).sample)
     with pytest.raises(FileNotFoundError):
         vae.NativeTemporalVAE.from_pretrained(str(tmp_path / "nowhere"))
+
+
+# ---------------------------------------------------------------------------------------------- the handle's weight store (csrc/model.hip)
+def _upload(v, sd):
+    """a second upload into the handle of a NativeTemporalVAE through the C ABI (the class uploads once, in its constructor), then finalize"""
+    import ctypes as C
+    from univst_amd import _native
+    lib, st = _native.load(), _native.stream_ptr()
+    for k, t in sd.items():
+        t = t.detach().cuda().contiguous()
+        _native.check(lib.univst_vae_load_tensor(v._h, k.encode(), t.data_ptr(), 0 if t.dtype == torch.float16 else 1, (C.c_int64 * t.dim())(*t.shape),
+                                                 t.dim(), st), f"vae_load_tensor({k})")
+    torch.cuda.current_stream().synchronize()
+    _native.check(lib.univst_vae_finalize(v._h, st), "vae_finalize")
+
+
+def _small_io():
+    z = torch.randn(2, 4, 8, 8, generator=torch.Generator().manual_seed(1)).half().cuda()                  # F = 2, 8 x 8 latents
+    x = (torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(2)) * 2 - 1).half().cuda()
+    return z, x
+
+
+def _both(v, z, x):
+    return v.decode(z, num_frames=2).sample, v.encode(x).latent_dist.parameters
+
+
+def test_vae_fp32_upload_equals_fp16_upload(nat):
+    """the same fp16-valued weights uploaded as fp16 tensors (copied) and as fp32 tensors (converted on the device by the store's one convert kernel):
+    decode and encode are bit-identical"""
+    from univst_amd import synth, vae
+    sd = synth.vae_state_dict(SMALL, seed=3)
+    assert all(t.dtype == torch.float16 for t in sd.values())
+    z, x = _small_io()
+    d16, e16 = _both(vae.NativeTemporalVAE(sd, SMALL), z, x)
+    d32, e32 = _both(vae.NativeTemporalVAE({k: t.float() for k, t in sd.items()}, SMALL), z, x)
+    assert torch.isfinite(d16.float()).all() and torch.isfinite(e16.float()).all() and d16.float().abs().max().item() > 0
+    assert torch.equal(d16, d32) and torch.equal(e16, e32)
+
+
+def test_vae_reload_replaces_weights_and_derived_layouts(nat):
+    """every tensor of a second state dict loaded over a finalized handle, then finalize: the handle equals one that only ever saw the second state
+    dict (weights, conv layouts, scaled q projections and folded mix factors alike) and differs from what it computed before"""
+    from univst_amd import synth, vae
+    X, Y = synth.vae_state_dict(SMALL, seed=3), synth.vae_state_dict(SMALL, seed=4)
+    z, x = _small_io()
+    a = vae.NativeTemporalVAE(X, SMALL)
+    d1, e1 = _both(a, z, x)
+    _upload(a, Y)
+    d2, e2 = _both(a, z, x)
+    df, ef = _both(vae.NativeTemporalVAE(Y, SMALL), z, x)
+    assert torch.equal(d2, df) and torch.equal(e2, ef)
+    assert not torch.equal(d1, d2) and not torch.equal(e1, e2)
+
+
+def test_vae_missing_weight_is_named_and_the_name_does_not_stick(nat):
+    from univst_amd import synth, vae
+    sd = synth.vae_state_dict(SMALL, seed=3)
+    z, _ = _small_io()
+    k1, k2 = "decoder.mid_block.resnets.0.spatial_res_block.norm1.bias", "decoder.mid_block.resnets.0.spatial_res_block.norm2.bias"
+    a = vae.NativeTemporalVAE({k: t for k, t in sd.items() if k != k1}, SMALL)
+    with pytest.raises(RuntimeError, match="was never loaded") as e:
+        a.decode(z, num_frames=2)
+    assert f"'{k1}'" in str(e.value)
+    _upload(a, {k1: sd[k1]})                                # the missing tensor into the same handle: complete now
+    assert torch.equal(a.decode(z, num_frames=2).sample, vae.NativeTemporalVAE(sd, SMALL).decode(z, num_frames=2).sample)
+    b = vae.NativeTemporalVAE({k: t for k, t in sd.items() if k != k2}, SMALL)
+    with pytest.raises(RuntimeError, match="was never loaded") as e:
+        b.decode(z, num_frames=2)
+    assert f"'{k2}'" in str(e.value) and k1 not in str(e.value)

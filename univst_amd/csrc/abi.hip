@@ -7,7 +7,7 @@
 #include <new>
 
 #include "../../include/univst.h"
-#include "common.h"
+#include "comm.h"
 #include "kernels.h"
 #include "unet.h"
 #include "vae.h"

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "comm.h"
 #include "unet.h"
 
 int uv_launch_delay_us(double us, hipStream_t s);

@@ -38,6 +38,13 @@ const char* uv_get_error();
         }                                     \
     } while (0)
 
+// pass a failed call's status up
+#define UV_RUN(x)             \
+    do {                      \
+        int _rc = (x);        \
+        if (_rc) return _rc;  \
+    } while (0)
+
 // UV_REQUIRE inside a plan function (kernels.h: UvLaunchPlan): the error stays in the plan, which is returned
 #define UV_PLAN_REQUIRE(pl, cond, ...)                            \
     do {                                                          \

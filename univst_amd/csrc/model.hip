@@ -1,0 +1,184 @@
+// The handle plumbing the model graphs share (model.h): weight store, activation arena, weight-preparation kernels.  All of it runs at load,
+// finalize and reserve time, or as a hash lookup in front of a launch; nothing here is on the per-step path.
+#include "model.h"
+
+#include "../../include/univst.h"
+
+namespace {
+
+__global__ void convert_f32_f16_kernel(const float* __restrict__ in, half_t* __restrict__ out, long n) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (half_t)in[i];
+}
+// [Co][Ci][taps] -> [Co][taps][CiP] (zero padded input channels): 2-D convs (taps = kh*kw) and Conv3d (3,1,1) (taps = 3) alike
+__global__ void permute_conv_weight_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci, int taps, int CiP) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)Co * taps * CiP) return;
+    const int c = (int)(i % CiP), t = (int)((i / CiP) % taps), o = (int)(i / ((long)CiP * taps));
+    out[i] = c < Ci ? in[((long)o * Ci + c) * taps + t] : (half_t)0.f;
+}
+// [Co][Ci][3][3] -> tap-inner [Co][Ci/64][9][64] (GemmParams::korder = 1: the nine taps of a 64-channel slab are consecutive k tiles)
+__global__ void permute_conv_weight_ti_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)Co * Ci * 9) return;
+    const int j = (int)(i % 64), t = (int)((i / 64) % 9), q = (int)((i / (64 * 9)) % (Ci / 64)), o = (int)(i / ((long)Ci * 9));
+    out[i] = in[((long)o * Ci + q * 64 + j) * 9 + t];
+}
+__global__ void scale_f16_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, long n, float f) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (half_t)((float)in[i] * f);
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ arena
+int uv_slab_grow(char** base, size_t* size, size_t need) {
+    if (*size >= need) return UV_OK;
+    UV_HIP(hipDeviceSynchronize());
+    if (*base) UV_HIP(hipFree(*base));
+    *base = nullptr;
+    *size = 0;
+    UV_HIP(hipMalloc((void**)base, need));
+    *size = need;
+    return UV_OK;
+}
+
+void* Arena::alloc(size_t bytes) {
+    bytes = (bytes + 255) & ~size_t(255);
+    for (size_t i = 0; i < blocks.size(); ++i) {
+        if (blocks[i].free && blocks[i].size >= bytes) {
+            if (blocks[i].size > bytes) {
+                Block rest{blocks[i].off + bytes, blocks[i].size - bytes, true};
+                blocks[i].size = bytes;
+                blocks.insert(blocks.begin() + i + 1, rest);
+            }
+            blocks[i].free = false;
+            size_t used = blocks[i].off + bytes;
+            if (used > high_water) high_water = used;
+            return base + blocks[i].off;
+        }
+    }
+    return nullptr;
+}
+void Arena::release(void* p) {
+    if (!p) return;
+    size_t off = (char*)p - base;
+    for (size_t i = 0; i < blocks.size(); ++i) {
+        if (blocks[i].off == off && !blocks[i].free) {
+            blocks[i].free = true;
+            if (i + 1 < blocks.size() && blocks[i + 1].free) {
+                blocks[i].size += blocks[i + 1].size;
+                blocks.erase(blocks.begin() + i + 1);
+            }
+            if (i > 0 && blocks[i - 1].free) {
+                blocks[i - 1].size += blocks[i].size;
+                blocks.erase(blocks.begin() + i);
+            }
+            return;
+        }
+    }
+}
+void Arena::reset() {
+    blocks.clear();
+    blocks.push_back(Block{0, size, true});
+}
+int Arena::ensure(size_t bytes) {
+    UV_RUN(uv_slab_grow(&base, &size, bytes));
+    reset();
+    return UV_OK;
+}
+
+// ------------------------------------------------------------------------------------------ weight store
+WeightStore::~WeightStore() {
+    for (auto& kv : weights) (void)hipFree(kv.second.ptr);
+    clear_derived();
+}
+
+int WeightStore::load(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
+    UV_REQUIRE(key && dev_ptr && ndim >= 1 && ndim <= 5, "load_tensor: bad arguments");
+    UV_REQUIRE(dtype == UNIVST_F16 || dtype == UNIVST_F32, "load_tensor(%s): dtype %d unsupported", key, dtype);
+    long n = 1;
+    WTensor t;
+    for (int i = 0; i < ndim; ++i) {
+        n *= shape[i];
+        t.shape.push_back(shape[i]);
+    }
+    UV_REQUIRE(n > 0, "load_tensor(%s): empty tensor", key);
+    UV_HIP(hipMalloc((void**)&t.ptr, (size_t)n * sizeof(half_t)));
+    if (dtype == UNIVST_F16) UV_HIP(hipMemcpyAsync(t.ptr, dev_ptr, (size_t)n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+    else hipLaunchKernelGGL(convert_f32_f16_kernel, dim3(nb(n)), dim3(256), 0, s, (const float*)dev_ptr, t.ptr, n);
+    UV_LAUNCH_CHECK();
+    auto it = weights.find(key);
+    if (it != weights.end()) {      // (work queued on s may still read the tensor this one replaces)
+        UV_HIP(hipStreamSynchronize(s));
+        (void)hipFree(it->second.ptr);
+    }
+    weights[key] = t;
+    return UV_OK;
+}
+
+const WTensor* WeightStore::find(const std::string& k) const {
+    auto it = weights.find(k);
+    if (it != weights.end()) return &it->second;
+    auto jt = derived.find(k);
+    return jt == derived.end() ? nullptr : &jt->second;
+}
+
+half_t* WeightStore::W(const std::string& k) {
+    const WTensor* t = find(k);
+    if (!t) {
+        if (missing.empty()) missing = k;
+        return nullptr;
+    }
+    return t->ptr;
+}
+
+int WeightStore::missing_error(const char* who) const {
+    uv_set_error("%s: weight '%s' was never loaded", who, missing.c_str());
+    return UV_ERR_STATE;
+}
+
+int WeightStore::derive(const std::string& k, std::vector<long> shape, half_t** out) {
+    auto it = derived.find(k);
+    if (it != derived.end()) {
+        (void)hipFree(it->second.ptr);
+        derived.erase(it);
+    }
+    long n = 1;
+    for (long v : shape) n *= v;
+    WTensor t;
+    t.shape = shape;
+    UV_HIP(hipMalloc((void**)&t.ptr, (size_t)n * sizeof(half_t)));
+    derived[k] = t;
+    *out = t.ptr;
+    return UV_OK;
+}
+
+void WeightStore::clear_derived() {
+    for (auto& kv : derived) (void)hipFree(kv.second.ptr);
+    derived.clear();
+}
+
+// ------------------------------------------------------------------------------------------ weight preparation
+int uv_derive_conv_layouts(WeightStore& st, const std::string& key, hipStream_t s) {
+    const WTensor* t = st.find(key);
+    UV_REQUIRE(t && t->shape.size() >= 3, "%s: not a loaded conv weight", key.c_str());
+    const int Co = (int)t->shape[0], Ci = (int)t->shape[1], CiP = (Ci + 7) / 8 * 8;
+    int taps = 1;
+    for (size_t d = 2; d < t->shape.size(); ++d) taps *= (int)t->shape[d];
+    half_t* d;
+    UV_RUN(st.derive(key + "#nhwc", {Co, taps, CiP}, &d));
+    hipLaunchKernelGGL(permute_conv_weight_kernel, dim3(nb((long)Co * taps * CiP)), dim3(256), 0, s, t->ptr, d, Co, Ci, taps, CiP);
+    if (taps == 9 && Ci % 64 == 0) {
+        UV_RUN(st.derive(key + "#ti", {Co, Ci / 64, 9, 64}, &d));
+        hipLaunchKernelGGL(permute_conv_weight_ti_kernel, dim3(nb((long)Co * Ci * 9)), dim3(256), 0, s, t->ptr, d, Co, Ci);
+    }
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+
+int uv_launch_scale_f16(const half_t* in, half_t* out, long n, float f, hipStream_t s) {
+    hipLaunchKernelGGL(scale_f16_kernel, dim3(nb(n)), dim3(256), 0, s, in, out, n, f);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}

@@ -17,13 +17,11 @@
 // convs (Cin = 3 / 2) and the 1x5 / 5x1 GRU convs gather their operand rows here (im2col) and run as plain GEMMs.
 #include <math.h>
 
-#include "common.h"
 #include "kernels.h"
+#include "model.h"
 #include "raft.h"
 
 namespace {
-
-inline unsigned nb(long n) { return (unsigned)((n + 255) / 256); }
 
 // ---------------------------------------------------------------- weight preparation
 __global__ void r_convert_f16_f32_kernel(const half_t* __restrict__ in, float* __restrict__ out, long n) {
@@ -555,14 +553,7 @@ int Raft::reserve(int Hn, int Wn) {
                  o_f1 = carve((size_t)N * 128 * 2), o_motion = carve((size_t)N * 128 * 2), o_gcol = carve((size_t)N * 1920 * 2), o_zr = carve((size_t)N * 256 * 2),
                  o_qpre = carve((size_t)N * 128 * 2), o_fh = carve((size_t)N * 256 * 2), o_delta = carve((size_t)N * 8 * 2), o_mh = carve((size_t)N * 256 * 2),
                  o_mask = carve((size_t)N * 576 * 2);
-    if (slab_bytes < off) {
-        UV_HIP(hipDeviceSynchronize());
-        if (slab) UV_HIP(hipFree(slab));
-        slab = nullptr;
-        slab_bytes = 0;
-        UV_HIP(hipMalloc((void**)&slab, off));
-        slab_bytes = off;
-    }
+    UV_RUN(uv_slab_grow(&slab, &slab_bytes, off));
     col7 = (half_t*)(slab + o_col7);
     for (int i = 0; i < 4; ++i) act[i] = (half_t*)(slab + o_act[i]);
     in_part = (float*)(slab + o_part);
@@ -591,12 +582,6 @@ int Raft::reserve(int Hn, int Wn) {
     W = Wn;
     return UV_OK;
 }
-
-#define RUN(x)               \
-    do {                     \
-        int _rc = (x);       \
-        if (_rc) return _rc; \
-    } while (0)
 
 namespace {
 struct RFwd {
@@ -666,8 +651,8 @@ struct RFwd {
     int encoder(const std::string& enc, bool inorm, int imgs, int H, int W, half_t* dst) {
         int hc = H / 2, wc = W / 2, C = 64;
         int ix = 0, iy1 = 1, iy2 = 2, id = 3;
-        RUN(lin(enc + ".convnormrelu", u.col7, (long)imgs * hc * wc, u.act[ix], 64));
-        RUN(norm(inorm, u.act[ix], imgs, (long)hc * wc, 64, 1));
+        UV_RUN(lin(enc + ".convnormrelu", u.col7, (long)imgs * hc * wc, u.act[ix], 64));
+        UV_RUN(norm(inorm, u.act[ix], imgs, (long)hc * wc, 64, 1));
         const int chans[3] = {64, 96, 128};
         for (int L = 1; L <= 3; ++L)
             for (int B = 0; B < 2; ++B) {
@@ -675,14 +660,14 @@ struct RFwd {
                 const int st = (B == 0 && L > 1) ? 2 : 1, Co = chans[L - 1];
                 const int ho = (hc - 1) / st + 1, wo = (wc - 1) / st + 1;
                 const long Po = (long)ho * wo;
-                RUN(conv(pre + ".convnormrelu1", u.act[ix], imgs, hc, wc, st, u.act[iy1], Co));
-                RUN(norm(inorm, u.act[iy1], imgs, Po, Co, 1));
-                RUN(conv(pre + ".convnormrelu2", u.act[iy1], imgs, ho, wo, 1, u.act[iy2], Co));
-                RUN(norm(inorm, u.act[iy2], imgs, Po, Co, 1));
+                UV_RUN(conv(pre + ".convnormrelu1", u.act[ix], imgs, hc, wc, st, u.act[iy1], Co));
+                UV_RUN(norm(inorm, u.act[iy1], imgs, Po, Co, 1));
+                UV_RUN(conv(pre + ".convnormrelu2", u.act[iy1], imgs, ho, wo, 1, u.act[iy2], Co));
+                UV_RUN(norm(inorm, u.act[iy2], imgs, Po, Co, 1));
                 const half_t* res = u.act[ix];
                 if (st == 2) {
-                    RUN(conv(pre + ".downsample", u.act[ix], imgs, hc, wc, 2, u.act[id], Co));
-                    RUN(norm(inorm, u.act[id], imgs, Po, Co, 0));
+                    UV_RUN(conv(pre + ".downsample", u.act[ix], imgs, hc, wc, 2, u.act[id], Co));
+                    UV_RUN(norm(inorm, u.act[id], imgs, Po, Co, 0));
                     res = u.act[id];
                 }
                 hipLaunchKernelGGL(r_add_relu_kernel, dim3(nb(imgs * Po * Co / 8)), dim3(256), 0, s, res, (const half_t*)u.act[iy2], u.act[iy1], imgs * Po * Co / 8);
@@ -708,17 +693,17 @@ static int raft_check_size(int H, int W) {
 
 // fills fmap [2][N][256], h32 / h16 (tanh half of the context encoder) and ctx16 (relu half); img1 / img2 uint8 [H][W][3]
 int Raft::encode(const uint8_t* img1, const uint8_t* img2, int Hn, int Wn, hipStream_t s) {
-    RUN(raft_check_size(Hn, Wn));
-    if (!finalized) RUN(finalize(s));
-    RUN(reserve(Hn, Wn));
+    UV_RUN(raft_check_size(Hn, Wn));
+    if (!finalized) UV_RUN(finalize(s));
+    UV_RUN(reserve(Hn, Wn));
     RFwd f{*this, s};
     const int Ho = Hn / 2, Wo = Wn / 2;
     const long P2 = (long)Ho * Wo, N = (long)(Hn / 8) * (Wn / 8);
     hipLaunchKernelGGL(r_im2col7_kernel, dim3(nb(P2 * 19)), dim3(256), 0, s, (const void*)img1, 0, 3, 1, Hn, Wn, 2, Ho, Wo, 152, col7);
     hipLaunchKernelGGL(r_im2col7_kernel, dim3(nb(P2 * 19)), dim3(256), 0, s, (const void*)img2, 0, 3, 1, Hn, Wn, 2, Ho, Wo, 152, col7 + P2 * 152);
     UV_LAUNCH_CHECK();
-    RUN(f.encoder("feature_encoder", true, 2, Hn, Wn, fmap));
-    RUN(f.encoder("context_encoder", false, 1, Hn, Wn, ctxout));
+    UV_RUN(f.encoder("feature_encoder", true, 2, Hn, Wn, fmap));
+    UV_RUN(f.encoder("context_encoder", false, 1, Hn, Wn, ctxout));
     hipLaunchKernelGGL(r_ctx_split_kernel, dim3(nb(N * 128)), dim3(256), 0, s, ctxout, h32, h16, ctx16, N * 128);
     UV_LAUNCH_CHECK();
     return UV_OK;
@@ -732,10 +717,10 @@ int Raft::gru(float* hs, half_t* hh16, const half_t* ctx, const half_t* mot, int
         const std::string g = "update_block.recurrent_block.convgru" + std::to_string(d + 1);
         hipLaunchKernelGGL(r_gru_im2col_kernel, dim3(nb(N * 240)), dim3(256), 0, s, hs, ctx, mot, (const half_t*)nullptr, d, hh, ww, gcol);
         UV_LAUNCH_CHECK();
-        RUN(f.lin(g + ".zr", gcol, N, zr, 256));
+        UV_RUN(f.lin(g + ".zr", gcol, N, zr, 256));
         hipLaunchKernelGGL(r_gru_im2col_kernel, dim3(nb(N * 240)), dim3(256), 0, s, hs, ctx, mot, (const half_t*)zr, d, hh, ww, gcol);
         UV_LAUNCH_CHECK();
-        RUN(f.lin(g + ".convq", gcol, N, qpre, 128));
+        UV_RUN(f.lin(g + ".convq", gcol, N, qpre, 128));
         hipLaunchKernelGGL(r_gru_blend_kernel, dim3(nb(N * 128)), dim3(256), 0, s, zr, qpre, hs, hh16, N * 128);
         UV_LAUNCH_CHECK();
     }
@@ -747,41 +732,41 @@ int Raft::update(int hh, int ww, hipStream_t s) {
     RFwd f{*this, s};
     const long N = (long)hh * ww;
     const std::string me = "update_block.motion_encoder.";
-    RUN(uv_raft_corr_lookup(pyr, coords1, hh, ww, nullptr, corr16, s));
-    RUN(f.conv(me + "convcorr1", corr16, 1, hh, ww, 1, c1, 256));
-    RUN(f.relu(c1, N * 256));
-    RUN(f.conv(me + "convcorr2", c1, 1, hh, ww, 1, c2, 256));                 // cat[corr, flow]: columns 0..191 | 192..255 of one buffer
+    UV_RUN(uv_raft_corr_lookup(pyr, coords1, hh, ww, nullptr, corr16, s));
+    UV_RUN(f.conv(me + "convcorr1", corr16, 1, hh, ww, 1, c1, 256));
+    UV_RUN(f.relu(c1, N * 256));
+    UV_RUN(f.conv(me + "convcorr2", c1, 1, hh, ww, 1, c2, 256));                 // cat[corr, flow]: columns 0..191 | 192..255 of one buffer
     hipLaunchKernelGGL(r_im2col7_kernel, dim3(nb(N * 13)), dim3(256), 0, s, (const void*)coords1, 1, 2, 1, hh, ww, 1, hh, ww, 104, colf);
     UV_LAUNCH_CHECK();
-    RUN(f.lin(me + "convflow1", colf, N, f1, 128));
-    RUN(f.relu(f1, N * 128));
-    RUN(f.conv(me + "convflow2", f1, 1, hh, ww, 1, c2 + 192, 256));
-    RUN(f.relu(c2, N * 256));
-    RUN(f.conv(me + "conv", c2, 1, hh, ww, 1, motion, 128));                  // 126 channels + 2 zero rows ...
-    RUN(f.relu(motion, N * 128));
+    UV_RUN(f.lin(me + "convflow1", colf, N, f1, 128));
+    UV_RUN(f.relu(f1, N * 128));
+    UV_RUN(f.conv(me + "convflow2", f1, 1, hh, ww, 1, c2 + 192, 256));
+    UV_RUN(f.relu(c2, N * 256));
+    UV_RUN(f.conv(me + "conv", c2, 1, hh, ww, 1, motion, 128));                  // 126 channels + 2 zero rows ...
+    UV_RUN(f.relu(motion, N * 128));
     hipLaunchKernelGGL(r_set_flow_kernel, dim3(nb(N)), dim3(256), 0, s, motion, coords1, hh, ww);      // ... that take the flow
     UV_LAUNCH_CHECK();
-    RUN(gru(h32, h16, ctx16, motion, hh, ww, s));
-    RUN(f.conv("update_block.flow_head.conv1", h16, 1, hh, ww, 1, fh, 256));
-    RUN(f.relu(fh, N * 256));
-    RUN(f.conv("update_block.flow_head.conv2", fh, 1, hh, ww, 1, delta, 8));
+    UV_RUN(gru(h32, h16, ctx16, motion, hh, ww, s));
+    UV_RUN(f.conv("update_block.flow_head.conv1", h16, 1, hh, ww, 1, fh, 256));
+    UV_RUN(f.relu(fh, N * 256));
+    UV_RUN(f.conv("update_block.flow_head.conv2", fh, 1, hh, ww, 1, delta, 8));
     hipLaunchKernelGGL(r_update_coords_kernel, dim3(nb(N)), dim3(256), 0, s, coords1, delta, N);
     UV_LAUNCH_CHECK();
     return UV_OK;
 }
 
 int Raft::forward(const uint8_t* img1, const uint8_t* img2, int Hn, int Wn, float* flow, hipStream_t s) {
-    RUN(encode(img1, img2, Hn, Wn, s));
+    UV_RUN(encode(img1, img2, Hn, Wn, s));
     RFwd f{*this, s};
     const int hh = Hn / 8, ww = Wn / 8;
     const long N = (long)hh * ww;
-    RUN(uv_raft_corr_pyramid(fmap, fmap + N * 256, hh, ww, pyr, s));
+    UV_RUN(uv_raft_corr_pyramid(fmap, fmap + N * 256, hh, ww, pyr, s));
     hipLaunchKernelGGL(r_init_coords_kernel, dim3(nb(N)), dim3(256), 0, s, coords1, hh, ww);
     UV_LAUNCH_CHECK();
-    for (int it = 0; it < 12; ++it) RUN(update(hh, ww, s));
+    for (int it = 0; it < 12; ++it) UV_RUN(update(hh, ww, s));
     // only the final flow is returned: the mask predictor runs once, on the last hidden state
-    RUN(f.conv("mask_predictor.convrelu", h16, 1, hh, ww, 1, mh, 256));
-    RUN(f.relu(mh, N * 256));
-    RUN(f.conv("mask_predictor.conv", mh, 1, hh, ww, 1, mask, 576));
+    UV_RUN(f.conv("mask_predictor.convrelu", h16, 1, hh, ww, 1, mh, 256));
+    UV_RUN(f.relu(mh, N * 256));
+    UV_RUN(f.conv("mask_predictor.conv", mh, 1, hh, ww, 1, mask, 576));
     return uv_raft_convex_upsample(coords1, 1, mask, hh, ww, flow, s);
 }

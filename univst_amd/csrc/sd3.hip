@@ -16,7 +16,7 @@
 
 #include "common.h"
 #include "kernels.h"
-#include "unet.h"
+#include "comm.h"
 #include "../../include/univst.h"
 
 namespace {
@@ -356,12 +356,6 @@ int linear(const half_t* X, long ldx, long M, int K, const half_t* W, const half
 
 }  // namespace
 
-#define RUN(x)                \
-    do {                      \
-        int _rc = (x);        \
-        if (_rc) return _rc;  \
-    } while (0)
-
 extern "C" {
 
 int univst_rmsnorm_heads(void* x, int64_t ld, int64_t rows, int heads, int d, const void* weight, float eps, void* stream) {
@@ -446,8 +440,8 @@ int univst_sd3_adain_shift(void* qkv, int64_t ld, int F, int N, int C, int heads
     float *smean = (float*)ws, *sstd = smean + (long)F * 2 * C, *cmean = sstd + (long)F * 2 * C, *cstd = cmean + (long)F * 2 * C;
     float *mu = cstd + (long)F * 2 * C, *rstd = mu + (long)F * 2 * heads;
     const long FN = (long)F * N;
-    RUN(uv_launch_colstats(q + FN * ld + C, ld, F, N, 2 * C, smean, sstd, s));           // style branch K | V: per (frame, channel) over N
-    RUN(uv_launch_colstats(q + 2 * FN * ld + C, ld, F, N, 2 * C, cmean, cstd, s));       // stylised branch K | V
+    UV_RUN(uv_launch_colstats(q + FN * ld + C, ld, F, N, 2 * C, smean, sstd, s));           // style branch K | V: per (frame, channel) over N
+    UV_RUN(uv_launch_colstats(q + 2 * FN * ld + C, ld, F, N, 2 * C, cmean, cstd, s));       // stylised branch K | V
     hipLaunchKernelGGL(sd3_group_stats_kernel, dim3((unsigned)((F * 2 * heads + 127) / 128)), dim3(128), 0, s, cmean, cstd, F, N, C, heads, mu, rstd);
     hipLaunchKernelGGL(sd3_shift_kernel, dim3((unsigned)((FN + 3) / 4)), dim3(256), 0, s, q, (long)ld, F, N, C, heads, smean, sstd, mu, rstd, alpha,
                        beta, gamma);
@@ -528,7 +522,7 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
             const unsigned par = uv_comm_kv_parity(comm);
             o_prev = 65536 + (2 + 2 * par) * slot;
             o_rfirst = o_prev + slot;
-            RUN(uv_comm_kv_begin(comm));
+            UV_RUN(uv_comm_kv_begin(comm));
             if (rank < world - 1) {
                 const long cpn = (long)N * (Cin / 8);
                 const unsigned cgrid = (unsigned)((cpn + 255) / 256);
@@ -537,25 +531,25 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
                                        (half_t*)(ws_c + o_send) + (long)b * N * Cin, (long)Cin, (long)N, Cin / 8);
                 UV_LAUNCH_CHECK();
             }
-            if (rank < world - 1 || emu) RUN(uv_comm_fork(comm, s, &xs));
-            RUN(uv_comm_kv_post_halo(comm, o_send, o_prev, bytes_h, xs));
+            if (rank < world - 1 || emu) UV_RUN(uv_comm_fork(comm, s, &xs));
+            UV_RUN(uv_comm_kv_post_halo(comm, o_send, o_prev, bytes_h, xs));
         }
         if (fused3(w->to_q, w->to_k, w->to_v, w->to_q_bias, w->to_k_bias, w->to_v_bias)) {
-            RUN(linear(x, Cin, rows_i, Cin, H(w->to_q), H(w->to_q_bias), 3 * C, qkv_i, 3 * C, s));
+            UV_RUN(linear(x, Cin, rows_i, Cin, H(w->to_q), H(w->to_q_bias), 3 * C, qkv_i, 3 * C, s));
         } else {
-            RUN(linear(x, Cin, rows_i, Cin, H(w->to_q), H(w->to_q_bias), C, qkv_i, 3 * C, s));
-            RUN(linear(x, Cin, rows_i, Cin, H(w->to_k), H(w->to_k_bias), C, qkv_i + C, 3 * C, s));
-            RUN(linear(x, Cin, rows_i, Cin, H(w->to_v), H(w->to_v_bias), C, qkv_i + 2 * C, 3 * C, s));
+            UV_RUN(linear(x, Cin, rows_i, Cin, H(w->to_q), H(w->to_q_bias), C, qkv_i, 3 * C, s));
+            UV_RUN(linear(x, Cin, rows_i, Cin, H(w->to_k), H(w->to_k_bias), C, qkv_i + C, 3 * C, s));
+            UV_RUN(linear(x, Cin, rows_i, Cin, H(w->to_v), H(w->to_v_bias), C, qkv_i + 2 * C, 3 * C, s));
         }
         // with q / k RMSNorm (SD3.5) the attention's scale * log2(e) is applied to q inside the norm (one fp16 rounding, as the norm's
         // own output has): the attention then runs with AttnParams::q_prescaled, which the pipelined head_dim-64 kernel needs
         const float qscale = 1.4426950408889634f / sqrtf((float)head_dim);
         const bool presc = w->norm_q && w->norm_k && (!enc || (w->norm_added_q && w->norm_added_k));
-        if (w->norm_q && w->norm_k) RUN(launch_rms_pair(qkv_i, 3 * C, rows_i, heads, head_dim, 0, H(w->norm_q), C, H(w->norm_k), rms_eps, s, presc ? qscale : 1.f));
-        else if (w->norm_q) RUN(univst_rmsnorm_heads(qkv_i, 3 * C, rows_i, heads, head_dim, w->norm_q, rms_eps, s));
-        else if (w->norm_k) RUN(univst_rmsnorm_heads(qkv_i + C, 3 * C, rows_i, heads, head_dim, w->norm_k, rms_eps, s));
+        if (w->norm_q && w->norm_k) UV_RUN(launch_rms_pair(qkv_i, 3 * C, rows_i, heads, head_dim, 0, H(w->norm_q), C, H(w->norm_k), rms_eps, s, presc ? qscale : 1.f));
+        else if (w->norm_q) UV_RUN(univst_rmsnorm_heads(qkv_i, 3 * C, rows_i, heads, head_dim, w->norm_q, rms_eps, s));
+        else if (w->norm_k) UV_RUN(univst_rmsnorm_heads(qkv_i + C, 3 * C, rows_i, heads, head_dim, w->norm_k, rms_eps, s));
         if (shift) {          // pnp_utils.py:183-194 (alpha 0.8, gamma 2.0); window test + beta come from the caller, evaluated in double
-            RUN(univst_sd3_adain_shift(qkv_i, 3 * C, Fb, N, C, heads, 0.8f, beta, 2.0f, st, s));
+            UV_RUN(univst_sd3_adain_shift(qkv_i, 3 * C, Fb, N, C, heads, 0.8f, beta, 2.0f, st, s));
         }
         if (sharded && (rank == 0 || emu)) {          // the clip's first frame: finished K | V rows of every branch -> every rank
             const long cpn = (long)N * (2 * C / 8);
@@ -566,22 +560,22 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
                                        (half_t*)(ws_c + o_first) + (long)b * N * 2 * C, (long)2 * C, (long)N, 2 * C / 8);
                 UV_LAUNCH_CHECK();
             }
-            RUN(uv_comm_fork(comm, s, &xs));
-            RUN(uv_comm_kv_post_first(comm, o_first, o_rfirst, bytes_kv, xs));
+            UV_RUN(uv_comm_fork(comm, s, &xs));
+            UV_RUN(uv_comm_kv_post_first(comm, o_first, o_rfirst, bytes_kv, xs));
         }
         if (enc) {
             const half_t* e = H(enc);
             if (fused3(w->add_q, w->add_k, w->add_v, w->add_q_bias, w->add_k_bias, w->add_v_bias)) {
-                RUN(linear(e, Cin, rows_t, Cin, H(w->add_q), H(w->add_q_bias), 3 * C, qkv_t, 3 * C, s));
+                UV_RUN(linear(e, Cin, rows_t, Cin, H(w->add_q), H(w->add_q_bias), 3 * C, qkv_t, 3 * C, s));
             } else {
-                RUN(linear(e, Cin, rows_t, Cin, H(w->add_q), H(w->add_q_bias), C, qkv_t, 3 * C, s));
-                RUN(linear(e, Cin, rows_t, Cin, H(w->add_k), H(w->add_k_bias), C, qkv_t + C, 3 * C, s));
-                RUN(linear(e, Cin, rows_t, Cin, H(w->add_v), H(w->add_v_bias), C, qkv_t + 2 * C, 3 * C, s));
+                UV_RUN(linear(e, Cin, rows_t, Cin, H(w->add_q), H(w->add_q_bias), C, qkv_t, 3 * C, s));
+                UV_RUN(linear(e, Cin, rows_t, Cin, H(w->add_k), H(w->add_k_bias), C, qkv_t + C, 3 * C, s));
+                UV_RUN(linear(e, Cin, rows_t, Cin, H(w->add_v), H(w->add_v_bias), C, qkv_t + 2 * C, 3 * C, s));
             }
             if (w->norm_added_q && w->norm_added_k)
-                RUN(launch_rms_pair(qkv_t, 3 * C, rows_t, heads, head_dim, 0, H(w->norm_added_q), C, H(w->norm_added_k), rms_eps, s, presc ? qscale : 1.f));
-            else if (w->norm_added_q) RUN(univst_rmsnorm_heads(qkv_t, 3 * C, rows_t, heads, head_dim, w->norm_added_q, rms_eps, s));
-            else if (w->norm_added_k) RUN(univst_rmsnorm_heads(qkv_t + C, 3 * C, rows_t, heads, head_dim, w->norm_added_k, rms_eps, s));
+                UV_RUN(launch_rms_pair(qkv_t, 3 * C, rows_t, heads, head_dim, 0, H(w->norm_added_q), C, H(w->norm_added_k), rms_eps, s, presc ? qscale : 1.f));
+            else if (w->norm_added_q) UV_RUN(univst_rmsnorm_heads(qkv_t, 3 * C, rows_t, heads, head_dim, w->norm_added_q, rms_eps, s));
+            else if (w->norm_added_k) UV_RUN(univst_rmsnorm_heads(qkv_t + C, 3 * C, rows_t, heads, head_dim, w->norm_added_k, rms_eps, s));
         }
         AttnParams a;
         a.k = qkv_i + C; a.v = qkv_i + 2 * C; a.ldkv = 3 * C;
@@ -598,24 +592,24 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
             a.q = qkv_i; a.ldq = 3 * C; a.Nq = N; a.o = o_i; a.ldo = C;
             a.state_out = phase == 1 ? state_i : nullptr;
             a.state_in = phase == 2 ? state_i : nullptr;
-            RUN(uv_launch_attention(a, s));                                  // image queries over [first | prev | cur] ++ text keys
+            UV_RUN(uv_launch_attention(a, s));                                  // image queries over [first | prev | cur] ++ text keys
             if (enc) {
                 a.q = qkv_t; a.Nq = Nt; a.o = o_t;
                 a.state_out = phase == 1 ? state_t : nullptr;
                 a.state_in = phase == 2 ? state_t : nullptr;
-                RUN(uv_launch_attention(a, s));                              // text queries over the same key set
+                UV_RUN(uv_launch_attention(a, s));                              // text queries over the same key set
             }
             return UV_OK;
         };
         if (!two_phase) {
             index(0);
             UV_LAUNCH_CHECK();
-            RUN(attend(0));
+            UV_RUN(attend(0));
         } else {
             index(1);
             UV_LAUNCH_CHECK();
-            RUN(attend(1));                                                  // the keys this rank holds ++ the text keys, while the halo is on the wire
-            RUN(uv_comm_kv_wait(comm, s));
+            UV_RUN(attend(1));                                                  // the keys this rank holds ++ the text keys, while the halo is on the wire
+            UV_RUN(uv_comm_kv_wait(comm, s));
             // the halo frames, rows behind the local ones [previous: nbr x N | first: nbr x N]: the previous frame from its hidden rows (to_k | to_v +
             // biases -> k RMSNorm -> its shift), the clip's first frame as the K | V rows rank 0 finished
             half_t* qh = qkv_i + rows_i * 3 * C;
@@ -623,15 +617,15 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
             const bool kvf = H(w->to_v) == H(w->to_k) + (long)C * Cin && ((!w->to_k_bias && !w->to_v_bias) || (w->to_k_bias && H(w->to_v_bias) == H(w->to_k_bias) + C));
             const half_t* hx = (const half_t*)(ws_c + o_prev);
             if (kvf) {
-                RUN(linear(hx, Cin, hrows, Cin, H(w->to_k), H(w->to_k_bias), 2 * C, qh + C, 3 * C, s));
+                UV_RUN(linear(hx, Cin, hrows, Cin, H(w->to_k), H(w->to_k_bias), 2 * C, qh + C, 3 * C, s));
             } else {
-                RUN(linear(hx, Cin, hrows, Cin, H(w->to_k), H(w->to_k_bias), C, qh + C, 3 * C, s));
-                RUN(linear(hx, Cin, hrows, Cin, H(w->to_v), H(w->to_v_bias), C, qh + 2 * C, 3 * C, s));
+                UV_RUN(linear(hx, Cin, hrows, Cin, H(w->to_k), H(w->to_k_bias), C, qh + C, 3 * C, s));
+                UV_RUN(linear(hx, Cin, hrows, Cin, H(w->to_v), H(w->to_v_bias), C, qh + 2 * C, 3 * C, s));
             }
-            if (w->norm_k) RUN(univst_rmsnorm_heads(qh + C, 3 * C, hrows, heads, head_dim, w->norm_k, rms_eps, s));
+            if (w->norm_k) UV_RUN(univst_rmsnorm_heads(qh + C, 3 * C, hrows, heads, head_dim, w->norm_k, rms_eps, s));
             if (shift)            // the previous frame of the three branches is the shift kernel's [3][F = 1][N]; its q columns are never projected and never
                                   // read (the kernel mixes them element-wise, statistics come from k / v only)
-                RUN(univst_sd3_adain_shift(qh, 3 * C, 1, N, C, heads, 0.8f, beta, 2.0f, st, s));
+                UV_RUN(univst_sd3_adain_shift(qh, 3 * C, 1, N, C, heads, 0.8f, beta, 2.0f, st, s));
             {
                 const long cpn = hrows * (2 * C / 8);
                 hipLaunchKernelGGL(sd3_copy2d_kernel, dim3((unsigned)((cpn + 255) / 256)), dim3(256), 0, s, (const half_t*)(ws_c + o_rfirst), (long)2 * C,
@@ -640,20 +634,20 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
             }
             index(2);
             UV_LAUNCH_CHECK();
-            RUN(attend(2));                                                  // the halo frames: continues from the (m, l) state, merges
+            UV_RUN(attend(2));                                                  // the halo frames: continues from the (m, l) state, merges
         }
         if (sharded) {
             // nobody starts the next exchange before every rank has consumed this one.  It also retires the forked stream without an event: the barrier
             // completes only after the peers consumed the packs, i.e. after this rank's multicast and raise have run
-            RUN(uv_comm_barrier(comm, s));
+            UV_RUN(uv_comm_barrier(comm, s));
             (void)xs;
         }
         // (gr: the block's gated residual rides in the out-projection's epilogue: out = res + gate[b] (.) to_out(o))
-        RUN(linear(o_i, C, rows_i, C, H(w->to_out), H(w->to_out_bias), Cin, (half_t*)out_img, Cin, s, gr ? H(gr->res_img) : nullptr,
+        UV_RUN(linear(o_i, C, rows_i, C, H(w->to_out), H(w->to_out_bias), Cin, (half_t*)out_img, Cin, s, gr ? H(gr->res_img) : nullptr,
                    gr ? H(gr->gate_img) : nullptr, gr ? gr->ld_gate_img : 0, N));
         if (enc) {
             if (w->to_add_out)
-                RUN(linear(o_t, C, rows_t, C, H(w->to_add_out), H(w->to_add_out_bias), Cin, (half_t*)out_txt, Cin, s, gr ? H(gr->res_txt) : nullptr,
+                UV_RUN(linear(o_t, C, rows_t, C, H(w->to_add_out), H(w->to_add_out_bias), Cin, (half_t*)out_txt, Cin, s, gr ? H(gr->res_txt) : nullptr,
                            gr ? H(gr->gate_txt) : nullptr, gr ? gr->ld_gate_txt : 0, Nt));
             else UV_HIP(hipMemcpyAsync(out_txt, o_t, (size_t)rows_t * C * sizeof(half_t), hipMemcpyDeviceToDevice, s));      // context_pre_only
         }

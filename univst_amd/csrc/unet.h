@@ -2,64 +2,12 @@
 #pragma once
 #include <string>
 #include <unordered_map>
-#include <vector>
 
 #include "../../include/univst.h"
-#include "common.h"
+#include "model.h"
 
-typedef univst_pnp univst_pnp_t;
-struct UNet;
-// comm.hip
-int uv_unet_attach_comm(UNet& u, univst_comm* c);
-void uv_comm_bind_stream(univst_comm* c, hipStream_t s);
-unsigned uv_comm_kv_parity(const univst_comm* c);
-int uv_comm_poll(univst_comm* c);
-int uv_comm_allreduce(univst_comm* c, float* buf, int n, hipStream_t s);
-int uv_comm_kv_exchange(univst_comm* c, long o_send, long o_first, long o_prev, long o_rfirst, long nbytes, hipStream_t s);
-int uv_comm_kv_post(univst_comm* c, long o_send, long o_first, long o_prev, long o_rfirst, long nbytes, hipStream_t x);
-int uv_comm_kv_begin(univst_comm* c);
-int uv_comm_kv_post_halo(univst_comm* c, long o_send, long o_prev, long nbytes, hipStream_t x);
-int uv_comm_kv_post_first(univst_comm* c, long o_first, long o_rfirst, long nbytes, hipStream_t x);
-int uv_comm_kv_wait(univst_comm* c, hipStream_t s);
-int uv_comm_fork(univst_comm* c, hipStream_t s, hipStream_t* x);
-int uv_comm_join(univst_comm* c, hipStream_t s);
-int uv_comm_launch_raise(unsigned* flag, unsigned epoch, hipStream_t s);
-int uv_comm_launch_wait(const unsigned* flag, unsigned epoch, int* status, hipStream_t s);
-int uv_comm_barrier(univst_comm* c, hipStream_t s);
-char* uv_comm_ws(univst_comm* c);
-long uv_comm_ws_bytes(const univst_comm* c);
-int uv_comm_rank(const univst_comm* c);
-bool uv_comm_emulated(const univst_comm* c);
-int uv_comm_world(const univst_comm* c);
-
-struct WTensor {
-    half_t* ptr = nullptr;
-    std::vector<long> shape;
-};
-
-struct Act {   // NHWC activation: [imgs, H, W, C] fp16
-    half_t* p = nullptr;
-    int imgs = 0, H = 0, W = 0, C = 0;
-    const float* gst = nullptr;      // GroupNorm (sum, sumsq) per 16-row fragment and 10-channel sub-group, left by the producing conv / linear's epilogue ([C/10][rows/16][2]) or null
-    long rows() const { return (long)imgs * H * W; }
-};
-
-struct Arena {   // first-fit allocator over one device slab; stream-ordered reuse
-    struct Block {
-        size_t off, size;
-        bool free;
-    };
-    char* base = nullptr;
-    size_t size = 0, high_water = 0;
-    std::vector<Block> blocks;
-    void* alloc(size_t bytes);
-    void release(void* p);
-    void reset();
-};
-
-struct UNet {
+struct UNet : WeightStore {
     univst_unet_cfg cfg;
-    std::unordered_map<std::string, WTensor> weights, derived;
     std::unordered_map<long, int*> idx_tables;
     std::unordered_map<std::string, long> temb_off;    // resnet prefix -> column offset in the fused time_emb_proj (finalize)
     long temb_total = 0;
@@ -75,7 +23,6 @@ struct UNet {
     // initialisation (found on the device at finalize).  Empty for 2-D-initialised weights: the graph then skips them exactly.
     std::unordered_map<std::string, int> temporal_conv_active;     // conv prefix ("...resnets.0.conv1", "conv_in", ...)
     std::unordered_map<std::string, int> temporal_attn_active;     // transformer block prefix ("...transformer_blocks.0")
-    std::string missing;
     // multi-GPU frame sharding hooks
     int rank = 0, world = 1;
     univst_allreduce_fn allreduce = nullptr;
@@ -102,9 +49,5 @@ struct UNet {
     int finalize(hipStream_t s);
     int reserve(int B, int F, int H, int W);
     int forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int W, int text_len,
-                const univst_pnp_t* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s);
-    const WTensor* find(const std::string& k) const;
-    half_t* W(const std::string& k);
-    int derive_alloc(const std::string& k, std::vector<long> shape, half_t** out);
-    int missing_error();
+                const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s);
 };

@@ -17,38 +17,12 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "comm.h"
 #include "kernels.h"
 #include "unet.h"
 
 namespace {
 
-__global__ void convert_f32_f16_kernel(const float* __restrict__ in, half_t* __restrict__ out, long n) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (half_t)in[i];
-}
-// [Co,Ci,kh,kw] -> [Co,kh*kw,CiP] (zero padded channels)
-__global__ void permute_conv_weight_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci, int taps,
-                                           int CiP) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = (long)Co * taps * CiP;
-    if (i >= total) return;
-    int c = (int)(i % CiP);
-    int t = (int)((i / CiP) % taps);
-    int o = (int)(i / ((long)CiP * taps));
-    out[i] = c < Ci ? in[((long)o * Ci + c) * taps + t] : (half_t)0.f;
-}
-// [Co,Ci,3,3] -> tap-inner [Co][Ci/64][9][64]
-__global__ void permute_conv_weight_ti_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = (long)Co * Ci * 9;
-    if (i >= total) return;
-    int j = (int)(i % 64);
-    int t = (int)((i / 64) % 9);
-    int q = (int)((i / (64 * 9)) % (Ci / 64));
-    int o = (int)(i / ((long)Ci * 9));
-    out[i] = in[((long)o * Ci + q * 64 + j) * 9 + t];
-}
 // [Co,Ci,3,3] -> [Co][Ci/32][9][32] (conv_patch_kernel: a k tile is two consecutive (32-channel slab, tap) units)
 __global__ void permute_conv_weight_t32_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -68,11 +42,6 @@ __global__ void geglu_interleave_kernel(const half_t* __restrict__ in, half_t* _
     int q = r / 32, j = r % 32;
     int src = j < 16 ? 16 * q + j : rows / 2 + 16 * q + (j - 16);
     out[i] = in[(long)src * cols + c];
-}
-// out[i] = fp16(in[i] * f): to_q weights with log2(e)/sqrt(head_dim) folded in (attention.hip, attn_pp40_kernel)
-__global__ void scale_f16_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, long n, float f) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (half_t)((float)in[i] * f);
 }
 
 // LayerNorm folded into the following linear (GemmParams::ln_stats): W'[n][k] = fp16(gamma[k] * W[n][k]), wsum[n] = sum_k W'[n][k]
@@ -100,13 +69,6 @@ __global__ __launch_bounds__(64) void ln_fold_weight_kernel(const half_t* __rest
     }
 }
 
-__global__ void count_not_dirac_kernel(const half_t* __restrict__ w, int Co, int Ci, int k, unsigned* cnt) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Co * Ci * k) return;
-    int t = (int)(i % k), ci = (int)((i / k) % Ci), co = (int)(i / ((long)k * Ci));
-    float expect = (co == ci && t == k / 2) ? 1.f : 0.f;
-    if ((float)w[i] != expect) atomicAdd(cnt, 1u);
-}
 __global__ void count_nonzero_kernel(const half_t* __restrict__ w, long n, unsigned* cnt) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && (float)w[i] != 0.f) atomicAdd(cnt, 1u);
@@ -206,55 +168,10 @@ __global__ __launch_bounds__(256) void temporal_attn_kernel(const half_t* __rest
     }
 }
 
-inline unsigned nb(long n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace
-
-// ------------------------------------------------------------------------------------------ arena
-void* Arena::alloc(size_t bytes) {
-    bytes = (bytes + 255) & ~size_t(255);
-    for (size_t i = 0; i < blocks.size(); ++i) {
-        if (blocks[i].free && blocks[i].size >= bytes) {
-            if (blocks[i].size > bytes) {
-                Block rest{blocks[i].off + bytes, blocks[i].size - bytes, true};
-                blocks[i].size = bytes;
-                blocks.insert(blocks.begin() + i + 1, rest);
-            }
-            blocks[i].free = false;
-            size_t used = blocks[i].off + bytes;
-            if (used > high_water) high_water = used;
-            return base + blocks[i].off;
-        }
-    }
-    return nullptr;
-}
-void Arena::release(void* p) {
-    if (!p) return;
-    size_t off = (char*)p - base;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-        if (blocks[i].off == off && !blocks[i].free) {
-            blocks[i].free = true;
-            if (i + 1 < blocks.size() && blocks[i + 1].free) {
-                blocks[i].size += blocks[i + 1].size;
-                blocks.erase(blocks.begin() + i + 1);
-            }
-            if (i > 0 && blocks[i - 1].free) {
-                blocks[i - 1].size += blocks[i].size;
-                blocks.erase(blocks.begin() + i);
-            }
-            return;
-        }
-    }
-}
-void Arena::reset() {
-    blocks.clear();
-    blocks.push_back(Block{0, size, true});
-}
 
 // ------------------------------------------------------------------------------------------ handle
 UNet::~UNet() {
-    for (auto& kv : weights) (void)hipFree(kv.second.ptr);
-    for (auto& kv : derived) (void)hipFree(kv.second.ptr);
     for (auto& kv : idx_tables) (void)hipFree(kv.second);
     if (arena.base) (void)hipFree(arena.base);
     if (d_counter) (void)hipFree(d_counter);
@@ -275,69 +192,13 @@ int UNet::comm_streams() {
 }
 
 int UNet::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
-    UV_REQUIRE(key && dev_ptr && ndim >= 1 && ndim <= 5, "load_tensor: bad arguments");
-    long n = 1;
-    WTensor t;
-    for (int i = 0; i < ndim; ++i) {
-        n *= shape[i];
-        t.shape.push_back(shape[i]);
-    }
-    UV_REQUIRE(n > 0, "load_tensor(%s): empty tensor", key);
-    UV_HIP(hipMalloc(&t.ptr, n * sizeof(half_t)));
-    if (dtype == 0) {
-        UV_HIP(hipMemcpyAsync(t.ptr, dev_ptr, n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-    } else if (dtype == 1) {
-        hipLaunchKernelGGL(convert_f32_f16_kernel, dim3(nb(n)), dim3(256), 0, s, (const float*)dev_ptr, t.ptr, n);
-        UV_LAUNCH_CHECK();
-    } else {
-        (void)hipFree(t.ptr);
-        uv_set_error("load_tensor(%s): dtype %d unsupported", key, dtype);
-        return UV_ERR_ARG;
-    }
-    auto it = weights.find(key);
-    if (it != weights.end()) {
-        UV_HIP(hipStreamSynchronize(s));
-        (void)hipFree(it->second.ptr);
-        weights.erase(it);
-    }
-    weights[key] = t;
+    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
     finalized = false;
     return UV_OK;
 }
 
-const WTensor* UNet::find(const std::string& k) const {
-    auto it = weights.find(k);
-    if (it != weights.end()) return &it->second;
-    auto jt = derived.find(k);
-    return jt == derived.end() ? nullptr : &jt->second;
-}
-
-half_t* UNet::W(const std::string& k) {
-    const WTensor* t = find(k);
-    if (!t) {
-        if (missing.empty()) missing = k;
-        return nullptr;
-    }
-    return t->ptr;
-}
-
-int UNet::derive_alloc(const std::string& k, std::vector<long> shape, half_t** out) {
-    auto it = derived.find(k);
-    if (it != derived.end()) {
-        (void)hipFree(it->second.ptr);
-        derived.erase(it);
-    }
-    long n = 1;
-    for (long v : shape) n *= v;
-    WTensor t;
-    t.shape = shape;
-    UV_HIP(hipMalloc(&t.ptr, n * sizeof(half_t)));
-    derived[k] = t;
-    *out = t.ptr;
-    return UV_OK;
-}
-
 int UNet::finalize(hipStream_t s) {
+    clear_derived();
     std::vector<std::string> keys;
     for (auto& kv : weights) keys.push_back(kv.first);
     // one counter per temporal UNIT (a conv's temporal weight + bias, a block's attn_temporal.to_out weight): non-zero = trained
@@ -386,25 +247,13 @@ int UNet::finalize(hipStream_t s) {
             hipLaunchKernelGGL(count_nonzero_kernel, dim3(nb(n)), dim3(256), 0, s, t.ptr, n,
                                d_counter + tslot[k.substr(0, k.find(".attn_temporal.to_out.0.weight")) + "#a"]);
         } else if (t.shape.size() == 4 && k.find("_temporal") == std::string::npos) {
-            // conv weights -> [Co][taps][CiP]
+            // conv weights -> [Co][taps][CiP] (+ the tap-inner copy)
             int Co = (int)t.shape[0], Ci = (int)t.shape[1], taps = (int)(t.shape[2] * t.shape[3]);
             UV_REQUIRE(taps == 1 || taps == 9, "%s: only 1x1 / 3x3 convs are supported", k.c_str());
-            int CiP = (Ci + 7) / 8 * 8;
-            half_t* d;
-            int rc = derive_alloc(k + "#nhwc", {Co, taps, CiP}, &d);
-            if (rc) return rc;
-            long n = (long)Co * taps * CiP;
-            hipLaunchKernelGGL(permute_conv_weight_kernel, dim3(nb(n)), dim3(256), 0, s, t.ptr, d, Co, Ci, taps, CiP);
-            if (taps == 9 && Ci % 64 == 0) {      // tap-inner copy (GemmParams::korder = 1)
-                half_t* d2;
-                rc = derive_alloc(k + "#ti", {Co, Ci / 64, 9, 64}, &d2);
-                if (rc) return rc;
-                hipLaunchKernelGGL(permute_conv_weight_ti_kernel, dim3(nb((long)Co * Ci * 9)), dim3(256), 0, s, t.ptr, d2, Co, Ci);
-            }
+            UV_RUN(uv_derive_conv_layouts(*this, k, s));
             if (taps == 9 && Ci % 64 == 0 && Co % 320 == 0 && k.find("downsamplers") == std::string::npos) {      // LDS-patch copy (GemmParams::W32; stride-1 convs)
                 half_t* d3;
-                rc = derive_alloc(k + "#t32", {Co, Ci / 32, 9, 32}, &d3);
-                if (rc) return rc;
+                UV_RUN(derive(k + "#t32", {Co, Ci / 32, 9, 32}, &d3));
                 hipLaunchKernelGGL(permute_conv_weight_t32_kernel, dim3(nb((long)Co * Ci * 9)), dim3(256), 0, s, t.ptr, d3, Co, Ci);
             }
         } else if (ends(k, ".attn1.to_q.weight")) {
@@ -413,17 +262,15 @@ int UNet::finalize(hipStream_t s) {
             UV_REQUIRE(tk && tv, "%s: to_k / to_v missing", p.c_str());
             long C = t.shape[0], K = t.shape[1];
             half_t* d;
-            int rc = derive_alloc(p + "qkv#fused", {3 * C, K}, &d);
-            if (rc) return rc;
+            UV_RUN(derive(p + "qkv#fused", {3 * C, K}, &d));
             UV_HIP(hipMemcpyAsync(d, t.ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             UV_HIP(hipMemcpyAsync(d + C * K, tk->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             UV_HIP(hipMemcpyAsync(d + 2 * C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             const int hd = (int)C / cfg.attention_heads[level_of(k)];
             if (hd == 40 || hd == 64 || hd == 80 || hd == 160) {         // second copy whose Q rows carry log2(e)/sqrt(d) (AttnParams::q_prescaled): the software-
                 half_t* d2;                     // pipelined kernels (head_dim 40: SD-v1.5; 64: the SD-v2.1 layout) take the scale from the weights
-                rc = derive_alloc(p + "qkv#fused#qs", {3 * C, K}, &d2);
-                if (rc) return rc;
-                hipLaunchKernelGGL(scale_f16_kernel, dim3(nb(C * K)), dim3(256), 0, s, t.ptr, d2, C * K, 1.4426950408889634f / sqrtf((float)hd));
+                UV_RUN(derive(p + "qkv#fused#qs", {3 * C, K}, &d2));
+                UV_RUN(uv_launch_scale_f16(t.ptr, d2, C * K, 1.4426950408889634f / sqrtf((float)hd), s));
                 UV_HIP(hipMemcpyAsync(d2 + C * K, tk->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
                 UV_HIP(hipMemcpyAsync(d2 + 2 * C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             }
@@ -432,9 +279,8 @@ int UNet::finalize(hipStream_t s) {
             const int hd = (int)C / cfg.attention_heads[level_of(k)];
             if (hd == 40) {
                 half_t* d2;
-                int rc = derive_alloc(k + "#qs", {C, K}, &d2);
-                if (rc) return rc;
-                hipLaunchKernelGGL(scale_f16_kernel, dim3(nb(C * K)), dim3(256), 0, s, t.ptr, d2, C * K, 1.4426950408889634f / sqrtf((float)hd));
+                UV_RUN(derive(k + "#qs", {C, K}, &d2));
+                UV_RUN(uv_launch_scale_f16(t.ptr, d2, C * K, 1.4426950408889634f / sqrtf((float)hd), s));
             }
         } else if (ends(k, ".attn2.to_k.weight")) {
             std::string p = k.substr(0, k.size() - strlen("to_k.weight"));
@@ -442,16 +288,14 @@ int UNet::finalize(hipStream_t s) {
             UV_REQUIRE(tv, "%s: to_v missing", p.c_str());
             long C = t.shape[0], K = t.shape[1];
             half_t* d;
-            int rc = derive_alloc(p + "kv#fused", {2 * C, K}, &d);
-            if (rc) return rc;
+            UV_RUN(derive(p + "kv#fused", {2 * C, K}, &d));
             UV_HIP(hipMemcpyAsync(d, t.ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             UV_HIP(hipMemcpyAsync(d + C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
         } else if (ends(k, ".ff.net.0.proj.weight") || ends(k, ".ff.net.0.proj.bias")) {
             int rows = (int)t.shape[0], cols = t.shape.size() > 1 ? (int)t.shape[1] : 1;
             UV_REQUIRE(rows % 32 == 0, "%s: GEGLU width %d must be a multiple of 32", k.c_str(), rows);
             half_t* d;
-            int rc = derive_alloc(k + "#geglu", {rows, cols}, &d);
-            if (rc) return rc;
+            UV_RUN(derive(k + "#geglu", {rows, cols}, &d));
             hipLaunchKernelGGL(geglu_interleave_kernel, dim3(nb((long)rows * cols)), dim3(256), 0, s, t.ptr, d, rows, cols);
             // K = 320 (the 64x64 level): a second copy in the row order of the X-resident kernel (gemm.hip geglu_xres_kernel)
             int kdim = cols;
@@ -462,10 +306,8 @@ int UNet::finalize(hipStream_t s) {
             }
             if (uv_geglu_xres_ok(rows, kdim)) {
                 half_t* dx;
-                rc = derive_alloc(k + "#xres", {rows, cols}, &dx);
-                if (rc) return rc;
-                rc = uv_launch_geglu_xres_permute(t.ptr, dx, rows, cols, s);
-                if (rc) return rc;
+                UV_RUN(derive(k + "#xres", {rows, cols}, &dx));
+                UV_RUN(uv_launch_geglu_xres_permute(t.ptr, dx, rows, cols, s));
             }
         }
     }
@@ -486,9 +328,9 @@ int UNet::finalize(hipStream_t s) {
                        "%s: LayerNorm / linear pair incomplete", (b + j.norm).c_str());
             const long N = w->shape[0], K = w->shape[1];
             half_t *wo, *ws, *lb;
-            int rc = derive_alloc(j.w + "#ln", {N, K}, &wo);
-            if (!rc) rc = derive_alloc(j.w + "#ln.wsum", {2 * N}, &ws);      // fp32 [N]
-            if (!rc) rc = derive_alloc(j.w + "#ln.bias", {2 * N}, &lb);      // fp32 [N]
+            int rc = derive(j.w + "#ln", {N, K}, &wo);
+            if (!rc) rc = derive(j.w + "#ln.wsum", {2 * N}, &ws);      // fp32 [N]
+            if (!rc) rc = derive(j.w + "#ln.bias", {2 * N}, &lb);      // fp32 [N]
             if (rc) return rc;
             hipLaunchKernelGGL(ln_fold_weight_kernel, dim3((unsigned)N), dim3(64), 0, s, w->ptr, gm->ptr, bt->ptr, bi ? bi->ptr : nullptr, wo,
                                (float*)ws, (float*)lb, (int)K);
@@ -505,10 +347,8 @@ int UNet::finalize(hipStream_t s) {
             const WTensor* w = find(src);
             if (!w) continue;
             half_t* d;
-            int rc = derive_alloc(src + "#frag", {w->shape[0], w->shape[1]}, &d);
-            if (rc) return rc;
-            rc = uv_launch_frag_pack(w->ptr, d, (int)w->shape[0], (int)w->shape[1], s);
-            if (rc) return rc;
+            UV_RUN(derive(src + "#frag", {w->shape[0], w->shape[1]}, &d));
+            UV_RUN(uv_launch_frag_pack(w->ptr, d, (int)w->shape[0], (int)w->shape[1], s));
         }
     }
     {   // all resnets' time_emb_proj stacked into one [sum Cout, 4*C0] matrix: one projection launch per forward instead of 22
@@ -525,10 +365,8 @@ int UNet::finalize(hipStream_t s) {
         if (!tk.empty()) {
             const long K = weights[tk[0]].shape[1];
             half_t *wa, *ba;
-            int rc = derive_alloc("time_emb_proj#all.weight", {temb_total, K}, &wa);
-            if (rc) return rc;
-            rc = derive_alloc("time_emb_proj#all.bias", {temb_total}, &ba);
-            if (rc) return rc;
+            UV_RUN(derive("time_emb_proj#all.weight", {temb_total, K}, &wa));
+            UV_RUN(derive("time_emb_proj#all.bias", {temb_total}, &ba));
             for (const std::string& k : tk) {
                 const std::string pre = k.substr(0, k.size() - strlen(".time_emb_proj.weight"));
                 const WTensor& wt = weights[k];
@@ -553,8 +391,7 @@ int UNet::finalize(hipStream_t s) {
             const int C = (int)w->shape[0];
             if (C % 8 == 0) {
                 half_t* d;
-                int rc = derive_alloc(pre + ".conv_temporal.weight#t3x3", {C, 9, C}, &d);
-                if (rc) return rc;
+                UV_RUN(derive(pre + ".conv_temporal.weight#t3x3", {C, 9, C}, &d));
                 hipLaunchKernelGGL(embed_temporal_weight_kernel, dim3(nb((long)C * 9 * C)), dim3(256), 0, s, w->ptr, d, C);
             }
             temporal_conv_active[pre] = 1;
@@ -565,8 +402,7 @@ int UNet::finalize(hipStream_t s) {
                        find(pre + ".attn_temporal.to_out.0.bias"), "%s: attn_temporal / norm_temporal parameters incomplete", pre.c_str());
             const long C = tq->shape[0], K = tq->shape[1];
             half_t* d;
-            int rc = derive_alloc(pre + ".attn_temporal.qkv#fused", {3 * C, K}, &d);
-            if (rc) return rc;
+            UV_RUN(derive(pre + ".attn_temporal.qkv#fused", {3 * C, K}, &d));
             UV_HIP(hipMemcpyAsync(d, tq->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             UV_HIP(hipMemcpyAsync(d + C * K, tk->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
             UV_HIP(hipMemcpyAsync(d + 2 * C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
@@ -584,14 +420,7 @@ int UNet::reserve(int B, int F, int H, int Wd) {
     // activations (28 level-0-sized tensors at the high-water mark of the graph) + the small workspaces + split-K partials + the pool of the
     // producers' GroupNorm statistics (Fwd::gst_pool: rows0 / 16 fragments x 32 sub-group slots x 64 tensors x (sum, sumsq) fp32 = 1 KB per row)
     size_t need = (size_t)rows0 * cfg.block_out_channels[0] * 2 * 28 + (64u << 20) + UV_SPLITK_WS_BYTES + (gn_producer ? (size_t)rows0 * 1024 : 0);
-    if (arena.size < need) {
-        UV_HIP(hipDeviceSynchronize());
-        if (arena.base) UV_HIP(hipFree(arena.base));
-        arena.base = nullptr;
-        UV_HIP(hipMalloc((void**)&arena.base, need));
-        arena.size = need;
-    }
-    arena.reset();
+    UV_RUN(arena.ensure(need));
     // K/V source tables for this (B,F)
     long key = ((long)B << 20) | F | ((long)rank << 40) | ((long)world << 50);
     if (!idx_tables.count(key)) {
@@ -669,17 +498,11 @@ int UNet::reserve(int B, int F, int H, int Wd) {
 }
 
 // ------------------------------------------------------------------------------------------ forward
-#define RUN(x)                \
-    do {                      \
-        int _rc = (x);        \
-        if (_rc) return _rc;  \
-    } while (0)
-
 struct Fwd {
     UNet& u;
     hipStream_t s;
     int B, F, text_len;
-    const univst_pnp_t* pnp;
+    const univst_pnp* pnp;
     half_t* emb = nullptr;     // [B, 4*C0]
     const half_t* text = nullptr;
     const int *idx_stock = nullptr, *idx_pnp = nullptr, *idx_text = nullptr, *cnt_stock = nullptr, *cnt_pnp = nullptr;
@@ -708,7 +531,7 @@ struct Fwd {
 
     half_t* alloc(long elems) {
         half_t* p = (half_t*)u.arena.alloc((size_t)elems * sizeof(half_t));
-        if (!p) uv_set_error("activation arena exhausted (%zu bytes); call univst_unet_reserve with the right geometry", u.arena.size);
+        if (!p) uv_set_error("unet: activation arena exhausted (%zu bytes); call univst_unet_reserve with the right geometry", u.arena.size);
         return p;
     }
     void free(void* p) { u.arena.release(p); }
@@ -725,8 +548,10 @@ struct Fwd {
             gc.allreduce = u.allreduce;
             gc.user = u.comm_user;
         }
+        half_t *gm = W(p + ".weight"), *bt = W(p + ".bias");
+        if (!gm || !bt) return u.missing_error("unet");      // (the kernels read both unconditionally)
         return uv_launch_groupnorm(a.p, b ? b->p : nullptr, a.C, b ? b->C : 0, a.rows(), rows_per_stat, u.cfg.norm_num_groups,
-                                   eps, W(p + ".weight"), W(p + ".bias"), silu, out, gn_ws, s, sharded ? &gc : nullptr,
+                                   eps, gm, bt, silu, out, gn_ws, s, sharded ? &gc : nullptr,
                                    rows_per_stat % 16 == 0 ? a.gst : nullptr, b ? b->gst : nullptr, fold);
     }
     // want_gst: let the epilogue leave the GroupNorm statistics of the output (Act::gst) for a following GroupNorm
@@ -765,7 +590,7 @@ struct Fwd {
         if (!out->p) return UV_ERR_STATE;
         g.Y = out->p;
         g.ldy = Cout;
-        if (!g.W || !g.bias) return u.missing_error();
+        if (!g.W || !g.bias) return u.missing_error("unet");
         g.partial = sk_ws;
         g.partial_bytes = UV_SPLITK_WS_BYTES;
         out->gst = nullptr;
@@ -776,7 +601,7 @@ struct Fwd {
                 g.gn_gw = 10;
                 g.gn_emitted = &emitted;
             }
-            RUN(uv_launch_gemm(g, 1, s));
+            UV_RUN(uv_launch_gemm(g, 1, s));
             if (g.gn_out) {
                 if (emitted) out->gst = g.gn_out;
                 else gst_give_back(out->rows(), Cout);
@@ -791,9 +616,9 @@ struct Fwd {
         g.Y = mid;
         g.rowbias = nullptr;
         g.R = nullptr;
-        RUN(uv_launch_gemm(g, 1, s));
+        UV_RUN(uv_launch_gemm(g, 1, s));
         half_t *tw = W(p + ".conv_temporal.weight"), *tb = W(p + ".conv_temporal.bias");
-        if (!tw || !tb) return u.missing_error();
+        if (!tw || !tb) return u.missing_error("unet");
         const long HWo = (long)g.Ho * g.Wo;
         if (Cout % 8 != 0) {
             UV_REQUIRE(!rowbias && !R, "%s: temporal conv on %d channels cannot carry a fused epilogue", p.c_str(), Cout);
@@ -820,10 +645,10 @@ struct Fwd {
             t.ldr = Cout;
             t.Y = out->p;
             t.ldy = Cout;
-            if (!t.W) return u.missing_error();
+            if (!t.W) return u.missing_error("unet");
             t.partial = sk_ws;
             t.partial_bytes = UV_SPLITK_WS_BYTES;
-            RUN(uv_launch_gemm(t, 1, s));
+            UV_RUN(uv_launch_gemm(t, 1, s));
         }
         free(mid);
         return UV_OK;
@@ -854,7 +679,7 @@ struct Fwd {
             g.ln_eps = 1e-5f;
             g.ln_wsum = (const float*)W(wkey + ".wsum");
             g.ln_bias = (const float*)W(wkey + ".bias");
-            if (!g.ln_wsum || !g.ln_bias) return u.missing_error();
+            if (!g.ln_wsum || !g.ln_bias) return u.missing_error("unet");
         }
         g.X = X;
         g.ldx = ldx;
@@ -869,10 +694,10 @@ struct Fwd {
         g.ldr = ldr;
         g.bias2 = bias2;
         g.geglu = geglu;
-        if (!g.W || (!bkey.empty() && !ln_in && !wsets && !g.bias)) return u.missing_error();
+        if (!g.W || (!bkey.empty() && !ln_in && !wsets && !g.bias)) return u.missing_error("unet");
         g.partial = sk_ws;
         g.partial_bytes = UV_SPLITK_WS_BYTES;
-        RUN(uv_launch_gemm(g, 0, s));
+        UV_RUN(uv_launch_gemm(g, 0, s));
         if (g.gn_out) {
             if (emitted) *gst_out = g.gn_out;
             else gst_give_back(M, N);
@@ -906,21 +731,21 @@ struct Fwd {
         kvs.o_first = kvs.o_send + slot;
         kvs.o_prev = kvs.o_first + slot * (1 + 2 * par);
         kvs.o_rfirst = kvs.o_prev + slot;
-        if (u.rank < u.world - 1) RUN(uv_launch_rows_pack(h, C, 0, C, N, B, F, F - 1, (half_t*)(u.comm_ws + kvs.o_send), s));
-        if (u.rank == 0) RUN(uv_launch_rows_pack(h, C, 0, C, N, B, F, 0, (half_t*)(u.comm_ws + kvs.o_first), s));
+        if (u.rank < u.world - 1) UV_RUN(uv_launch_rows_pack(h, C, 0, C, N, B, F, F - 1, (half_t*)(u.comm_ws + kvs.o_send), s));
+        if (u.rank == 0) UV_RUN(uv_launch_rows_pack(h, C, 0, C, N, B, F, 0, (half_t*)(u.comm_ws + kvs.o_first), s));
         kvs.emu = !u.native_comm && u.emu_wire_gbps > 0;
         if (!u.native_comm && !kvs.emu) return UV_OK;
         const bool sends = u.rank < u.world - 1 || kvs.emu;           // (the last rank posts nothing)
         hipStream_t x = s;
         if (u.kv_overlap && sends) {
-            RUN(u.comm_streams());
+            UV_RUN(u.comm_streams());
             x = u.xstream;
             UV_HIP(hipEventRecord(u.ev_fork, s));
             UV_HIP(hipStreamWaitEvent(x, u.ev_fork, 0));
             u.x_dirty = true;
         }
         if (u.native_comm) {
-            RUN(uv_comm_kv_post(u.native_comm, kvs.o_send, kvs.o_first, kvs.o_prev, kvs.o_rfirst, kvs.nbytes, x));
+            UV_RUN(uv_comm_kv_post(u.native_comm, kvs.o_send, kvs.o_first, kvs.o_prev, kvs.o_rfirst, kvs.nbytes, x));
         } else {
             // the slowest transfer of this exchange on a node this box does not have: one pack per link (the first-frame pack reaches every rank over
             // its own link from rank 0, the halo pack over the link from rank - 1) except on rank 1, whose one link from rank 0 carries both.  The delay
@@ -932,8 +757,8 @@ struct Fwd {
                 UV_HIP(hipMemsetAsync(u.emu_flag, 0, 64, s));
                 UV_HIP(hipStreamSynchronize(s));
             }
-            RUN(uv_launch_delay_us(us, x));
-            RUN(uv_comm_launch_raise(u.emu_flag, ++u.emu_epoch, x));
+            UV_RUN(uv_launch_delay_us(us, x));
+            UV_RUN(uv_comm_launch_raise(u.emu_flag, ++u.emu_epoch, x));
         }
         return UV_OK;
     }
@@ -944,7 +769,7 @@ struct Fwd {
             uv_set_error("kv_exchange callback failed (%d)", rc);
             return UV_ERR_STATE;
         }
-        if (kvs.emu && u.rank > 0) RUN(uv_comm_launch_wait(u.emu_flag, u.emu_epoch, (int*)(u.emu_flag + 1), s));
+        if (kvs.emu && u.rank > 0) UV_RUN(uv_comm_launch_wait(u.emu_flag, u.emu_epoch, (int*)(u.emu_flag + 1), s));
         return UV_OK;
     }
 
@@ -954,26 +779,26 @@ struct Fwd {
         const int rps = F * x.H * x.W;
         half_t* n1 = alloc(x.rows() * Cin);
         if (!n1) return UV_ERR_STATE;
-        RUN(groupnorm(x, skip, rps, u.cfg.norm_eps, p + ".norm1", 1, n1, true));
+        UV_RUN(groupnorm(x, skip, rps, u.cfg.norm_eps, p + ".norm1", 1, n1, true));
         auto to = u.temb_off.find(p);
         UV_REQUIRE(to != u.temb_off.end() && temb_all, "%s: time_emb_proj missing", p.c_str());
         Act n1a{n1, x.imgs, x.H, x.W, Cin}, h;
-        RUN(conv(n1a, nullptr, p + ".conv1", Cout, 9, 1, 0, temb_all + to->second, nullptr, &h, u.temb_total, true));
+        UV_RUN(conv(n1a, nullptr, p + ".conv1", Cout, 9, 1, 0, temb_all + to->second, nullptr, &h, u.temb_total, true));
         free(n1);
         half_t* n2 = alloc(h.rows() * Cout);
         if (!n2) return UV_ERR_STATE;
-        RUN(groupnorm(h, nullptr, rps, u.cfg.norm_eps, p + ".norm2", 1, n2, true));
+        UV_RUN(groupnorm(h, nullptr, rps, u.cfg.norm_eps, p + ".norm2", 1, n2, true));
         free(h.p);
         const half_t* res = x.p;
         Act sc{};
         if (u.find(p + ".conv_shortcut.weight")) {
-            RUN(conv(x, skip, p + ".conv_shortcut", Cout, 1, 1, 0, nullptr, nullptr, &sc));
+            UV_RUN(conv(x, skip, p + ".conv_shortcut", Cout, 1, 1, 0, nullptr, nullptr, &sc));
             res = sc.p;
         } else {
             UV_REQUIRE(!skip && x.C == Cout, "%s: no conv_shortcut but channel mismatch", p.c_str());
         }
         Act n2a{n2, x.imgs, x.H, x.W, Cout};
-        RUN(conv(n2a, nullptr, p + ".conv2", Cout, 9, 1, 0, nullptr, res, out, 0, true));
+        UV_RUN(conv(n2a, nullptr, p + ".conv2", Cout, 9, 1, 0, nullptr, res, out, 0, true));
         free(n2);
         if (sc.p) free(sc.p);
         return UV_OK;
@@ -1000,10 +825,10 @@ struct Fwd {
             if (!wsets || !b32) return UV_ERR_STATE;
             UvGnFold gf;
             gf.W = W(wpi); gf.bias = W(p + ".proj_in.bias"); gf.N = C; gf.W_out = wsets; gf.bias32 = b32;
-            if (!gf.W || !gf.bias) return u.missing_error();
-            RUN(groupnorm(x, nullptr, N, 1e-6f, p + ".norm", 0, nullptr, false, &gf));
+            if (!gf.W || !gf.bias) return u.missing_error("unet");
+            UV_RUN(groupnorm(x, nullptr, N, 1e-6f, p + ".norm", 0, nullptr, false, &gf));
         } else {
-            RUN(groupnorm(x, nullptr, N, 1e-6f, p + ".norm", 0, t0));
+            UV_RUN(groupnorm(x, nullptr, N, 1e-6f, p + ".norm", 0, t0));
         }
         half_t* h = alloc(rows * C);
         if (!h) return UV_ERR_STATE;
@@ -1021,7 +846,7 @@ struct Fwd {
         const bool fold3 = fold && u.ln_fold > 1 && (xres3 || uv_linear_fold_consumer_ok(rows, 8 * C, C, true));
         float* lnst = fold ? (float*)alloc(rows * (C / 160) * 4) : nullptr;      // [rows][C/160][2] fp32
         if (fold && !lnst) return UV_ERR_STATE;
-        RUN(linear(gnf ? x.p : t0, C, rows, C, wpi, p + ".proj_in.bias", C, h, C, nullptr, 0, nullptr, 0, lnst, nullptr, nullptr, wsets, b32, N));
+        UV_RUN(linear(gnf ? x.p : t0, C, rows, C, wpi, p + ".proj_in.bias", C, h, C, nullptr, 0, nullptr, 0, lnst, nullptr, nullptr, wsets, b32, N));
         if (gnf) {
             free(wsets);
             free(b32);
@@ -1029,24 +854,24 @@ struct Fwd {
         // ---- attn1
         half_t *gm, *bt;
         gm = W(b + ".norm1.weight"); bt = W(b + ".norm1.bias");
-        if (!gm || !bt) return u.missing_error();
-        if (!fold) RUN(uv_launch_layernorm(h, C, t0, C, gm, bt, rows, C, 1e-5f, s));
+        if (!gm || !bt) return u.missing_error("unet");
+        if (!fold) UV_RUN(uv_launch_layernorm(h, C, t0, C, gm, bt, rows, C, 1e-5f, s));
         const bool shard = u.world > 1, halo = shard && u.rank > 0;
-        if (shard) RUN(kv_post(h, C, N));                  // the boundary frames' hidden rows leave now, on the forked stream
+        if (shard) UV_RUN(kv_post(h, C, N));                  // the boundary frames' hidden rows leave now, on the forked stream
         const long extra_rows = shard ? (long)2 * B * N : 0;     // the halo frames' q|k|v rows behind the local ones: [prev: B x N | first: B x N]
         half_t* qkv = alloc((rows + extra_rows) * 3 * C);
         if (!qkv) return UV_ERR_STATE;
         const bool qs = u.find(b + ".attn1.qkv#fused#qs") != nullptr;      // head_dim 40: scale folded into to_q (finalize)
         const std::string wqkv = b + (qs ? ".attn1.qkv#fused#qs" : ".attn1.qkv#fused");
-        if (fold) RUN(linear(h, C, rows, C, wqkv + "#ln", "", 3 * C, qkv, 3 * C, nullptr, 0, nullptr, 0, nullptr, lnst));
-        else RUN(linear(t0, C, rows, C, wqkv, "", 3 * C, qkv, 3 * C));
+        if (fold) UV_RUN(linear(h, C, rows, C, wqkv + "#ln", "", 3 * C, qkv, 3 * C, nullptr, 0, nullptr, 0, nullptr, lnst));
+        else UV_RUN(linear(t0, C, rows, C, wqkv, "", 3 * C, qkv, 3 * C));
         const bool registered = pnp_layer && pnp && pnp->registered;
         const bool shift = registered && pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f;
         float beta = 0.f;
         if (shift) {
             UV_REQUIRE(B == 3, "PnP attention shift needs the three-branch batch (B=3), got B=%d", B);
             beta = (0.9f - 0.1f) / (pnp->eta1 * 50.f - pnp->eta2 * 50.f) * ((float)pnp->idx - pnp->eta2 * 50.f) + 0.1f;
-            RUN(uv_launch_adain_shift(qkv, 3 * C, F, N, C, ad_ws, ad_ws + (long)F * 2 * C, pnp->alpha, beta, pnp->gamma, s));
+            UV_RUN(uv_launch_adain_shift(qkv, 3 * C, F, N, C, ad_ws, ad_ws + (long)F * 2 * C, pnp->alpha, beta, pnp->gamma, s));
         }
         AttnParams ap;
         ap.q = qkv; ap.k = qkv + C; ap.v = qkv + 2 * C;
@@ -1065,8 +890,8 @@ struct Fwd {
             if (!state) return UV_ERR_STATE;
             ap.state_out = state;
         }
-        RUN(uv_launch_attention(ap, s));
-        if (shard) RUN(kv_join());
+        UV_RUN(uv_launch_attention(ap, s));
+        if (shard) UV_RUN(kv_join());
         if (halo) {
             // the two halo frames: LayerNorm (norm1) of the received hidden rows -> to_k | to_v (all of q|k|v inside the window: the shift kernel works on
             // the fused rows) -> the AdaIN shift of each frame -> phase 2 over them.  The sender would have computed the same K | V from the same fp16 rows
@@ -1074,17 +899,17 @@ struct Fwd {
             const long hrows = 2L * B * N;
             half_t* tn = alloc(hrows * C);
             if (!tn) return UV_ERR_STATE;
-            RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_prev), C, tn, C, gm, bt, (long)B * N, C, 1e-5f, s));
-            RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_rfirst), C, tn + (long)B * N * C, C, gm, bt, (long)B * N, C, 1e-5f, s));
+            UV_RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_prev), C, tn, C, gm, bt, (long)B * N, C, 1e-5f, s));
+            UV_RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_rfirst), C, tn + (long)B * N * C, C, gm, bt, (long)B * N, C, 1e-5f, s));
             half_t* qh = qkv + rows * 3 * C;
             half_t* wfull = W(wqkv);
-            if (!wfull) return u.missing_error();
+            if (!wfull) return u.missing_error("unet");
             if (shift) {
-                RUN(linear(tn, C, hrows, C, wqkv, "", 3 * C, qh, 3 * C));
+                UV_RUN(linear(tn, C, hrows, C, wqkv, "", 3 * C, qh, 3 * C));
                 for (int sl = 0; sl < 2; ++sl)            // rows [slot][3 branches][N] = the shift kernel's [3][F = 1][N]
-                    RUN(uv_launch_adain_shift(qh + (long)sl * B * N * 3 * C, 3 * C, 1, N, C, ad_ws, ad_ws + 2L * C, pnp->alpha, beta, pnp->gamma, s));
+                    UV_RUN(uv_launch_adain_shift(qh + (long)sl * B * N * 3 * C, 3 * C, 1, N, C, ad_ws, ad_ws + 2L * C, pnp->alpha, beta, pnp->gamma, s));
             } else {
-                RUN(linear(tn, C, hrows, C, wqkv, "", 2 * C, qh + C, 3 * C, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, wfull + (long)C * C));
+                UV_RUN(linear(tn, C, hrows, C, wqkv, "", 2 * C, qh + C, 3 * C, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, wfull + (long)C * C));
             }
             free(tn);
             ap.src_idx = registered ? idx2_pnp : idx2_stock;
@@ -1092,7 +917,7 @@ struct Fwd {
             ap.src_logw = nullptr;
             ap.state_out = nullptr;
             ap.state_in = state;
-            RUN(uv_launch_attention(ap, s));
+            UV_RUN(uv_launch_attention(ap, s));
             ap.state_in = nullptr;
             free(state);
         }
@@ -1126,11 +951,11 @@ struct Fwd {
         if (!h2 || !kv) return UV_ERR_STATE;
         half_t *gm2 = W(b + ".norm2.weight"), *bt2 = W(b + ".norm2.bias"), *gm3 = W(b + ".norm3.weight"), *bt3 = W(b + ".norm3.bias");
         half_t* tb = W(b + ".attn_temporal.to_out.0.bias");
-        if (!gm2 || !bt2 || !gm3 || !bt3 || !tb) return u.missing_error();
+        if (!gm2 || !bt2 || !gm3 || !bt3 || !tb) return u.missing_error("unet");
         const bool qs2 = u.find(b + ".attn2.to_q.weight#qs") != nullptr;
         const std::string wq2 = b + (qs2 ? ".attn2.to_q.weight#qs" : ".attn2.to_q.weight");
         const bool t_attn = u.temporal_attn_active.count(b) != 0;
-        RUN(linear(text, u.cfg.cross_attention_dim, (long)B * text_len, u.cfg.cross_attention_dim, b + ".attn2.kv#fused", "",
+        UV_RUN(linear(text, u.cfg.cross_attention_dim, (long)B * text_len, u.cfg.cross_attention_dim, b + ".attn2.kv#fused", "",
                    2 * C, kv, 2 * C));
         // round 5, second step: the self-attention's out projection rides in FRONT of the fused text cross-attention (fused.hip, PRE): h2 = to_out(attn1) + h
         // is that kernel's input and residual and nothing else reads it, so it stays in the block's LDS
@@ -1142,7 +967,7 @@ struct Fwd {
             if (a2pre) {
                 half_t* kvf = alloc(uv_attn2_kvf_halfs(B, heads, d));
                 if (!kvf || !(h3 = alloc(rows * C))) return UV_ERR_STATE;
-                RUN(uv_launch_kv_frag_pack(kv, kvf, B, text_len, C, heads, s));
+                UV_RUN(uv_launch_kv_frag_pack(kv, kvf, B, text_len, C, heads, s));
                 Attn2Params a2;
                 a2.X = t0; a2.ldx = C; a2.M = (int)rows;
                 a2.Wp_f = W(wpf0); a2.bias_p = W(b + ".attn1.to_out.0.bias"); a2.Rp = h; a2.ldrp = C;
@@ -1154,14 +979,14 @@ struct Fwd {
                 a2.Wo_f = W(wof0); a2.bias_o = W(b + ".attn2.to_out.0.bias");
                 a2.Y = h3; a2.ldy = C;
                 a2.stats_out = fold3 ? lb : nullptr;
-                if (!a2.bias_p || !a2.bias_o || !a2.ln_wsum || !a2.ln_bias) return u.missing_error();
-                RUN(uv_launch_attn2_fused(a2, C, s));
+                if (!a2.bias_p || !a2.bias_o || !a2.ln_wsum || !a2.ln_bias) return u.missing_error("unet");
+                UV_RUN(uv_launch_attn2_fused(a2, C, s));
                 free(kvf);
                 free(kv);
                 free(h);
                 free(h2);
             } else {
-            RUN(linear(t0 + o, C, brows, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", C, h2 + o, C, h + o, C, nullptr, 0, lb));
+            UV_RUN(linear(t0 + o, C, brows, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", C, h2 + o, C, h + o, C, nullptr, 0, lb));
             if (nbands == 1) free(h);
             // ---- attn2 (text)
             // ONE launch where the shape allows (round 5, fused.hip): q projection (LayerNorm folded), the 77-key attention of the wave's two
@@ -1170,14 +995,14 @@ struct Fwd {
             if (nbands == 1 && u.attn2_fused && uv_attn2_fused_ok(C, heads, F * N, text_len) && u.find(wqf) && u.find(wof)) {
                 half_t* kvf = alloc(uv_attn2_kvf_halfs(B, heads, d));
                 if (!kvf || !(h3 = alloc(rows * C))) return UV_ERR_STATE;
-                RUN(uv_launch_kv_frag_pack(kv, kvf, B, text_len, C, heads, s));
-                if (!fold) RUN(uv_launch_layernorm(h2, C, t0, C, gm2, bt2, rows, C, 1e-5f, s));
+                UV_RUN(uv_launch_kv_frag_pack(kv, kvf, B, text_len, C, heads, s));
+                if (!fold) UV_RUN(uv_launch_layernorm(h2, C, t0, C, gm2, bt2, rows, C, 1e-5f, s));
                 Attn2Params a2;
                 a2.X = fold ? h2 : t0; a2.ldx = C; a2.M = (int)rows;
                 if (fold) {
                     a2.ln_stats = lb; a2.ln_slots = C / 160; a2.ln_eps = 1e-5f;
                     a2.ln_wsum = (const float*)W(wq2 + "#ln.wsum"); a2.ln_bias = (const float*)W(wq2 + "#ln.bias");
-                    if (!a2.ln_wsum || !a2.ln_bias) return u.missing_error();
+                    if (!a2.ln_wsum || !a2.ln_bias) return u.missing_error("unet");
                 }
                 a2.Wq_f = W(wqf); a2.kvf = kvf;
                 a2.rows_per_branch = F * N; a2.heads = heads; a2.Nkv = text_len;
@@ -1185,26 +1010,26 @@ struct Fwd {
                 a2.Wo_f = W(wof); a2.bias_o = W(b + ".attn2.to_out.0.bias");
                 a2.R = h2; a2.ldr = C; a2.Y = h3; a2.ldy = C;
                 a2.stats_out = fold3 ? lb : nullptr;
-                if (!a2.bias_o) return u.missing_error();
-                RUN(uv_launch_attn2_fused(a2, C, s));
+                if (!a2.bias_o) return u.missing_error("unet");
+                UV_RUN(uv_launch_attn2_fused(a2, C, s));
                 free(kvf);
                 free(kv);
                 free(h2);
             } else {
             if (!q2 && !(q2 = alloc(brows * C))) return UV_ERR_STATE;
-            if (!fold) RUN(uv_launch_layernorm(h2 + o, C, t0 + o, C, gm2, bt2, brows, C, 1e-5f, s));
-            if (fold) RUN(linear(h2 + o, C, brows, C, wq2 + "#ln", "", C, q2, C, nullptr, 0, nullptr, 0, nullptr, lb));
-            else RUN(linear(t0 + o, C, brows, C, wq2, "", C, q2, C));
+            if (!fold) UV_RUN(uv_launch_layernorm(h2 + o, C, t0 + o, C, gm2, bt2, brows, C, 1e-5f, s));
+            if (fold) UV_RUN(linear(h2 + o, C, brows, C, wq2 + "#ln", "", C, q2, C, nullptr, 0, nullptr, 0, nullptr, lb));
+            else UV_RUN(linear(t0 + o, C, brows, C, wq2, "", C, q2, C));
             ap.q = q2; ap.ldq = C;
             ap.k = kv; ap.v = kv + C; ap.ldkv = 2 * C;
             ap.o = t0 + o; ap.ldo = C;
             ap.src_idx = idx_text + bd * band_imgs; ap.src_cnt = nullptr; ap.src_logw = nullptr; ap.nsrc = 1; ap.Nkv = text_len;
             ap.BF = band_imgs;
             ap.q_prescaled = qs2;
-            RUN(uv_launch_attention(ap, s));
+            UV_RUN(uv_launch_attention(ap, s));
             if (nbands == 1) { free(q2); free(kv); }
             if (!h3 && !(h3 = alloc(rows * C))) return UV_ERR_STATE;
-            RUN(linear(t0 + o, C, brows, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", C, h3 + o, C, h2 + o, C, nullptr, 0, fold3 ? lb : nullptr));
+            UV_RUN(linear(t0 + o, C, brows, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", C, h3 + o, C, h2 + o, C, nullptr, 0, fold3 ? lb : nullptr));
             if (nbands == 1) free(h2);
             }
             }
@@ -1215,14 +1040,14 @@ struct Fwd {
             const std::string wff = b + (xres ? ".ff.net.0.proj.weight#xres" : ".ff.net.0.proj.weight#geglu");
             const std::string bff = b + (xres ? ".ff.net.0.proj.bias#xres" : ".ff.net.0.proj.bias#geglu");
             if (!fold3) {
-                RUN(uv_launch_layernorm(h3 + o, C, t0 + o, C, gm3, bt3, brows, C, 1e-5f, s));
-                RUN(linear(t0 + o, C, brows, C, wff, bff, 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1));
+                UV_RUN(uv_launch_layernorm(h3 + o, C, t0 + o, C, gm3, bt3, brows, C, 1e-5f, s));
+                UV_RUN(linear(t0 + o, C, brows, C, wff, bff, 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1));
             } else {
-                RUN(linear(h3 + o, C, brows, C, wff + "#ln", "", 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1, nullptr, lb));
+                UV_RUN(linear(h3 + o, C, brows, C, wff + "#ln", "", 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1, nullptr, lb));
             }
             if (nbands == 1 && lnst) free(lnst);
             if (!h4 && !(h4 = alloc(rows * C))) return UV_ERR_STATE;
-            RUN(linear(mid, 4 * C, brows, 4 * C, b + ".ff.net.2.weight", b + ".ff.net.2.bias", C, h4 + o, C, h3 + o, C, t_attn ? nullptr : tb));
+            UV_RUN(linear(mid, 4 * C, brows, 4 * C, b + ".ff.net.2.weight", b + ".ff.net.2.bias", C, h4 + o, C, h3 + o, C, t_attn ? nullptr : tb));
         }
         ap.BF = x.imgs;                // (the band loop narrowed it)
         if (nbands > 1) {
@@ -1237,11 +1062,11 @@ struct Fwd {
         if (t_attn) {      // TRAINED temporal attention (attention.py:336-346): LayerNorm, q|k|v, softmax over the F frames of every pixel, to_out + residual
             UV_REQUIRE(F <= 32, "temporal attention: clips of %d frames (kernel holds <= 32 scores per query)", F);
             gm = W(b + ".norm_temporal.weight"); bt = W(b + ".norm_temporal.bias");
-            if (!gm || !bt) return u.missing_error();
-            RUN(uv_launch_layernorm(h4, C, t0, C, gm, bt, rows, C, 1e-5f, s));
+            if (!gm || !bt) return u.missing_error("unet");
+            UV_RUN(uv_launch_layernorm(h4, C, t0, C, gm, bt, rows, C, 1e-5f, s));
             half_t* qkvt = alloc(rows * 3 * C);
             if (!qkvt) return UV_ERR_STATE;
-            RUN(linear(t0, C, rows, C, b + ".attn_temporal.qkv#fused", "", 3 * C, qkvt, 3 * C));
+            UV_RUN(linear(t0, C, rows, C, b + ".attn_temporal.qkv#fused", "", 3 * C, qkvt, 3 * C));
             const long nthr = (long)B * N * heads * F;
             const float sc = 1.f / sqrtf((float)d);
             switch (d) {
@@ -1258,7 +1083,7 @@ struct Fwd {
             free(qkvt);
             half_t* h5 = alloc(rows * C);
             if (!h5) return UV_ERR_STATE;
-            RUN(linear(t0, C, rows, C, b + ".attn_temporal.to_out.0.weight", b + ".attn_temporal.to_out.0.bias", C, h5, C, h4, C));
+            UV_RUN(linear(t0, C, rows, C, b + ".attn_temporal.to_out.0.weight", b + ".attn_temporal.to_out.0.bias", C, h5, C, h4, C));
             free(h4);
             h4 = h5;
         }
@@ -1266,31 +1091,26 @@ struct Fwd {
         out->imgs = x.imgs; out->H = x.H; out->W = x.W; out->C = C;
         out->p = alloc(rows * C);
         if (!out->p) return UV_ERR_STATE;
-        RUN(linear(h4, C, rows, C, p + (u.find(p + ".proj_out.weight#nhwc") ? ".proj_out.weight#nhwc" : ".proj_out.weight"), p + ".proj_out.bias", C, out->p,
+        UV_RUN(linear(h4, C, rows, C, p + (u.find(p + ".proj_out.weight#nhwc") ? ".proj_out.weight#nhwc" : ".proj_out.weight"), p + ".proj_out.bias", C, out->p,
                    C, x.p, C, nullptr, 0, nullptr, nullptr, &out->gst));
         free(h4);
         return UV_OK;
     }
 };
 
-int UNet::missing_error() {
-    uv_set_error("weight '%s' was never loaded", missing.c_str());
-    return UV_ERR_STATE;
-}
-
 int UNet::forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int Wd, int text_len,
-                  const univst_pnp_t* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s) {
+                  const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s) {
     UV_REQUIRE(finalized, "forward: call univst_unet_finalize after loading weights");
     UV_REQUIRE(world == 1 || (temporal_conv_active.empty() && temporal_attn_active.empty()),
                "forward: trained temporal layers couple all frames of a pixel; frame sharding (world=%d) is not supported with them", world);
     if (native_comm) {
-        RUN(uv_comm_poll(native_comm));          // a peer timed out in an earlier call: report instead of queueing more work
+        UV_RUN(uv_comm_poll(native_comm));          // a peer timed out in an earlier call: report instead of queueing more work
         uv_comm_bind_stream(native_comm, s);
     }
     UV_REQUIRE(B >= 1 && B <= 8 && F >= 1 && H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0,
                "forward: unsupported geometry B=%d F=%d H=%d W=%d (H, W multiples of 8; B <= 8)", B, F, H, Wd);
-    RUN(reserve(B, F, H, Wd));
-    missing.clear();
+    UV_RUN(reserve(B, F, H, Wd));
+    clear_missing();
     const int* boc = cfg.block_out_channels;
     const int C0 = boc[0], TED = 4 * C0, L = cfg.layers_per_block;
     Fwd f{*this, s, B, F, text_len, pnp};
@@ -1326,27 +1146,27 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     half_t* e1 = f.alloc((long)B * TED);
     f.emb = f.alloc((long)B * TED);
     if (!tsin || !e1 || !f.emb) return UV_ERR_STATE;
-    RUN(uv_launch_timestep_embed(timestep, tsin, B, C0, cfg.flip_sin_to_cos, cfg.freq_shift, s));
+    UV_RUN(uv_launch_timestep_embed(timestep, tsin, B, C0, cfg.flip_sin_to_cos, cfg.freq_shift, s));
     {
         half_t *w1 = W("time_embedding.linear_1.weight"), *b1 = W("time_embedding.linear_1.bias");
         half_t *w2 = W("time_embedding.linear_2.weight"), *b2 = W("time_embedding.linear_2.bias");
-        if (!w1 || !b1 || !w2 || !b2) return missing_error();
-        RUN(uv_launch_linear_small(tsin, w1, b1, e1, B, TED, C0, 0, s));
-        RUN(uv_launch_linear_small(e1, w2, b2, f.emb, B, TED, TED, 1, s));
+        if (!w1 || !b1 || !w2 || !b2) return missing_error("unet");
+        UV_RUN(uv_launch_linear_small(tsin, w1, b1, e1, B, TED, C0, 0, s));
+        UV_RUN(uv_launch_linear_small(e1, w2, b2, f.emb, B, TED, TED, 1, s));
         if (temb_total > 0) {           // resnet.py:349-351 for all resnets at once
             half_t *wa = W("time_emb_proj#all.weight"), *ba = W("time_emb_proj#all.bias");
             f.temb_all = f.alloc((long)B * temb_total);
-            if (!wa || !ba || !f.temb_all) return missing_error();
-            RUN(uv_launch_linear_small(f.emb, wa, ba, f.temb_all, B, (int)temb_total, TED, 1, s));
+            if (!wa || !ba || !f.temb_all) return missing_error("unet");
+            UV_RUN(uv_launch_linear_small(f.emb, wa, ba, f.temb_all, B, (int)temb_total, TED, 1, s));
         }
     }
     // ---- conv_in
     const int CP = (cfg.in_channels + 7) / 8 * 8;
     Act x0{f.alloc((long)B * F * H * Wd * CP), B * F, H, Wd, CP};
     if (!x0.p) return UV_ERR_STATE;
-    RUN(uv_launch_ncfhw_to_nhwc(sample, x0.p, B, cfg.in_channels, F, H * Wd, CP, s));
+    UV_RUN(uv_launch_ncfhw_to_nhwc(sample, x0.p, B, cfg.in_channels, F, H * Wd, CP, s));
     Act x;
-    RUN(f.conv(x0, nullptr, "conv_in", C0, 9, 1, 0, nullptr, nullptr, &x, 0, true));
+    UV_RUN(f.conv(x0, nullptr, "conv_in", C0, 9, 1, 0, nullptr, nullptr, &x, 0, true));
     f.free(x0.p);
 
     std::vector<Act> skips;
@@ -1357,14 +1177,14 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         const bool has_attn = i < 3;
         for (int j = 0; j < L; ++j) {
             Act y;
-            RUN(f.resblock(p + ".resnets." + std::to_string(j), x, nullptr, boc[i], &y));
+            UV_RUN(f.resblock(p + ".resnets." + std::to_string(j), x, nullptr, boc[i], &y));
             bool x_is_skip = false;
             for (auto& sk : skips) x_is_skip |= (sk.p == x.p);
             if (!x_is_skip) f.free(x.p);
             x = y;
             if (has_attn) {
                 Act z;
-                RUN(f.transformer(p + ".attentions." + std::to_string(j), x, false, cfg.attention_heads[i], &z));
+                UV_RUN(f.transformer(p + ".attentions." + std::to_string(j), x, false, cfg.attention_heads[i], &z));
                 f.free(x.p);
                 x = z;
             }
@@ -1372,7 +1192,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         }
         if (i != 3) {
             Act y;
-            RUN(f.conv(x, nullptr, p + ".downsamplers.0.conv", boc[i], 9, 2, 0, nullptr, nullptr, &y, 0, true));
+            UV_RUN(f.conv(x, nullptr, p + ".downsamplers.0.conv", boc[i], 9, 2, 0, nullptr, nullptr, &y, 0, true));
             x = y;
             skips.push_back(x);
         }
@@ -1380,10 +1200,10 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     // ---- mid
     {
         Act y, z, w;
-        RUN(f.resblock("mid_block.resnets.0", x, nullptr, boc[3], &y));
-        RUN(f.transformer("mid_block.attentions.0", y, false, cfg.attention_heads[3], &z));
+        UV_RUN(f.resblock("mid_block.resnets.0", x, nullptr, boc[3], &y));
+        UV_RUN(f.transformer("mid_block.attentions.0", y, false, cfg.attention_heads[3], &z));
         f.free(y.p);
-        RUN(f.resblock("mid_block.resnets.1", z, nullptr, boc[3], &w));
+        UV_RUN(f.resblock("mid_block.resnets.1", z, nullptr, boc[3], &w));
         f.free(z.p);
         x = w;   // previous x is skips.back(), still owned by the skip list
     }
@@ -1397,20 +1217,20 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
             Act sk = skips.back();
             skips.pop_back();
             Act y;
-            RUN(f.resblock(p + ".resnets." + std::to_string(j), x, &sk, Cout, &y));
+            UV_RUN(f.resblock(p + ".resnets." + std::to_string(j), x, &sk, Cout, &y));
             f.free(x.p);
             f.free(sk.p);
             x = y;
             if (has_attn) {
                 Act z;
-                RUN(f.transformer(p + ".attentions." + std::to_string(j), x, j < 3 && pnp_layers[i][j], cfg.attention_heads[3 - i], &z));
+                UV_RUN(f.transformer(p + ".attentions." + std::to_string(j), x, j < 3 && pnp_layers[i][j], cfg.attention_heads[3 - i], &z));
                 f.free(x.p);
                 x = z;
             }
         }
         if (i != 3) {
             Act y;
-            RUN(f.conv(x, nullptr, p + ".upsamplers.0.conv", Cout, 9, 1, 1, nullptr, nullptr, &y, 0, true));
+            UV_RUN(f.conv(x, nullptr, p + ".upsamplers.0.conv", Cout, 9, 1, 1, nullptr, nullptr, &y, 0, true));
             f.free(x.p);
             x = y;
         }
@@ -1420,15 +1240,15 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     // ---- out
     half_t* n = f.alloc(x.rows() * x.C);
     if (!n) return UV_ERR_STATE;
-    RUN(f.groupnorm(x, nullptr, F * x.H * x.W, cfg.norm_eps, "conv_norm_out", 1, n, true));
+    UV_RUN(f.groupnorm(x, nullptr, F * x.H * x.W, cfg.norm_eps, "conv_norm_out", 1, n, true));
     Act na{n, x.imgs, x.H, x.W, x.C}, y;
-    RUN(f.conv(na, nullptr, "conv_out", cfg.out_channels, 9, 1, 0, nullptr, nullptr, &y));
-    RUN(uv_launch_nhwc_to_ncfhw(y.p, cfg.out_channels, eps_out, B, cfg.out_channels, F, H * Wd, s));
+    UV_RUN(f.conv(na, nullptr, "conv_out", cfg.out_channels, 9, 1, 0, nullptr, nullptr, &y));
+    UV_RUN(uv_launch_nhwc_to_ncfhw(y.p, cfg.out_channels, eps_out, B, cfg.out_channels, F, H * Wd, s));
     if (x_dirty) {                 // the forked stream's posts of this forward complete before anything the caller queues behind it (and a capture can end)
         UV_HIP(hipEventRecord(ev_join, xstream));
         UV_HIP(hipStreamWaitEvent(s, ev_join, 0));
         x_dirty = false;
     }
-    if (!missing.empty()) return missing_error();
+    if (!missing.empty()) return missing_error("unet");
     return UV_OK;
 }

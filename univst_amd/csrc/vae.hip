@@ -27,37 +27,11 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
 #include "kernels.h"
-#include "unet.h"
 #include "vae.h"
 
 namespace {
 
-inline unsigned nb(long n) { return (unsigned)((n + 255) / 256); }
-
-__global__ void v_convert_f32_f16_kernel(const float* __restrict__ in, half_t* __restrict__ out, long n) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (half_t)in[i];
-}
-// [Co][Ci][taps] -> [Co][taps][CiP] (zero padded input channels): 2-D convs (taps = kh*kw) and Conv3d (3,1,1) (taps = 3) alike
-__global__ void v_permute_conv_weight_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci, int taps, int CiP) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Co * taps * CiP) return;
-    const int c = (int)(i % CiP), t = (int)((i / CiP) % taps), o = (int)(i / ((long)CiP * taps));
-    out[i] = c < Ci ? in[((long)o * Ci + c) * taps + t] : (half_t)0.f;
-}
-// [Co][Ci][3][3] -> tap-inner [Co][Ci/64][9][64] (GemmParams::korder = 1: the nine taps of a 64-channel slab are consecutive k tiles)
-__global__ void v_permute_conv_weight_ti_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Co * Ci * 9) return;
-    const int j = (int)(i % 64), t = (int)((i / 64) % 9), q = (int)((i / (64 * 9)) % (Ci / 64)), o = (int)(i / ((long)Ci * 9));
-    out[i] = in[((long)o * Ci + q * 64 + j) * 9 + t];
-}
-__global__ void v_scale_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, long n, float f) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (half_t)((float)in[i] * f);
-}
 // softmax over the rows of S [rows][N] fp16, in place, fp32 arithmetic; one wave per row (N % 8 == 0).  The scores arrive ROUNDED TO fp16: a logit beyond
 // 65504 is +inf there and exp(inf - inf) would turn the whole row into NaN (SD-family VAE mid-block activations are large: force_upcast in the stock
 // config) — scores are clamped to the fp16 range on load, so such a row degrades to a tie between its saturated keys instead
@@ -125,57 +99,17 @@ __global__ __launch_bounds__(256) void v_time_conv_out_kernel(const half_t* __re
 }  // namespace
 
 Vae::~Vae() {
-    for (auto& kv : weights) (void)hipFree(kv.second.ptr);
-    for (auto& kv : derived) (void)hipFree(kv.second.ptr);
     if (arena.base) (void)hipFree(arena.base);
 }
 
 int Vae::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
-    UV_REQUIRE(key && dev_ptr && ndim >= 1 && ndim <= 5, "vae_load_tensor: bad arguments");
-    UV_REQUIRE(dtype == UNIVST_F16 || dtype == UNIVST_F32, "vae_load_tensor: dtype %d", dtype);
-    long n = 1;
-    WTensor t;
-    for (int i = 0; i < ndim; ++i) {
-        n *= shape[i];
-        t.shape.push_back(shape[i]);
-    }
-    UV_REQUIRE(n > 0, "%s: empty tensor", key);
-    UV_HIP(hipMalloc((void**)&t.ptr, (size_t)n * sizeof(half_t)));
-    if (dtype == UNIVST_F16) UV_HIP(hipMemcpyAsync(t.ptr, dev_ptr, (size_t)n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-    else hipLaunchKernelGGL(v_convert_f32_f16_kernel, dim3(nb(n)), dim3(256), 0, s, (const float*)dev_ptr, t.ptr, n);
-    UV_LAUNCH_CHECK();
-    auto it = weights.find(key);
-    if (it != weights.end()) {
-        UV_HIP(hipStreamSynchronize(s));
-        (void)hipFree(it->second.ptr);
-    }
-    weights[key] = t;
+    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
     finalized = false;
     return UV_OK;
 }
 
-const WTensor* Vae::find(const std::string& k) const {
-    auto it = weights.find(k);
-    if (it != weights.end()) return &it->second;
-    auto jt = derived.find(k);
-    return jt != derived.end() ? &jt->second : nullptr;
-}
-half_t* Vae::W(const std::string& k) {
-    const WTensor* t = find(k);
-    if (!t) {
-        missing = k;
-        return nullptr;
-    }
-    return t->ptr;
-}
-int Vae::missing_error() {
-    uv_set_error("vae: weight '%s' was never loaded", missing.c_str());
-    return UV_ERR_STATE;
-}
-
 int Vae::finalize(hipStream_t s) {
-    for (auto& kv : derived) (void)hipFree(kv.second.ptr);
-    derived.clear();
+    clear_derived();
     mix.clear();
     std::vector<std::string> keys;
     for (auto& kv : weights) keys.push_back(kv.first);
@@ -183,48 +117,22 @@ int Vae::finalize(hipStream_t s) {
         size_t n = strlen(suf);
         return a.size() >= n && a.compare(a.size() - n, n, suf) == 0;
     };
-    auto derive = [&](const std::string& k, std::vector<long> shape, half_t** out) {
-        long n = 1;
-        for (long v : shape) n *= v;
-        WTensor t;
-        t.shape = shape;
-        if (hipMalloc((void**)&t.ptr, (size_t)n * sizeof(half_t)) != hipSuccess) {
-            uv_set_error("vae_finalize: out of device memory for %s", k.c_str());
-            return UV_ERR_HIP;
-        }
-        derived[k] = t;
-        *out = t.ptr;
-        return UV_OK;
-    };
     for (const std::string& k : keys) {
         const WTensor& t = weights[k];
         if ((t.shape.size() == 4 || t.shape.size() == 5) && ends(k, ".weight") && k != "decoder.time_conv_out.weight") {
-            // Conv2d [Co,Ci,kh,kw] / Conv3d [Co,Ci,3,1,1] -> [Co][taps][CiP]
-            const int Co = (int)t.shape[0], Ci = (int)t.shape[1];
+            // Conv2d [Co,Ci,kh,kw] / Conv3d [Co,Ci,3,1,1] -> [Co][taps][CiP] (+ the tap-inner copy for the 256x320 tile's fast im2col addressing)
             int taps = 1;
             for (size_t d = 2; d < t.shape.size(); ++d) taps *= (int)t.shape[d];
             if (t.shape.size() == 4) UV_REQUIRE((taps == 1 || taps == 9) && t.shape[2] == t.shape[3], "%s: only 1x1 / 3x3 Conv2d", k.c_str());
             else UV_REQUIRE(taps == 3 && t.shape[2] == 3, "%s: only (3,1,1) Conv3d", k.c_str());
-            const int CiP = (Ci + 7) / 8 * 8;
-            half_t* d;
-            int rc = derive(k + "#nhwc", {Co, taps, CiP}, &d);
-            if (rc) return rc;
-            hipLaunchKernelGGL(v_permute_conv_weight_kernel, dim3(nb((long)Co * taps * CiP)), dim3(256), 0, s, t.ptr, d, Co, Ci, taps, CiP);
-            if (t.shape.size() == 4 && taps == 9 && Ci % 64 == 0) {      // tap-inner copy for the 256x320 tile's fast im2col addressing
-                half_t* d2;
-                rc = derive(k + "#ti", {Co, Ci / 64, 9, 64}, &d2);
-                if (rc) return rc;
-                hipLaunchKernelGGL(v_permute_conv_weight_ti_kernel, dim3(nb((long)Co * Ci * 9)), dim3(256), 0, s, t.ptr, d2, Co, Ci);
-            }
+            UV_RUN(uv_derive_conv_layouts(*this, k, s));
         } else if (ends(k, ".to_q.weight") || ends(k, ".to_q.bias")) {
             // the attention scale 1/sqrt(head_dim) (one head: head_dim = C) rides on the q projection, so the fp16 scores are the scaled ones
             long n = 1;
             for (long v : t.shape) n *= v;
             half_t* d;
-            int rc = derive(k + "#qs", t.shape, &d);
-            if (rc) return rc;
-            const long Cq = t.shape[0];
-            hipLaunchKernelGGL(v_scale_kernel, dim3(nb(n)), dim3(256), 0, s, t.ptr, d, n, 1.f / sqrtf((float)Cq));
+            UV_RUN(derive(k + "#qs", t.shape, &d));
+            UV_RUN(uv_launch_scale_f16(t.ptr, d, n, 1.f / sqrtf((float)t.shape[0]), s));
         }
     }
     UV_LAUNCH_CHECK();
@@ -246,9 +154,8 @@ int Vae::finalize(hipStream_t s) {
             long n = 1;
             for (long v : t->shape) n *= v;
             half_t* d;
-            int rc = derive(kv.first + suf + "#mix", t->shape, &d);
-            if (rc) return rc;
-            hipLaunchKernelGGL(v_scale_kernel, dim3(nb(n)), dim3(256), 0, s, t->ptr, d, n, sig);
+            UV_RUN(derive(kv.first + suf + "#mix", t->shape, &d));
+            UV_RUN(uv_launch_scale_f16(t->ptr, d, n, sig, s));
         }
     }
     UV_LAUNCH_CHECK();
@@ -256,12 +163,6 @@ int Vae::finalize(hipStream_t s) {
     finalized = true;
     return UV_OK;
 }
-
-#define RUN(x)                \
-    do {                      \
-        int _rc = (x);        \
-        if (_rc) return _rc;  \
-    } while (0)
 
 namespace {
 struct VFwd {
@@ -279,7 +180,7 @@ struct VFwd {
 
     int groupnorm(const Act& a, long rows_per_stat, const std::string& p, int silu, half_t* out, float eps = 1e-6f) {
         half_t *g = W(p + ".weight"), *b = W(p + ".bias");
-        if (!g || !b) return u.missing_error();
+        if (!g || !b) return u.missing_error("vae");
         return uv_launch_groupnorm(a.p, nullptr, a.C, 0, a.rows(), (int)rows_per_stat, u.cfg.norm_num_groups, eps, g, b, silu, out, gn_ws, s);
     }
     // 2-D conv on [imgs, H, W, C]; asym: the encoder's stride-2 conv (input padded at the bottom / right only)
@@ -308,7 +209,7 @@ struct VFwd {
         g.korder = (taps == 9 && !asym && stride == 1 && a.C % 64 == 0 && u.find(p + ".weight#ti")) ? 1 : 0;
         g.W = W(p + (g.korder ? ".weight#ti" : ".weight#nhwc"));
         g.bias = W(p + ".bias");
-        if (!g.W || !g.bias) return u.missing_error();
+        if (!g.W || !g.bias) return u.missing_error("vae");
         g.R = R;
         g.ldr = Cout;
         out->imgs = a.imgs;
@@ -339,7 +240,7 @@ struct VFwd {
         g.K = 3 * a.C;
         g.W = W(p + ".weight#nhwc" + mixsuf);
         g.bias = W(p + ".bias" + mixsuf);
-        if (!g.W || !g.bias) return u.missing_error();
+        if (!g.W || !g.bias) return u.missing_error("vae");
         g.R = R;
         g.ldr = a.C;
         g.Y = out;
@@ -366,24 +267,24 @@ struct VFwd {
         const long hw = (long)x.H * x.W;
         half_t* n1 = alloc(x.rows() * x.C);
         if (!n1) return UV_ERR_STATE;
-        RUN(groupnorm(x, hw, p + ".norm1", 1, n1));
+        UV_RUN(groupnorm(x, hw, p + ".norm1", 1, n1));
         Act n1a{n1, x.imgs, x.H, x.W, x.C}, h;
-        RUN(conv(n1a, p + ".conv1", Cout, 9, 1, 0, false, nullptr, &h));
+        UV_RUN(conv(n1a, p + ".conv1", Cout, 9, 1, 0, false, nullptr, &h));
         free(n1);
         half_t* n2 = alloc(h.rows() * Cout);
         if (!n2) return UV_ERR_STATE;
-        RUN(groupnorm(h, hw, p + ".norm2", 1, n2));
+        UV_RUN(groupnorm(h, hw, p + ".norm2", 1, n2));
         free(h.p);
         const half_t* res = x.p;
         Act sc{};
         if (u.find(p + ".conv_shortcut.weight")) {
-            RUN(conv(x, p + ".conv_shortcut", Cout, 1, 1, 0, false, nullptr, &sc));
+            UV_RUN(conv(x, p + ".conv_shortcut", Cout, 1, 1, 0, false, nullptr, &sc));
             res = sc.p;
         } else {
             UV_REQUIRE(x.C == Cout, "%s: no conv_shortcut but %d -> %d channels", p.c_str(), x.C, Cout);
         }
         Act n2a{n2, x.imgs, x.H, x.W, Cout};
-        RUN(conv(n2a, p + ".conv2", Cout, 9, 1, 0, false, res, out));
+        UV_RUN(conv(n2a, p + ".conv2", Cout, 9, 1, 0, false, res, out));
         free(n2);
         if (sc.p) free(sc.p);
         return UV_OK;
@@ -394,14 +295,14 @@ struct VFwd {
         const long rps = (long)F * x.H * x.W;
         half_t* n1 = alloc(x.rows() * x.C);
         if (!n1) return UV_ERR_STATE;
-        RUN(groupnorm(x, rps, p + ".norm1", 1, n1, 1e-5f));
+        UV_RUN(groupnorm(x, rps, p + ".norm1", 1, n1, 1e-5f));
         half_t* h = alloc(x.rows() * x.C);
         if (!h) return UV_ERR_STATE;
         Act n1a{n1, x.imgs, x.H, x.W, x.C};
-        RUN(frame_conv(n1a, F, p + ".conv1", nullptr, h));
+        UV_RUN(frame_conv(n1a, F, p + ".conv1", nullptr, h));
         Act ha{h, x.imgs, x.H, x.W, x.C};
-        RUN(groupnorm(ha, rps, p + ".norm2", 1, n1, 1e-5f));
-        RUN(frame_conv(n1a, F, p + ".conv2", x.p, out, "#mix"));     // x + sigmoid(mix) * (conv2 + bias): the block's output AND the AlphaBlender (finalize)
+        UV_RUN(groupnorm(ha, rps, p + ".norm2", 1, n1, 1e-5f));
+        UV_RUN(frame_conv(n1a, F, p + ".conv2", x.p, out, "#mix"));     // x + sigmoid(mix) * (conv2 + bias): the block's output AND the AlphaBlender (finalize)
         free(h);
         free(n1);
         return UV_OK;
@@ -409,12 +310,12 @@ struct VFwd {
     // diffusers SpatioTemporalResBlock with AlphaBlender("learned", switch_spatial_to_temporal_mix = True)
     int st_resblock(const std::string& p, const Act& x, int F, int Cout, Act* out) {
         Act sp;
-        RUN(resnet2d(p + ".spatial_res_block", x, Cout, &sp));
+        UV_RUN(resnet2d(p + ".spatial_res_block", x, Cout, &sp));
         auto it = u.mix.find(p);
         UV_REQUIRE(it != u.mix.end(), "%s: time_mixer.mix_factor missing", p.c_str());
         half_t* tp = alloc(sp.rows() * Cout);
         if (!tp) return UV_ERR_STATE;
-        RUN(resnet_temporal(p + ".temporal_res_block", sp, F, tp));      // = alpha * spatial + (1 - alpha) * temporal, alpha = 1 - sigmoid(mix): folded into conv2
+        UV_RUN(resnet_temporal(p + ".temporal_res_block", sp, F, tp));      // = alpha * spatial + (1 - alpha) * temporal, alpha = 1 - sigmoid(mix): folded into conv2
         free(sp.p);
         sp.p = tp;
         *out = sp;
@@ -430,24 +331,24 @@ struct VFwd {
         UV_REQUIRE(N % 8 == 0 && C % 8 == 0, "%s: %d tokens x %d channels", p.c_str(), N, C);
         half_t* gn = alloc(rows * C);
         if (!gn) return UV_ERR_STATE;
-        RUN(groupnorm(x, N, p + ".group_norm", 0, gn));
+        UV_RUN(groupnorm(x, N, p + ".group_norm", 0, gn));
         half_t *q = alloc(rows * C), *k = alloc(rows * C), *v = alloc(rows * C);
         if (!q || !k || !v) return UV_ERR_STATE;
         half_t *wq = W(p + ".to_q.weight#qs"), *bq = W(p + ".to_q.bias#qs"), *wk = W(p + ".to_k.weight"), *bk = W(p + ".to_k.bias"), *wv = W(p + ".to_v.weight"),
                *bv = W(p + ".to_v.bias"), *wo = W(p + ".to_out.0.weight"), *bo = W(p + ".to_out.0.bias");
-        if (!wq || !bq || !wk || !bk || !wv || !bv || !wo || !bo) return u.missing_error();
-        RUN(linear(gn, rows, C, wq, bq, C, q));
-        RUN(linear(gn, rows, C, wk, bk, C, k));
-        RUN(linear(gn, rows, C, wv, bv, C, v));
+        if (!wq || !bq || !wk || !bk || !wv || !bv || !wo || !bo) return u.missing_error("vae");
+        UV_RUN(linear(gn, rows, C, wq, bq, C, q));
+        UV_RUN(linear(gn, rows, C, wk, bk, C, k));
+        UV_RUN(linear(gn, rows, C, wv, bv, C, v));
         half_t *S = alloc((long)N * N), *vT = alloc((long)N * C);
         if (!S || !vT) return UV_ERR_STATE;
         for (int f = 0; f < x.imgs; ++f) {
             const long o = (long)f * N * C;
-            RUN(linear(q + o, N, C, k + o, nullptr, N, S));                              // scores [N, N] (already scaled: the scale rides on q)
+            UV_RUN(linear(q + o, N, C, k + o, nullptr, N, S));                              // scores [N, N] (already scaled: the scale rides on q)
             hipLaunchKernelGGL(v_softmax_rows_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, S, (long)N, N);
             hipLaunchKernelGGL(v_transpose_kernel, dim3((C + 31) / 32, (N + 31) / 32), dim3(256), 0, s, v + o, vT, N, C);
             UV_LAUNCH_CHECK();
-            RUN(linear(S, N, N, vT, nullptr, C, gn + o));                                 // O = P V  (gn is free by now)
+            UV_RUN(linear(S, N, N, vT, nullptr, C, gn + o));                                 // O = P V  (gn is free by now)
         }
         free(S);
         free(vT);
@@ -457,7 +358,7 @@ struct VFwd {
         out->imgs = x.imgs; out->H = x.H; out->W = x.W; out->C = C;
         out->p = alloc(rows * C);
         if (!out->p) return UV_ERR_STATE;
-        RUN(linear(gn, rows, C, wo, bo, C, out->p, x.p));
+        UV_RUN(linear(gn, rows, C, wo, bo, C, out->p, x.p));
         free(gn);
         return UV_OK;
     }
@@ -470,16 +371,7 @@ int Vae::reserve(long imgs, int H, int Wd) {
     const long rows = imgs * H * Wd;
     const long N = (long)(H / 8) * (Wd / 8);
     size_t need = (size_t)rows * cfg.block_out_channels[1] * 2 * 5 + (size_t)N * N * 2 + (size_t)imgs * N * cfg.block_out_channels[3] * 2 * 8 + (256u << 20);
-    if (arena.size < need) {
-        UV_HIP(hipDeviceSynchronize());
-        if (arena.base) UV_HIP(hipFree(arena.base));
-        arena.base = nullptr;
-        arena.size = 0;
-        UV_HIP(hipMalloc((void**)&arena.base, need));
-        arena.size = need;
-    }
-    arena.reset();
-    return UV_OK;
+    return arena.ensure(need);
 }
 
 // z [imgs, latent, h, w] fp16 (already divided by the scaling factor) -> out [imgs, out_channels, 8h, 8w] fp16; imgs = clips x num_frames
@@ -487,52 +379,53 @@ int Vae::decode(const half_t* z, long imgs, int num_frames, int h, int w, half_t
     UV_REQUIRE(finalized, "vae_decode: call univst_vae_finalize after loading weights");
     UV_REQUIRE(imgs > 0 && num_frames > 0 && imgs % num_frames == 0 && h > 0 && w > 0, "vae_decode: %ld images are not whole clips of %d frames", imgs, num_frames);
     const int* boc = cfg.block_out_channels;
-    RUN(reserve(imgs, h * 8, w * 8));
+    UV_RUN(reserve(imgs, h * 8, w * 8));
+    clear_missing();
     VFwd f{*this, s};
     f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
     if (!f.gn_ws) return UV_ERR_STATE;
     const int Lp = (cfg.latent_channels + 7) / 8 * 8;
     Act x{f.alloc(imgs * h * w * Lp), (int)imgs, h, w, Lp};
     if (!x.p) return UV_ERR_STATE;
-    RUN(uv_launch_ncfhw_to_nhwc(z, x.p, (int)imgs, cfg.latent_channels, 1, h * w, Lp, s));
+    UV_RUN(uv_launch_ncfhw_to_nhwc(z, x.p, (int)imgs, cfg.latent_channels, 1, h * w, Lp, s));
     Act cur;
-    RUN(f.conv(x, "decoder.conv_in", boc[3], 9, 1, 0, false, nullptr, &cur));
+    UV_RUN(f.conv(x, "decoder.conv_in", boc[3], 9, 1, 0, false, nullptr, &cur));
     f.free(x.p);
     Act nxt;
     // mid block: resnets[0], attention, resnets[1]
-    RUN(f.st_resblock("decoder.mid_block.resnets.0", cur, num_frames, boc[3], &nxt));
+    UV_RUN(f.st_resblock("decoder.mid_block.resnets.0", cur, num_frames, boc[3], &nxt));
     f.free(cur.p);
     cur = nxt;
-    RUN(f.attention("decoder.mid_block.attentions.0", cur, &nxt));
+    UV_RUN(f.attention("decoder.mid_block.attentions.0", cur, &nxt));
     f.free(cur.p);
     cur = nxt;
     if (cfg.layers_per_block >= 2) {      // (MidBlockTemporalDecoder.forward zips resnets[1:] with its ONE attention: only resnets[1] runs behind it)
-        RUN(f.st_resblock("decoder.mid_block.resnets.1", cur, num_frames, boc[3], &nxt));
+        UV_RUN(f.st_resblock("decoder.mid_block.resnets.1", cur, num_frames, boc[3], &nxt));
         f.free(cur.p);
         cur = nxt;
     }
     for (int b = 0; b < 4; ++b) {
         const int Cout = boc[3 - b];
         for (int l = 0; l < cfg.layers_per_block + 1; ++l) {
-            RUN(f.st_resblock("decoder.up_blocks." + std::to_string(b) + ".resnets." + std::to_string(l), cur, num_frames, Cout, &nxt));
+            UV_RUN(f.st_resblock("decoder.up_blocks." + std::to_string(b) + ".resnets." + std::to_string(l), cur, num_frames, Cout, &nxt));
             f.free(cur.p);
             cur = nxt;
         }
         if (b < 3) {
-            RUN(f.conv(cur, "decoder.up_blocks." + std::to_string(b) + ".upsamplers.0.conv", Cout, 9, 1, 1, false, nullptr, &nxt));
+            UV_RUN(f.conv(cur, "decoder.up_blocks." + std::to_string(b) + ".upsamplers.0.conv", Cout, 9, 1, 1, false, nullptr, &nxt));
             f.free(cur.p);
             cur = nxt;
         }
     }
     half_t* n = f.alloc(cur.rows() * cur.C);
     if (!n) return UV_ERR_STATE;
-    RUN(f.groupnorm(cur, (long)cur.H * cur.W, "decoder.conv_norm_out", 1, n));
+    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "decoder.conv_norm_out", 1, n));
     Act na{n, cur.imgs, cur.H, cur.W, cur.C};
     f.free(cur.p);
-    RUN(f.conv(na, "decoder.conv_out", cfg.out_channels, 9, 1, 0, false, nullptr, &nxt));
+    UV_RUN(f.conv(na, "decoder.conv_out", cfg.out_channels, 9, 1, 0, false, nullptr, &nxt));
     f.free(n);
     half_t *tw = W("decoder.time_conv_out.weight"), *tb = W("decoder.time_conv_out.bias");
-    if (!tw || !tb) return missing_error();
+    if (!tw || !tb) return missing_error("vae");
     const long HW = (long)nxt.H * nxt.W;
     hipLaunchKernelGGL(v_time_conv_out_kernel, dim3(nb(imgs * HW)), dim3(256), 0, s, nxt.p, cfg.out_channels, out, tw, tb, (int)(imgs / num_frames), num_frames, HW,
                        cfg.out_channels);
@@ -546,48 +439,49 @@ int Vae::encode(const half_t* xin, long imgs, int H, int Wd, half_t* moments, hi
     UV_REQUIRE(finalized, "vae_encode: call univst_vae_finalize after loading weights");
     UV_REQUIRE(imgs > 0 && H % 8 == 0 && Wd % 8 == 0, "vae_encode: %ld images of %d x %d (multiples of 8)", imgs, H, Wd);
     const int* boc = cfg.block_out_channels;
-    RUN(reserve(imgs, H, Wd));
+    UV_RUN(reserve(imgs, H, Wd));
+    clear_missing();
     VFwd f{*this, s};
     f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
     if (!f.gn_ws) return UV_ERR_STATE;
     const int Ip = (cfg.in_channels + 7) / 8 * 8;
     Act x{f.alloc(imgs * H * Wd * Ip), (int)imgs, H, Wd, Ip};
     if (!x.p) return UV_ERR_STATE;
-    RUN(uv_launch_ncfhw_to_nhwc(xin, x.p, (int)imgs, cfg.in_channels, 1, H * Wd, Ip, s));
+    UV_RUN(uv_launch_ncfhw_to_nhwc(xin, x.p, (int)imgs, cfg.in_channels, 1, H * Wd, Ip, s));
     Act cur, nxt;
-    RUN(f.conv(x, "encoder.conv_in", boc[0], 9, 1, 0, false, nullptr, &cur));
+    UV_RUN(f.conv(x, "encoder.conv_in", boc[0], 9, 1, 0, false, nullptr, &cur));
     f.free(x.p);
     for (int b = 0; b < 4; ++b) {
         for (int l = 0; l < cfg.layers_per_block; ++l) {
-            RUN(f.resnet2d("encoder.down_blocks." + std::to_string(b) + ".resnets." + std::to_string(l), cur, boc[b], &nxt));
+            UV_RUN(f.resnet2d("encoder.down_blocks." + std::to_string(b) + ".resnets." + std::to_string(l), cur, boc[b], &nxt));
             f.free(cur.p);
             cur = nxt;
         }
         if (b < 3) {
-            RUN(f.conv(cur, "encoder.down_blocks." + std::to_string(b) + ".downsamplers.0.conv", boc[b], 9, 2, 0, true, nullptr, &nxt));
+            UV_RUN(f.conv(cur, "encoder.down_blocks." + std::to_string(b) + ".downsamplers.0.conv", boc[b], 9, 2, 0, true, nullptr, &nxt));
             f.free(cur.p);
             cur = nxt;
         }
     }
-    RUN(f.resnet2d("encoder.mid_block.resnets.0", cur, boc[3], &nxt));
+    UV_RUN(f.resnet2d("encoder.mid_block.resnets.0", cur, boc[3], &nxt));
     f.free(cur.p);
     cur = nxt;
-    RUN(f.attention("encoder.mid_block.attentions.0", cur, &nxt));
+    UV_RUN(f.attention("encoder.mid_block.attentions.0", cur, &nxt));
     f.free(cur.p);
     cur = nxt;
-    RUN(f.resnet2d("encoder.mid_block.resnets.1", cur, boc[3], &nxt));
+    UV_RUN(f.resnet2d("encoder.mid_block.resnets.1", cur, boc[3], &nxt));
     f.free(cur.p);
     cur = nxt;
     half_t* n = f.alloc(cur.rows() * cur.C);
     if (!n) return UV_ERR_STATE;
-    RUN(f.groupnorm(cur, (long)cur.H * cur.W, "encoder.conv_norm_out", 1, n));
+    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "encoder.conv_norm_out", 1, n));
     Act na{n, cur.imgs, cur.H, cur.W, cur.C};
     f.free(cur.p);
-    RUN(f.conv(na, "encoder.conv_out", 2 * cfg.latent_channels, 9, 1, 0, false, nullptr, &cur));
+    UV_RUN(f.conv(na, "encoder.conv_out", 2 * cfg.latent_channels, 9, 1, 0, false, nullptr, &cur));
     f.free(n);
-    RUN(f.conv(cur, "quant_conv", 2 * cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt));
+    UV_RUN(f.conv(cur, "quant_conv", 2 * cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt));
     f.free(cur.p);
-    RUN(uv_launch_nhwc_to_ncfhw(nxt.p, 2 * cfg.latent_channels, moments, (int)imgs, 2 * cfg.latent_channels, 1, nxt.H * nxt.W, s));
+    UV_RUN(uv_launch_nhwc_to_ncfhw(nxt.p, 2 * cfg.latent_channels, moments, (int)imgs, 2 * cfg.latent_channels, 1, nxt.H * nxt.W, s));
     f.free(nxt.p);
     return UV_OK;
 }

@@ -202,6 +202,43 @@ int univst_raft_corr_lookup(const float* pyramid, const float* coords, int fh, i
  * [8 fh, 8 fw, 2]: softmax over the 9 taps k of each sub-pixel (i, j) applied to the 3x3 neighbourhood (zero padded) of 8 * flow */
 int univst_raft_convex_upsample(const float* flow, const void* mask, int fh, int fw, float* out, void* stream);
 
+/* ------------------------------------------------------------------ CLIP text tower handle (the `text_encoder` of both pipelines)
+ * transformers' CLIPTextModel / CLIPTextModelWithProjection behind `pipeline.text_encoder(ids)` (stable_diffusion.py _encode_prompt,
+ * ddim_inversion.py, custom_pipeline.py _get_clip_prompt_embeds) as one graph of gfx950 kernels per call: SD-v1.5's CLIP-L, SD-v2.1's OpenCLIP-H,
+ * SD3's CLIP-L and CLIP-bigG.  THIRD-PARTY network, restated from its published definition with that class's state-dict keys (csrc/clip.hip);
+ * tests/clip_ref.py is the yardstick and tests/test_clip_ref.py holds it to transformers. */
+typedef struct univst_clip univst_clip;
+typedef struct {
+    int vocab_size;                 /* 49408 */
+    int hidden_size;                /* 768 / 1024 / 1280: num_heads * 64 */
+    int intermediate_size;          /* 4 * hidden_size */
+    int num_layers;                 /* 12 / 23 / 32 */
+    int num_heads;                  /* hidden_size / 64 */
+    int max_positions;              /* 77 (<= 80) */
+    int hidden_act;                 /* 0: quick_gelu  x sigmoid(1.702 x);  1: gelu (exact, erf) */
+    float layer_norm_eps;           /* 1e-5 */
+    int projection_dim;             /* 0: no text_projection (CLIPTextModel) */
+    int eos_token_id;               /* 2: legacy pooling (the position of the largest id); else the first position holding this id, 0 if none */
+} univst_clip_cfg;
+/* refuses (before any launch) a head dim other than 64 and max_positions beyond 80 */
+int univst_clip_create(const univst_clip_cfg* cfg, univst_clip** out);
+int univst_clip_destroy(univst_clip* h);
+/* key = transformers state-dict name with or without one leading "text_model." ("text_model.encoder.layers.3.mlp.fc1.weight",
+ * "embeddings.token_embedding.weight", "text_projection.weight"); dtype 0 = fp16, 1 = fp32 */
+int univst_clip_load_tensor(univst_clip* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+/* checks every tensor the config calls for and derives the fused q|k|v weights (the attention scale 1/8 folded into the q rows) */
+int univst_clip_finalize(univst_clip* h, void* stream);
+/* ids int64 [B, S] (S <= max_positions; an id outside [0, vocab) is clamped) -> any of: last_hidden fp16 [B, S, C] (after final_layer_norm),
+ * hidden_states fp16 [L + 1, B, S, C] (the residual streams before final_layer_norm: embeddings, then every layer's output), pooled fp16
+ * [B, projection_dim or C] (text_embeds / pooler_output); NULL skips an output.  The first call at a (B, S) sizes the arena; later calls at that
+ * size neither allocate nor synchronise. */
+int univst_clip_encode(univst_clip* h, const int64_t* ids, int B, int S, void* last_hidden, void* hidden_states, void* pooled, void* stream);
+/* read-outs of a handle: "arena_high_water" (bytes), "splitk_bytes" (the split-K workspace the arena holds for the linears of the last (B, S)) */
+int univst_clip_query(univst_clip* h, const char* name, double* out);
+/* the tower's attention on its own (tests): qkv fp16 [B * S, 3 * heads * 64] = q | k | v rows, q already scaled by 1/8; causal softmax over
+ * the S <= 80 positions of each (batch, head) -> out fp16 [B * S, heads * 64] */
+int univst_clip_attention(const void* qkv, int B, int S, int heads, void* out, void* stream);
+
 /* ------------------------------------------------------------------ stand-alone operators (also used by tests) */
 /* Y[M,N] = X[M,K] W[N,K]^T + bias + residual; geglu != 0: the diffusers GEGLU projection (FeedForward net[0], attention.py:241) — writes the
  * N/2 columns x * gelu(gate), W / bias rows pre-interleaved: geglu = 1 in blocks of [16 x rows | 16 gate rows] (any K), geglu = 2 in the

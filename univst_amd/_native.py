@@ -21,6 +21,11 @@ class UnetCfg(C.Structure):
                 ("freq_shift", C.c_float)]
 
 
+class ClipCfg(C.Structure):
+    _fields_ = [("vocab_size", C.c_int), ("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
+                ("max_positions", C.c_int), ("hidden_act", C.c_int), ("layer_norm_eps", C.c_float), ("projection_dim", C.c_int), ("eos_token_id", C.c_int)]
+
+
 class VaeCfg(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("latent_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -81,6 +86,13 @@ SIGNATURES = {
     "univst_vae_finalize": (_I, [_P, _P]),
     "univst_vae_decode": (_I, [_P, _P, _L, _I, _I, _I, _P, _P]),
     "univst_vae_encode": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "univst_clip_create": (_I, [_P, C.POINTER(_P)]),
+    "univst_clip_destroy": (_I, [_P]),
+    "univst_clip_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),
+    "univst_clip_finalize": (_I, [_P, _P]),
+    "univst_clip_encode": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "univst_clip_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
+    "univst_clip_attention": (_I, [_P, _I, _I, _I, _P, _P]),
     "univst_raft_create": (_I, [C.POINTER(_P)]),
     "univst_raft_destroy": (_I, [_P]),
     "univst_raft_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),

@@ -12,6 +12,7 @@
 #include "unet.h"
 #include "vae.h"
 #include "raft.h"
+#include "clip.h"
 
 static thread_local char g_err[1024] = "";
 void uv_set_error(const char* fmt, ...) {
@@ -184,6 +185,50 @@ int univst_linear_gated(const void* X, int64_t ldx, const void* W, const void* b
 int univst_geglu_xres_permute(const void* in, void* out, int rows, int cols, void* s) {
     UV_REQUIRE(in && out, "geglu_xres_permute: null argument");
     return uv_launch_geglu_xres_permute(H(in), HM(out), rows, cols, S(s));
+}
+struct univst_clip {
+    Clip impl;
+};
+int univst_clip_create(const univst_clip_cfg* cfg, univst_clip** out) {
+    UV_REQUIRE(cfg && out, "clip_create: null argument");
+    UV_RUN(uv_clip_check_cfg(*cfg));
+    univst_clip* h = new (std::nothrow) univst_clip();
+    UV_REQUIRE(h, "clip_create: out of host memory");
+    h->impl.cfg = *cfg;
+    *out = h;
+    return UV_OK;
+}
+int univst_clip_destroy(univst_clip* h) {
+    delete h;
+    return UV_OK;
+}
+int univst_clip_load_tensor(univst_clip* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
+}
+int univst_clip_finalize(univst_clip* h, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.finalize(S(s));
+}
+int univst_clip_encode(univst_clip* h, const int64_t* ids, int B, int Sq, void* last_hidden, void* hidden_states, void* pooled, void* s) {
+    UV_REQUIRE(h && ids, "clip_encode: null argument");
+    return h->impl.encode(ids, B, Sq, HM(last_hidden), HM(hidden_states), HM(pooled), S(s));
+}
+int univst_clip_query(univst_clip* h, const char* name, double* out) {
+    UV_REQUIRE(h && name && out, "clip_query: null argument");
+    if (!strcmp(name, "arena_high_water")) {
+        *out = (double)h->impl.arena.high_water;
+        return UV_OK;
+    }
+    if (!strcmp(name, "splitk_bytes")) {
+        *out = (double)h->impl.splitk_bytes;
+        return UV_OK;
+    }
+    uv_set_error("clip_query: unknown quantity '%s'", name);
+    return UV_ERR_ARG;
+}
+int univst_clip_attention(const void* qkv, int B, int Sq, int heads, void* out, void* s) {
+    return uv_launch_clip_attention(H(qkv), B, Sq, heads, HM(out), S(s));
 }
 struct univst_vae {
     Vae impl;

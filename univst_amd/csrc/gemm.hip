@@ -1376,7 +1376,7 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const half_t* __restr
 
 }  // namespace
 
-static int uv_num_cus() {
+int uv_num_cus() {
     static int n = 0;
     if (n == 0) {
         int dev = 0;

@@ -167,6 +167,7 @@ int uv_attention_plan_text(const AttnParams& p, char* buf, int n);
 std::string uv_gemm_plan_symbols();          // ';'-joined keys of the launch tables
 std::string uv_attention_plan_symbols();
 
+int uv_num_cus();                            // compute units of the current device: the `ncu` uv_launch_gemm plans with
 int uv_launch_gemm(const GemmParams& p, int mode, hipStream_t stream);
 bool uv_linear_takes_big_direct(long M, int N, int K, long ldx = 0);
 // LayerNorm fold around a plain linear: may it emit the row statistics of its output / apply those of its input?  (256x320 direct path,

@@ -1,6 +1,8 @@
 """Shared pieces of the three SD-v1.5 command-line entry points (mirrors of src/sd/run_*_sd.py of the reference).
 
-CLIP (transformers) is a third-party model and stays a stock PyTorch-ROCm module; the SVD temporal VAE is LOADED through diffusers
+CLIP (transformers) is a third-party model: by default it stays a stock PyTorch-ROCm module, and ``UNIVST_TEXT_ENCODER=native`` runs
+its text tower on the native library instead (univst_amd.text.NativeCLIPText reads ``<model>/text_encoder`` itself; the tokenizer stays
+transformers').  The SVD temporal VAE is LOADED through diffusers
 (its checkpoint format and config) and then runs on the native library (univst_amd.vae.NativeTemporalVAE takes the stock module's state dict;
 round 5, SURVEY §8 f2 — ``UNIVST_VAE=stock`` keeps the diffusers module).  Both must be available locally — there is no hub access on the target
 boxes.  The UNet, the DDIM loops, the PnP injection, mask blending and AdaIN run in the native HIP library."""
@@ -9,11 +11,28 @@ import os
 import torch
 
 
+def load_text_encoder(pretrained_model_path, subfolder, weight_dtype, projected):
+    """``UNIVST_TEXT_ENCODER=native``: the CLIP text tower on the native library (fp16, read from the local ``<model>/<subfolder>`` directory without
+    importing the transformers model class).  Default ``stock``: transformers' CLIPTextModel / CLIPTextModelWithProjection, as the reference builds it."""
+    mode = os.environ.get("UNIVST_TEXT_ENCODER", "stock")
+    if mode not in ("stock", "native"):
+        raise ValueError(f"UNIVST_TEXT_ENCODER={mode!r}: 'stock' or 'native'")
+    if mode == "native":
+        if weight_dtype != torch.float16:
+            raise ValueError(f"UNIVST_TEXT_ENCODER=native computes in fp16 only; weight_dtype is {weight_dtype}")
+        if not os.path.isdir(os.path.join(pretrained_model_path, subfolder)):
+            raise FileNotFoundError(f"UNIVST_TEXT_ENCODER=native needs a local directory {os.path.join(pretrained_model_path, subfolder)}")
+        from ...text import NativeCLIPText
+        return NativeCLIPText.from_pretrained(pretrained_model_path, subfolder=subfolder)
+    from transformers import CLIPTextModel, CLIPTextModelWithProjection
+    return (CLIPTextModelWithProjection if projected else CLIPTextModel).from_pretrained(pretrained_model_path, subfolder=subfolder).requires_grad_(False)
+
+
 def build_pipeline(pretrained_model_path, weight_dtype=torch.float16, vae_path="stabilityai/stable-video-diffusion-img2vid"):
     """The objects run_*_sd.py build (src/sd/run_video_style_transfer_sd.py:30-47).  diffusers is needed only where a local directory cannot be read
     without it: the VAE loads natively from ``<vae_path>/vae`` (config.json + safetensors / bin) when that is a directory, and the DDIM scheduler
     is the native one (same ``from_pretrained(path, subfolder="scheduler")``) when diffusers is absent."""
-    from transformers import CLIPTextModel, CLIPTokenizer
+    from transformers import CLIPTokenizer
     from ...backbones.video_diffusion_sd.models.unet_3d_condition import UNetPseudo3DConditionModel
     from ...backbones.video_diffusion_sd.pipelines.stable_diffusion import SpatioTemporalStableDiffusionPipeline
     from ...vae import NativeTemporalVAE
@@ -22,7 +41,7 @@ def build_pipeline(pretrained_model_path, weight_dtype=torch.float16, vae_path="
     except ImportError:
         from ...schedulers import DDIMScheduler
     tokenizer = CLIPTokenizer.from_pretrained(pretrained_model_path, subfolder="tokenizer")
-    text_encoder = CLIPTextModel.from_pretrained(pretrained_model_path, subfolder="text_encoder").requires_grad_(False)
+    text_encoder = load_text_encoder(pretrained_model_path, "text_encoder", weight_dtype, projected=False)
     vae = None
     stock = os.environ.get("UNIVST_VAE", "native") == "stock"
     if not stock and weight_dtype != torch.float16:

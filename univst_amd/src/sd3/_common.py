@@ -1,7 +1,8 @@
 """Shared pieces of the three SD3 / SD3.5 command-line entry points (mirrors of src/sd3/run_*_sd3.py of the reference).
 
 The CLIP / T5 text encoders (transformers) and the VAE (diffusers AutoencoderKL) are third-party models and stay stock
-PyTorch-ROCm modules; they must be available locally — there is no hub access on the target boxes.  The MM-DiT, the processors, the
+PyTorch-ROCm modules (``UNIVST_TEXT_ENCODER=native`` runs the two CLIP towers on the native library, univst_amd.text.NativeCLIPText; T5 stays
+stock); they must be available locally — there is no hub access on the target boxes.  The MM-DiT, the processors, the
 rectified-flow inversions and the transfer loop run on the native HIP library."""
 import json
 import os
@@ -31,7 +32,8 @@ def load_transformer(pretrained_model_path, weight_dtype=torch.float16):
 
 
 def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
-    from transformers import CLIPTextModelWithProjection, CLIPTokenizer, T5EncoderModel, T5TokenizerFast
+    from transformers import CLIPTokenizer, T5EncoderModel, T5TokenizerFast
+    from ..sd._common import load_text_encoder
     try:
         from diffusers import AutoencoderKL, FlowMatchEulerDiscreteScheduler
     except ImportError as e:  # pragma: no cover
@@ -43,9 +45,10 @@ def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
     transformer = load_transformer(pretrained_model_path, weight_dtype)
     transformer.set_attn_processor({n: CrossFrameProcessor() for n in transformer.attn_processors})      # run_*_sd3.py:58-69
     enc = lambda cls, name: sub(cls, name).requires_grad_(False).to(weight_dtype).cuda()         # noqa: E731
+    clip = lambda name: load_text_encoder(pretrained_model_path, name, weight_dtype, projected=True).to(weight_dtype).cuda()      # noqa: E731
     return CustomStableDiffusion3Pipeline(
         tokenizer=sub(CLIPTokenizer, "tokenizer"), tokenizer_2=sub(CLIPTokenizer, "tokenizer_2"), tokenizer_3=sub(T5TokenizerFast, "tokenizer_3"),
-        text_encoder=enc(CLIPTextModelWithProjection, "text_encoder"), text_encoder_2=enc(CLIPTextModelWithProjection, "text_encoder_2"),
+        text_encoder=clip("text_encoder"), text_encoder_2=clip("text_encoder_2"),
         text_encoder_3=enc(T5EncoderModel, "text_encoder_3"), vae=enc(AutoencoderKL, "vae"), transformer=transformer,
         scheduler=sub(FlowMatchEulerDiscreteScheduler, "scheduler"))
 

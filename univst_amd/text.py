@@ -1,0 +1,181 @@
+"""The CLIP text tower behind the pipelines' ``text_encoder`` call sites, on the native library.
+
+``NativeCLIPText`` stands where the reference keeps transformers' ``CLIPTextModel`` (SD-v1.5 / v2.1: src/sd/run_*_sd.py, called at
+pipelines/stable_diffusion.py _encode_prompt and inversion_tools/ddim_inversion.py) or ``CLIPTextModelWithProjection`` (SD3 / SD3.5: both CLIP towers,
+pipelines/custom_pipeline.py _get_clip_prompt_embeds): ``enc(ids)[0]``, ``enc(ids, output_hidden_states=True).hidden_states[-2]``, ``.config``,
+``.dtype``, ``.device``, ``.to(...)``.  It takes that class's state dict unchanged — keys with or without the ``text_model.`` prefix — and runs one
+C-ABI call per encode (univst_clip_*, csrc/clip.hip).  The network is third-party: restated from its published definition; tests/clip_ref.py is the
+yardstick, held to transformers by tests/test_clip_ref.py.  The tokenizers stay transformers' (host code)."""
+import ctypes as C
+import types
+
+import torch
+
+from . import _native
+
+DEFAULT_CONFIG = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
+                      max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5, projection_dim=768, eos_token_id=2)
+_ACTS = {"quick_gelu": 0, "gelu": 1}
+
+
+class CLIPTextOutput:
+    """what the call sites read of transformers' BaseModelOutputWithPooling / CLIPTextModelOutput: attributes, and ``out[0]`` = the first field
+    (last_hidden_state for the plain model, text_embeds for the projected one)"""
+
+    def __init__(self, fields):
+        self._fields = [(k, v) for k, v in fields if v is not None]
+        for k, v in fields:
+            setattr(self, k, v)
+
+    def to_tuple(self):
+        return tuple(v for _, v in self._fields)
+
+    def __getitem__(self, i):
+        return dict(self._fields)[i] if isinstance(i, str) else self.to_tuple()[i]
+
+    def __len__(self):
+        return len(self._fields)
+
+
+class NativeCLIPText:
+    def __init__(self, state_dict, config=None, with_projection=None, device="cuda"):
+        cfg = dict(DEFAULT_CONFIG)
+        if config is not None:
+            get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+            has = (lambda k: k in config) if isinstance(config, dict) else (lambda k: hasattr(config, k))
+            cfg.update({k: get(k) for k in DEFAULT_CONFIG if has(k) and get(k) is not None})
+        if with_projection is None:
+            with_projection = "text_projection.weight" in state_dict
+        if cfg["hidden_act"] not in _ACTS:
+            raise ValueError(f"NativeCLIPText: hidden_act {cfg['hidden_act']!r} (the native tower has quick_gelu and gelu)")
+        self.with_projection = bool(with_projection)
+        self.config = types.SimpleNamespace(use_attention_mask=False, **cfg)
+        self.device = torch.device(device)
+        lib = _native.load()
+        c = _native.ClipCfg(cfg["vocab_size"], cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
+                            cfg["max_position_embeddings"], _ACTS[cfg["hidden_act"]], cfg["layer_norm_eps"],
+                            cfg["projection_dim"] if self.with_projection else 0, cfg["eos_token_id"])
+        h = C.c_void_p()
+        _native.check(lib.univst_clip_create(C.byref(c), C.byref(h)), "clip_create")
+        self._h = h
+        st = _native.stream_ptr()
+        for k, v in state_dict.items():
+            if not torch.is_tensor(v) or not v.is_floating_point():       # (old checkpoints carry embeddings.position_ids, an int64 buffer)
+                continue
+            if k == "text_projection.weight" and not self.with_projection:
+                continue
+            t = v.detach().to(device=device)
+            t = t.to(torch.float16 if t.dtype not in (torch.float16, torch.float32) else t.dtype).contiguous()
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            _native.check(lib.univst_clip_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
+                          f"clip_load_tensor({k})")
+        _native.check(lib.univst_clip_finalize(h, st), "clip_finalize")
+        torch.cuda.current_stream().synchronize()
+
+    @classmethod
+    def from_module(cls, m, device="cuda"):
+        """a loaded transformers CLIPTextModel / CLIPTextModelWithProjection"""
+        return cls(m.state_dict(), config=m.config, with_projection=hasattr(m, "text_projection"), device=device)
+
+    from_state_dict = classmethod(lambda cls, sd, config=None, with_projection=None, device="cuda": cls(sd, config, with_projection, device))
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder="text_encoder", device="cuda", **_):
+        """Load a transformers-format text-encoder directory WITHOUT transformers: ``<path>/<subfolder>/config.json`` + ``model.safetensors`` /
+        ``model.fp16.safetensors`` / ``pytorch_model.bin`` — what ``CLIPTextModel.from_pretrained(path, subfolder="text_encoder")`` reads.  Local
+        directories only (the target boxes have no hub access); raises FileNotFoundError otherwise.  ``architectures`` (or ``_class_name``) of the
+        config says whether the tower carries text_projection."""
+        import json
+        import os
+        d = os.path.join(path, subfolder) if subfolder else path
+        cfg_file = os.path.join(d, "config.json")
+        if not os.path.isfile(cfg_file):
+            raise FileNotFoundError(f"{cfg_file} not found (NativeCLIPText.from_pretrained needs a local transformers-format directory)")
+        with open(cfg_file) as f:
+            raw = json.load(f)
+        if isinstance(raw.get("text_config"), dict):      # a CLIPConfig with the tower's settings nested
+            raw = {**raw, **raw["text_config"]}
+        names = list(raw.get("architectures") or []) + [raw.get("_class_name") or ""]
+        if not any(n in ("CLIPTextModel", "CLIPTextModelWithProjection") for n in names):
+            raise ValueError(f"{cfg_file}: architectures = {names}; the native text tower restates CLIPTextModel / CLIPTextModelWithProjection only")
+        for name in ("model.safetensors", "model.fp16.safetensors", "pytorch_model.bin"):
+            w = os.path.join(d, name)
+            if os.path.isfile(w):
+                if name.endswith(".safetensors"):
+                    from safetensors.torch import load_file
+                    sd = load_file(w)
+                else:
+                    sd = torch.load(w, map_location="cpu")
+                return cls(sd, config=raw, with_projection="CLIPTextModelWithProjection" in names, device=device)
+        raise FileNotFoundError(f"no model.safetensors / model.fp16.safetensors / pytorch_model.bin under {d}")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                _native.load().univst_clip_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    # ---- what the call sites touch of an nn.Module
+    @property
+    def dtype(self):
+        return torch.float16
+
+    def to(self, *a, **k):
+        return self
+
+    def cuda(self, *a, **k):
+        return self
+
+    def requires_grad_(self, *a, **k):
+        return self
+
+    def eval(self):
+        return self
+
+    def query(self, name):
+        """read-outs of the handle (include/univst.h ``univst_clip_query``): ``arena_high_water``, ``splitk_bytes``"""
+        out = C.c_double()
+        _native.check(_native.load().univst_clip_query(self._h, name.encode(), C.byref(out)), f"clip_query({name})")
+        return int(out.value)
+
+    def arena_high_water(self):
+        return self.query("arena_high_water")
+
+    def _check(self, t, what):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"NativeCLIPText.{what}: the native text encoder runs on the GPU only (no CPU / eager fallback); got "
+                               f"{'a ' + str(t.device) + ' tensor' if torch.is_tensor(t) else type(t).__name__}")
+        return t
+
+    @torch.no_grad()
+    def __call__(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=True, **_):
+        ids = self._check(input_ids, "__call__")
+        if ids.dim() != 2 or ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"NativeCLIPText: input_ids must be an integer tensor [B, S], got {ids.dtype} {tuple(ids.shape)}")
+        if attention_mask is not None and not bool((attention_mask != 0).all()):
+            raise NotImplementedError("NativeCLIPText: a padding attention_mask is not implemented (no UniVST configuration sets use_attention_mask)")
+        ids = ids.to(torch.int64).contiguous()
+        B, S = ids.shape
+        cfg = self.config
+        if S < 1 or S > cfg.max_position_embeddings:
+            raise ValueError(f"NativeCLIPText: sequence length {S} exceeds max_position_embeddings {cfg.max_position_embeddings}")
+        lo, hi = int(ids.min()), int(ids.max())       # one range check per call; the kernel clamps regardless
+        if lo < 0 or hi >= cfg.vocab_size:
+            raise IndexError(f"NativeCLIPText: input id {lo if lo < 0 else hi} is outside the vocabulary [0, {cfg.vocab_size})")
+        Cw, L = cfg.hidden_size, cfg.num_hidden_layers
+        last = torch.empty(B, S, Cw, device=ids.device, dtype=torch.float16)
+        hs = torch.empty(L + 1, B, S, Cw, device=ids.device, dtype=torch.float16) if output_hidden_states else None
+        pooled = torch.empty(B, cfg.projection_dim if self.with_projection else Cw, device=ids.device, dtype=torch.float16)
+        _native.check(_native.load().univst_clip_encode(self._h, _native.ptr(ids), B, S, _native.ptr(last), _native.ptr(hs), _native.ptr(pooled),
+                                                        _native.stream_ptr()), "clip_encode")
+        hidden = tuple(hs.unbind(0)) if hs is not None else None
+        if self.with_projection:
+            out = CLIPTextOutput([("text_embeds", pooled), ("last_hidden_state", last), ("hidden_states", hidden)])
+        else:
+            out = CLIPTextOutput([("last_hidden_state", last), ("pooler_output", pooled), ("hidden_states", hidden)])
+        return out if return_dict else out.to_tuple()
+
+    forward = __call__

@@ -239,6 +239,45 @@ int univst_clip_query(univst_clip* h, const char* name, double* out);
  * the S <= 80 positions of each (batch, head) -> out fp16 [B * S, heads * 64] */
 int univst_clip_attention(const void* qkv, int B, int S, int heads, void* out, void* stream);
 
+/* ------------------------------------------------------------------ T5 encoder handle (the `text_encoder_3` of the SD3 / SD3.5 pipeline)
+ * transformers' T5EncoderModel (encoder stack only, v1.1 gated-gelu form: T5 v1.1-XXL) behind `pipeline.text_encoder_3(ids)[0]`
+ * (custom_pipeline.py encode_prompt) as one graph of gfx950 kernels per call.  THIRD-PARTY network, restated from its published definition with
+ * that class's state-dict keys (csrc/t5.hip); tests/t5_ref.py is the yardstick and tests/test_t5_ref.py holds it to transformers.  The residual
+ * stream is fp32 (T5's outgrows the fp16 range); norms write fp16, linears run fp16 with fp32 accumulation. */
+typedef struct univst_t5 univst_t5;
+typedef struct {
+    int vocab_size;                 /* 32128 */
+    int d_model;                    /* 4096 (a multiple of 8) */
+    int d_ff;                       /* 10240 (a multiple of 8); feed_forward_proj = "gated-gelu": wi_0 (gelu_new) * wi_1, then wo */
+    int num_layers;                 /* 24 */
+    int num_heads;                  /* 64; num_heads * d_kv may differ from d_model */
+    int d_kv;                       /* 64: the only head dim the attention kernel has */
+    int num_buckets;                /* 32: relative_attention_num_buckets */
+    int max_distance;               /* 128: relative_attention_max_distance */
+    float layer_norm_eps;           /* 1e-6 */
+} univst_t5_cfg;
+/* refuses (before any launch, naming the field) d_kv other than 64, widths that are no multiple of 8, fewer than 4 buckets */
+int univst_t5_create(const univst_t5_cfg* cfg, univst_t5** out);
+int univst_t5_destroy(univst_t5* h);
+/* key = transformers state-dict name ("encoder.block.3.layer.1.DenseReluDense.wi_0.weight", "encoder.final_layer_norm.weight",
+ * "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"); the tied embedding loads as "shared.weight" or
+ * "encoder.embed_tokens.weight" (either or both: one copy is kept); dtype 0 = fp16, 1 = fp32 */
+int univst_t5_load_tensor(univst_t5* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+/* checks every tensor the config calls for and derives the fused q|k|v and wi_0|wi_1 weights and the per-head bias table [heads][delta + 511] */
+int univst_t5_finalize(univst_t5* h, void* stream);
+/* ids int64 [B, S] (1 <= S <= 512; an id outside [0, vocab) is clamped) -> last_hidden fp16 [B, S, d_model] (after final_layer_norm).  The first
+ * call at a (B, S) sizes the arena; later calls at that size neither allocate nor synchronise. */
+int univst_t5_encode(univst_t5* h, const int64_t* ids, int B, int S, void* last_hidden, void* stream);
+/* read-outs of a handle: "arena_high_water" (bytes), "splitk_bytes" (the split-K workspace the arena holds for the linears of the last (B, S)),
+ * "weight_bytes" (loaded tensors plus the fused copies and the bias table) */
+int univst_t5_query(univst_t5* h, const char* name, double* out);
+/* the encoder's attention on its own (tests): qkv fp16 [B * S, 3 * heads * 64] = q | k | v rows (no scaling is applied), bias_table fp32
+ * [heads][1023] indexed by (key position - query position) + 511; bidirectional softmax over the S <= 512 positions of each (batch, head)
+ * -> out fp16 [B * S, heads * 64] */
+int univst_t5_attention(const void* qkv, const float* bias_table, int B, int S, int heads, void* out, void* stream);
+/* host only (no GPU): transformers' T5Attention._relative_position_bucket (bidirectional) for the deltas -(n-1) .. n-1 -> out[2n - 1] */
+int univst_debug_t5_buckets(int num_buckets, int max_distance, int n, int* out);
+
 /* ------------------------------------------------------------------ stand-alone operators (also used by tests) */
 /* Y[M,N] = X[M,K] W[N,K]^T + bias + residual; geglu != 0: the diffusers GEGLU projection (FeedForward net[0], attention.py:241) — writes the
  * N/2 columns x * gelu(gate), W / bias rows pre-interleaved: geglu = 1 in blocks of [16 x rows | 16 gate rows] (any K), geglu = 2 in the

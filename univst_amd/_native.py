@@ -26,6 +26,11 @@ class ClipCfg(C.Structure):
                 ("max_positions", C.c_int), ("hidden_act", C.c_int), ("layer_norm_eps", C.c_float), ("projection_dim", C.c_int), ("eos_token_id", C.c_int)]
 
 
+class T5Cfg(C.Structure):
+    _fields_ = [("vocab_size", C.c_int), ("d_model", C.c_int), ("d_ff", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int), ("d_kv", C.c_int),
+                ("num_buckets", C.c_int), ("max_distance", C.c_int), ("layer_norm_eps", C.c_float)]
+
+
 class VaeCfg(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("latent_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -93,6 +98,14 @@ SIGNATURES = {
     "univst_clip_encode": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "univst_clip_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
     "univst_clip_attention": (_I, [_P, _I, _I, _I, _P, _P]),
+    "univst_t5_create": (_I, [_P, C.POINTER(_P)]),
+    "univst_t5_destroy": (_I, [_P]),
+    "univst_t5_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),
+    "univst_t5_finalize": (_I, [_P, _P]),
+    "univst_t5_encode": (_I, [_P, _P, _I, _I, _P, _P]),
+    "univst_t5_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
+    "univst_t5_attention": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "univst_debug_t5_buckets": (_I, [_I, _I, _I, C.POINTER(_I)]),
     "univst_raft_create": (_I, [C.POINTER(_P)]),
     "univst_raft_destroy": (_I, [_P]),
     "univst_raft_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),

@@ -13,6 +13,7 @@
 #include "vae.h"
 #include "raft.h"
 #include "clip.h"
+#include "t5.h"
 
 static thread_local char g_err[1024] = "";
 void uv_set_error(const char* fmt, ...) {
@@ -230,6 +231,55 @@ int univst_clip_query(univst_clip* h, const char* name, double* out) {
 int univst_clip_attention(const void* qkv, int B, int Sq, int heads, void* out, void* s) {
     return uv_launch_clip_attention(H(qkv), B, Sq, heads, HM(out), S(s));
 }
+struct univst_t5 {
+    T5 impl;
+};
+int univst_t5_create(const univst_t5_cfg* cfg, univst_t5** out) {
+    UV_REQUIRE(cfg && out, "t5_create: null argument");
+    UV_RUN(uv_t5_check_cfg(*cfg));
+    univst_t5* h = new (std::nothrow) univst_t5();
+    UV_REQUIRE(h, "t5_create: out of host memory");
+    h->impl.cfg = *cfg;
+    *out = h;
+    return UV_OK;
+}
+int univst_t5_destroy(univst_t5* h) {
+    delete h;
+    return UV_OK;
+}
+int univst_t5_load_tensor(univst_t5* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
+}
+int univst_t5_finalize(univst_t5* h, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.finalize(S(s));
+}
+int univst_t5_encode(univst_t5* h, const int64_t* ids, int B, int Sq, void* last_hidden, void* s) {
+    UV_REQUIRE(h && ids && last_hidden, "t5_encode: null argument");
+    return h->impl.encode(ids, B, Sq, HM(last_hidden), S(s));
+}
+int univst_t5_query(univst_t5* h, const char* name, double* out) {
+    UV_REQUIRE(h && name && out, "t5_query: null argument");
+    if (!strcmp(name, "arena_high_water")) {
+        *out = (double)h->impl.arena.high_water;
+        return UV_OK;
+    }
+    if (!strcmp(name, "splitk_bytes")) {
+        *out = (double)h->impl.splitk_bytes;
+        return UV_OK;
+    }
+    if (!strcmp(name, "weight_bytes")) {
+        *out = h->impl.weight_bytes();
+        return UV_OK;
+    }
+    uv_set_error("t5_query: unknown quantity '%s'", name);
+    return UV_ERR_ARG;
+}
+int univst_t5_attention(const void* qkv, const float* bias_table, int B, int Sq, int heads, void* out, void* s) {
+    return uv_launch_t5_attention(H(qkv), bias_table, B, Sq, heads, HM(out), S(s));
+}
+int univst_debug_t5_buckets(int num_buckets, int max_distance, int n, int* out) { return uv_t5_bucket_table(num_buckets, max_distance, n, out); }
 struct univst_vae {
     Vae impl;
 };

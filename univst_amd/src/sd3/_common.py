@@ -1,8 +1,8 @@
 """Shared pieces of the three SD3 / SD3.5 command-line entry points (mirrors of src/sd3/run_*_sd3.py of the reference).
 
 The CLIP / T5 text encoders (transformers) and the VAE (diffusers AutoencoderKL) are third-party models and stay stock
-PyTorch-ROCm modules (``UNIVST_TEXT_ENCODER=native`` runs the two CLIP towers on the native library, univst_amd.text.NativeCLIPText; T5 stays
-stock); they must be available locally — there is no hub access on the target boxes.  The MM-DiT, the processors, the
+PyTorch-ROCm modules by default (``UNIVST_TEXT_ENCODER=native`` runs the two CLIP towers on the native library, univst_amd.text.NativeCLIPText, and
+``UNIVST_T5_ENCODER=native`` the T5 encoder, univst_amd.text.NativeT5Encoder); they must be available locally — there is no hub access on the target boxes.  The MM-DiT, the processors, the
 rectified-flow inversions and the transfer loop run on the native HIP library."""
 import json
 import os
@@ -31,8 +31,26 @@ def load_transformer(pretrained_model_path, weight_dtype=torch.float16):
     return model.half().cuda().requires_grad_(False)
 
 
+def load_t5_encoder(pretrained_model_path, subfolder, weight_dtype):
+    """``UNIVST_T5_ENCODER=native``: the T5 encoder on the native library (fp16 with an fp32 residual stream, read from the local
+    ``<model>/<subfolder>`` directory without importing the transformers model class).  Default ``stock``: transformers' T5EncoderModel, as the
+    reference builds it."""
+    mode = os.environ.get("UNIVST_T5_ENCODER", "stock")
+    if mode not in ("stock", "native"):
+        raise ValueError(f"UNIVST_T5_ENCODER={mode!r}: 'stock' or 'native'")
+    if mode == "native":
+        if weight_dtype != torch.float16:
+            raise ValueError(f"UNIVST_T5_ENCODER=native computes in fp16 only; weight_dtype is {weight_dtype}")
+        if not os.path.isdir(os.path.join(pretrained_model_path, subfolder)):
+            raise FileNotFoundError(f"UNIVST_T5_ENCODER=native needs a local directory {os.path.join(pretrained_model_path, subfolder)}")
+        from ...text import NativeT5Encoder
+        return NativeT5Encoder.from_pretrained(pretrained_model_path, subfolder=subfolder)
+    from transformers import T5EncoderModel
+    return T5EncoderModel.from_pretrained(pretrained_model_path, subfolder=subfolder).requires_grad_(False)
+
+
 def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
-    from transformers import CLIPTokenizer, T5EncoderModel, T5TokenizerFast
+    from transformers import CLIPTokenizer, T5TokenizerFast
     from ..sd._common import load_text_encoder
     try:
         from diffusers import AutoencoderKL, FlowMatchEulerDiscreteScheduler
@@ -49,7 +67,7 @@ def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
     return CustomStableDiffusion3Pipeline(
         tokenizer=sub(CLIPTokenizer, "tokenizer"), tokenizer_2=sub(CLIPTokenizer, "tokenizer_2"), tokenizer_3=sub(T5TokenizerFast, "tokenizer_3"),
         text_encoder=clip("text_encoder"), text_encoder_2=clip("text_encoder_2"),
-        text_encoder_3=enc(T5EncoderModel, "text_encoder_3"), vae=enc(AutoencoderKL, "vae"), transformer=transformer,
+        text_encoder_3=load_t5_encoder(pretrained_model_path, "text_encoder_3", weight_dtype).to(weight_dtype).cuda(), vae=enc(AutoencoderKL, "vae"), transformer=transformer,
         scheduler=sub(FlowMatchEulerDiscreteScheduler, "scheduler"))
 
 

@@ -173,6 +173,40 @@ int univst_vae_decode(univst_vae* h, const void* z, int64_t imgs, int num_frames
  * (mean | logvar; sampling stays with the caller, which owns the RNG) */
 int univst_vae_encode(univst_vae* h, const void* x, int64_t imgs, int H, int W, void* moments, void* stream);
 
+/* ------------------------------------------------------------------ plain AutoencoderKL handle (the `vae` of the SD3 / SD3.5 pipeline)
+ * diffusers' AutoencoderKL (DownEncoderBlock2D / UpDecoderBlock2D x 4, mid_block_add_attention) behind `pipeline.vae.decode / encode`
+ * (custom_pipeline.py decode path, inversion_tools/flow_inversion.py latent encoding; src/sd3/run_*_sd3.py load it from `<model>/vae`): the SD3 16-channel
+ * VAE, SD-v1.5's image VAE.  The layers of the temporal VAE without the temporal ones, on the same kernels.  THIRD-PARTY network, restated from its
+ * published definition with that class's state-dict names (csrc/vae.hip); tests/klvae_ref.py is the yardstick; parity unpinned.  All GroupNorm eps 1e-6.
+ *   attn_score_bytes (0: 128 MiB): bound on the fp16 score matrix of the one-head mid-block attention.  The query rows of a frame run in chunks of Qc rows
+ *       against all N = H/8 * W/8 keys, Qc the largest multiple of 128 (the GEMM row tile) with Qc * N * 2 <= attn_score_bytes, at least 128, at most N.
+ *   pass_bytes (0: 8 GiB): bound on the activation arena.  No layer couples images, so a call runs its batch in groups of the most images whose arena
+ *       need stays under it (at least one image; the last group may be smaller); the arena is sized from the group. */
+typedef struct univst_klvae univst_klvae;
+typedef struct {
+    int in_channels, out_channels, latent_channels;      /* 3, 3, 16 (SD3) / 4 (SD-v1.5); latent_channels a multiple of 4 */
+    int block_out_channels[4];                           /* 128, 256, 512, 512 (multiples of 8 and even multiples of norm_num_groups) */
+    int layers_per_block;                                /* 2 */
+    int norm_num_groups;                                 /* 32 */
+    int use_quant_conv, use_post_quant_conv;             /* SD3: 0, 0; SD-v1.5: 1, 1 */
+    int64_t attn_score_bytes, pass_bytes;
+} univst_klvae_cfg;
+int univst_klvae_create(const univst_klvae_cfg* cfg, univst_klvae** out);
+int univst_klvae_destroy(univst_klvae* h);
+/* key = diffusers state-dict name ("decoder.up_blocks.0.resnets.1.conv1.weight", "decoder.mid_block.attentions.0.to_q.weight", ...); the attention
+ * weights are [C, C] linears (univst_amd.vae.kl_tensors maps the query / key / value / proj_attn names and 1x1-conv shapes of old checkpoints) */
+int univst_klvae_load_tensor(univst_klvae* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+int univst_klvae_finalize(univst_klvae* h, void* stream);
+/* AutoencoderKL.decode(z).sample: z [imgs, latent, h, w] (already z / scaling_factor + shift_factor) -> out [imgs, out_channels, 8h, 8w]; h * w a multiple of 8 */
+int univst_klvae_decode(univst_klvae* h, const void* z, int64_t imgs, int lat_h, int lat_w, void* out, void* stream);
+/* AutoencoderKL.encode(x).latent_dist.parameters: x [imgs, in_channels, H, W] in [-1, 1] -> moments [imgs, 2*latent, H/8, W/8] (mean | logvar; the caller
+ * samples).  H, W multiples of 8, H/8 * W/8 a multiple of 8 */
+int univst_klvae_encode(univst_klvae* h, const void* x, int64_t imgs, int H, int W, void* moments, void* stream);
+/* read-outs of a handle: "arena_high_water" (bytes), "arena_bytes" (the arena's size = the need of the largest group so far: the supported way to size
+ * pass_bytes — run a group of g images once, read it, and give it as pass_bytes to get groups of g at that image size), "attn_chunks" (chunks per
+ * frame of the attention in the last call), "passes" (groups the last call ran its batch in) */
+int univst_klvae_query(univst_klvae* h, const char* name, double* out);
+
 /* ------------------------------------------------------------------ RAFT-large optical flow handle (the `flow_fn` of src/cal_optica_flow.py)
  * The flow estimator behind get_warp (cal_optica_flow.py:51-99) and the sliding-window smoother (stable_diffusion.py:731-747): torchvision's
  * raft_large as one graph of gfx950 kernels per image pair (12 flow updates, final flow only, eval mode).  THIRD-PARTY network, restated from its

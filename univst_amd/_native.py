@@ -36,6 +36,12 @@ class VaeCfg(C.Structure):
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
 
 
+class KlVaeCfg(C.Structure):
+    _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("latent_channels", C.c_int), ("block_out_channels", C.c_int * 4),
+                ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int), ("use_quant_conv", C.c_int), ("use_post_quant_conv", C.c_int),
+                ("attn_score_bytes", C.c_int64), ("pass_bytes", C.c_int64)]
+
+
 class PnP(C.Structure):
     _fields_ = [("registered", C.c_int), ("idx", C.c_int), ("eta1", C.c_float), ("eta2", C.c_float),
                 ("alpha", C.c_float), ("gamma", C.c_float)]
@@ -91,6 +97,13 @@ SIGNATURES = {
     "univst_vae_finalize": (_I, [_P, _P]),
     "univst_vae_decode": (_I, [_P, _P, _L, _I, _I, _I, _P, _P]),
     "univst_vae_encode": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "univst_klvae_create": (_I, [_P, C.POINTER(_P)]),
+    "univst_klvae_destroy": (_I, [_P]),
+    "univst_klvae_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),
+    "univst_klvae_finalize": (_I, [_P, _P]),
+    "univst_klvae_decode": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "univst_klvae_encode": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "univst_klvae_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
     "univst_clip_create": (_I, [_P, C.POINTER(_P)]),
     "univst_clip_destroy": (_I, [_P]),
     "univst_clip_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),

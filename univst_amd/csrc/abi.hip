@@ -318,6 +318,75 @@ int univst_vae_encode(univst_vae* h, const void* x, int64_t imgs, int Hh, int W,
     UV_REQUIRE(h && x && moments, "vae_encode: null argument");
     return h->impl.encode(H(x), imgs, Hh, W, HM(moments), S(s));
 }
+struct univst_klvae {
+    KlVae impl;
+};
+int univst_klvae_create(const univst_klvae_cfg* cfg, univst_klvae** out) {
+    UV_REQUIRE(cfg && out, "klvae_create: null argument");
+    UV_REQUIRE(cfg->norm_num_groups > 0 && cfg->layers_per_block >= 1 && cfg->in_channels >= 1 && cfg->in_channels <= 8 && cfg->out_channels >= 1 &&
+               cfg->out_channels <= 8, "klvae_create: bad config");
+    UV_REQUIRE(cfg->latent_channels >= 4 && cfg->latent_channels <= 64 && cfg->latent_channels % 4 == 0,
+               "klvae_create: latent_channels=%d: the moments' 2 x latent_channels must be a multiple of 8 (at most 128)", cfg->latent_channels);
+    UV_REQUIRE(cfg->attn_score_bytes >= 0 && cfg->pass_bytes >= 0, "klvae_create: negative budget");
+    for (int i = 0; i < 4; ++i) {
+        const int c = cfg->block_out_channels[i];
+        UV_REQUIRE(c > 0 && c % 8 == 0 && c % cfg->norm_num_groups == 0 && (c / cfg->norm_num_groups) % 2 == 0,
+                   "klvae_create: block_out_channels[%d]=%d must be a multiple of 8 and an even multiple of the group count", i, c);
+    }
+    univst_klvae* h = new (std::nothrow) univst_klvae();
+    UV_REQUIRE(h, "klvae_create: out of host memory");
+    h->impl.kcfg = *cfg;
+    univst_vae_cfg& b = h->impl.cfg;
+    b.in_channels = cfg->in_channels;
+    b.out_channels = cfg->out_channels;
+    b.latent_channels = cfg->latent_channels;
+    for (int i = 0; i < 4; ++i) b.block_out_channels[i] = cfg->block_out_channels[i];
+    b.layers_per_block = cfg->layers_per_block;
+    b.norm_num_groups = cfg->norm_num_groups;
+    *out = h;
+    return UV_OK;
+}
+int univst_klvae_destroy(univst_klvae* h) {
+    delete h;
+    return UV_OK;
+}
+int univst_klvae_load_tensor(univst_klvae* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
+}
+int univst_klvae_finalize(univst_klvae* h, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.finalize(S(s));
+}
+int univst_klvae_decode(univst_klvae* h, const void* z, int64_t imgs, int lat_h, int lat_w, void* out, void* s) {
+    UV_REQUIRE(h && z && out, "klvae_decode: null argument");
+    return h->impl.decode(H(z), imgs, lat_h, lat_w, HM(out), S(s));
+}
+int univst_klvae_encode(univst_klvae* h, const void* x, int64_t imgs, int Hh, int W, void* moments, void* s) {
+    UV_REQUIRE(h && x && moments, "klvae_encode: null argument");
+    return h->impl.encode(H(x), imgs, Hh, W, HM(moments), S(s));
+}
+int univst_klvae_query(univst_klvae* h, const char* name, double* out) {
+    UV_REQUIRE(h && name && out, "klvae_query: null argument");
+    if (!strcmp(name, "arena_high_water")) {
+        *out = (double)h->impl.arena.high_water;
+        return UV_OK;
+    }
+    if (!strcmp(name, "arena_bytes")) {
+        *out = (double)h->impl.arena.size;
+        return UV_OK;
+    }
+    if (!strcmp(name, "attn_chunks")) {
+        *out = (double)h->impl.attn_chunks;
+        return UV_OK;
+    }
+    if (!strcmp(name, "passes")) {
+        *out = (double)h->impl.passes;
+        return UV_OK;
+    }
+    uv_set_error("klvae_query: unknown quantity '%s'", name);
+    return UV_ERR_ARG;
+}
 struct univst_raft {
     Raft impl;
 };

@@ -98,6 +98,14 @@ __global__ __launch_bounds__(256) void v_time_conv_out_kernel(const half_t* __re
 
 }  // namespace
 
+// query rows per chunk of the one-head attention under a score budget: the largest multiple of the 128-row GEMM tile whose [Qc, N] fp16 scores fit,
+// at least one tile, at most N (the attention and the arena formula both size from it)
+long uv_vae_attn_chunk_rows(long score_bytes, long N) {
+    long Qc = score_bytes / (2L * N) / 128 * 128;
+    if (Qc < 128) Qc = 128;
+    return Qc > N ? N : Qc;
+}
+
 Vae::~Vae() {
     if (arena.base) (void)hipFree(arena.base);
 }
@@ -184,7 +192,8 @@ struct VFwd {
         return uv_launch_groupnorm(a.p, nullptr, a.C, 0, a.rows(), (int)rows_per_stat, u.cfg.norm_num_groups, eps, g, b, silu, out, gn_ws, s);
     }
     // 2-D conv on [imgs, H, W, C]; asym: the encoder's stride-2 conv (input padded at the bottom / right only)
-    int conv(const Act& a, const std::string& p, int Cout, int taps, int stride, int up, bool asym, const half_t* R, Act* out) {
+    // ldy > Cout (the plain VAE's post_quant_conv in front of a conv that reads channels padded to 8): rows of ldy halfs, the columns behind Cout zero
+    int conv(const Act& a, const std::string& p, int Cout, int taps, int stride, int up, bool asym, const half_t* R, Act* out, int ldy = 0) {
         GemmParams g;
         g.X = a.p;
         g.C1 = a.C;
@@ -215,11 +224,12 @@ struct VFwd {
         out->imgs = a.imgs;
         out->H = g.Ho;
         out->W = g.Wo;
-        out->C = Cout;
-        out->p = alloc(out->rows() * Cout);
+        out->C = ldy > Cout ? ldy : Cout;
+        out->p = alloc(out->rows() * out->C);
         if (!out->p) return UV_ERR_STATE;
+        if (out->C > Cout) UV_HIP(hipMemsetAsync(out->p, 0, (size_t)out->rows() * out->C * sizeof(half_t), s));
         g.Y = out->p;
-        g.ldy = Cout;
+        g.ldy = out->C;
         return uv_launch_gemm(g, 1, s);
     }
     // Conv3d (3,1,1) over the F frames of every pixel: the 3x1 tap geometry on (image rows = frames, image columns = pixels)
@@ -325,10 +335,15 @@ struct VFwd {
     // Numerics: the scaled scores of a frame are stored in fp16 between the QK^T GEMM and the row softmax (|ds| <= 2^-11 |s|: for logits of a few tens
     // that is the size of the error the fp16 q and k rows themselves carry — the reference runs this VAE in fp16 too, `vae.to(weight_dtype)`); the softmax
     // arithmetic and the PV accumulation are fp32.  A d = 512 flash kernel would avoid the N x N round trip; at 64 x 64 tokens the two GEMMs take 2 % of a decode.
-    int attention(const std::string& p, const Act& x, Act* out) {
+    // score_bytes > 0 (the plain VAE): the query rows of a frame go through in chunks of Qc rows against all N keys, Qc the largest multiple of the
+    // 128-row GEMM tile whose [Qc, N] fp16 scores fit the budget (at least one tile).  Every chunk sees every key, so a chunk's softmax rows are final:
+    // nothing is merged.  score_bytes == 0 (the temporal VAE): one chunk, the whole frame.
+    int attention(const std::string& p, const Act& x, Act* out, long score_bytes = 0, long* chunks = nullptr) {
         const int C = x.C, N = x.H * x.W;
         const long rows = x.rows();
         UV_REQUIRE(N % 8 == 0 && C % 8 == 0, "%s: %d tokens x %d channels", p.c_str(), N, C);
+        const long Qc = score_bytes > 0 ? uv_vae_attn_chunk_rows(score_bytes, N) : N;
+        if (chunks) *chunks = (N + Qc - 1) / Qc;
         half_t* gn = alloc(rows * C);
         if (!gn) return UV_ERR_STATE;
         UV_RUN(groupnorm(x, N, p + ".group_norm", 0, gn));
@@ -340,15 +355,19 @@ struct VFwd {
         UV_RUN(linear(gn, rows, C, wq, bq, C, q));
         UV_RUN(linear(gn, rows, C, wk, bk, C, k));
         UV_RUN(linear(gn, rows, C, wv, bv, C, v));
-        half_t *S = alloc((long)N * N), *vT = alloc((long)N * C);
+        half_t *S = alloc(Qc * N), *vT = alloc((long)N * C);
         if (!S || !vT) return UV_ERR_STATE;
         for (int f = 0; f < x.imgs; ++f) {
             const long o = (long)f * N * C;
-            UV_RUN(linear(q + o, N, C, k + o, nullptr, N, S));                              // scores [N, N] (already scaled: the scale rides on q)
-            hipLaunchKernelGGL(v_softmax_rows_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, S, (long)N, N);
-            hipLaunchKernelGGL(v_transpose_kernel, dim3((C + 31) / 32, (N + 31) / 32), dim3(256), 0, s, v + o, vT, N, C);
-            UV_LAUNCH_CHECK();
-            UV_RUN(linear(S, N, N, vT, nullptr, C, gn + o));                                 // O = P V  (gn is free by now)
+            for (long c0 = 0; c0 < N; c0 += Qc) {
+                const long qc = N - c0 < Qc ? N - c0 : Qc;                                      // the last chunk may be ragged (a multiple of 8 rows)
+                UV_RUN(linear(q + o + c0 * C, qc, C, k + o, nullptr, N, S));                    // scores [qc, N] (already scaled: the scale rides on q)
+                hipLaunchKernelGGL(v_softmax_rows_kernel, dim3((unsigned)((qc + 3) / 4)), dim3(256), 0, s, S, qc, N);
+                // V^T once per frame, behind the first chunk's softmax
+                if (c0 == 0) hipLaunchKernelGGL(v_transpose_kernel, dim3((C + 31) / 32, (N + 31) / 32), dim3(256), 0, s, v + o, vT, N, C);
+                UV_LAUNCH_CHECK();
+                UV_RUN(linear(S, qc, N, vT, nullptr, C, gn + o + c0 * C));                      // O = P V  (gn is free by now)
+            }
         }
         free(S);
         free(vT);
@@ -483,5 +502,168 @@ int Vae::encode(const half_t* xin, long imgs, int H, int Wd, half_t* moments, hi
     f.free(cur.p);
     UV_RUN(uv_launch_nhwc_to_ncfhw(nxt.p, 2 * cfg.latent_channels, moments, (int)imgs, 2 * cfg.latent_channels, 1, nxt.H * nxt.W, s));
     f.free(nxt.p);
+    return UV_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the plain AutoencoderKL (univst_klvae)
+// diffusers 0.35 AutoencoderKL (models/autoencoders/autoencoder_kl.py; vae.py Encoder / Decoder, unet_2d_blocks.py DownEncoderBlock2D / UpDecoderBlock2D /
+// UNetMidBlock2D with mid_block_add_attention) under that class's state-dict names — THIRD-PARTY, restated from the published definition; PARITY UNPINNED
+// (tests/klvae_ref.py is a second restatement).  The encoder is Vae::encode's (quant_conv only where the config has one); the decoder is
+//   [post_quant_conv 1x1] | conv_in | mid: resnet, 1-head attention, resnet | 4 x [layers_per_block + 1 ResnetBlock2D, nearest x2 + conv on the first three] |
+//   GroupNorm + SiLU + conv_out
+// with no temporal layer.  No layer couples images, so a call runs its batch in groups whose arena need stays under pass_bytes, and the attention's
+// score matrix is bounded by attn_score_bytes (VFwd::attention).
+size_t KlVae::need_bytes(long imgs, int H, int Wd) const {
+    // Vae::reserve's live set per image, with the score matrix bounded by the budget
+    const size_t rows = (size_t)imgs * H * Wd;
+    const size_t N = (size_t)(H / 8) * (Wd / 8);
+    const size_t Qc = (size_t)uv_vae_attn_chunk_rows(score_bytes(), (long)N);
+    const int* boc = cfg.block_out_channels;
+    const size_t wide = boc[0] > boc[1] ? boc[0] : boc[1];      // the widest tensor at the full resolution (a config may have its first width above its second)
+    return rows * wide * 2 * 5 + Qc * N * 2 + (size_t)imgs * N * cfg.block_out_channels[3] * 2 * 8 + (256u << 20);
+}
+
+long KlVae::group_of(long imgs, int H, int Wd) const {
+    const size_t budget = kcfg.pass_bytes > 0 ? (size_t)kcfg.pass_bytes : (size_t)8 << 30;
+    const size_t one = need_bytes(1, H, Wd), per = need_bytes(2, H, Wd) - one;      // the need is linear in the image count
+    long g = budget > one ? 1 + (long)((budget - one) / per) : 1;
+    return g < imgs ? g : imgs;
+}
+
+// z [imgs, latent, h, w] fp16 (already z / scaling_factor + shift_factor) -> out [imgs, out_channels, 8h, 8w] fp16
+int KlVae::decode(const half_t* z, long imgs, int h, int w, half_t* out, hipStream_t s) {
+    UV_REQUIRE(finalized, "klvae_decode: call univst_klvae_finalize after loading weights");
+    UV_REQUIRE(imgs > 0 && h > 0 && w > 0, "klvae_decode: %ld images of %d x %d latents", imgs, h, w);
+    UV_REQUIRE(((long)h * w) % 8 == 0, "klvae_decode: %d x %d latents: the token count of the mid-block attention must be a multiple of 8", h, w);
+    const long g = group_of(imgs, h * 8, w * 8);
+    UV_RUN(arena.ensure(need_bytes(g, h * 8, w * 8)));
+    clear_missing();
+    passes = 0;
+    for (long i0 = 0; i0 < imgs; i0 += g, ++passes) {
+        const long n = imgs - i0 < g ? imgs - i0 : g;
+        UV_RUN(decode_pass(z + i0 * cfg.latent_channels * h * w, n, h, w, out + i0 * cfg.out_channels * 64L * h * w, s));
+    }
+    return UV_OK;
+}
+
+int KlVae::decode_pass(const half_t* z, long imgs, int h, int w, half_t* out, hipStream_t s) {
+    const int* boc = cfg.block_out_channels;
+    VFwd f{*this, s};
+    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
+    if (!f.gn_ws) return UV_ERR_STATE;
+    const int Lp = (cfg.latent_channels + 7) / 8 * 8;
+    Act cur{f.alloc(imgs * h * w * Lp), (int)imgs, h, w, Lp}, nxt;
+    if (!cur.p) return UV_ERR_STATE;
+    UV_RUN(uv_launch_ncfhw_to_nhwc(z, cur.p, (int)imgs, cfg.latent_channels, 1, h * w, Lp, s));
+    if (kcfg.use_post_quant_conv) {
+        UV_RUN(f.conv(cur, "post_quant_conv", cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt, Lp));
+        f.free(cur.p);
+        cur = nxt;
+    }
+    UV_RUN(f.conv(cur, "decoder.conv_in", boc[3], 9, 1, 0, false, nullptr, &nxt));
+    f.free(cur.p);
+    cur = nxt;
+    // UNetMidBlock2D: resnets[0], then (attention, resnets[1])
+    UV_RUN(f.resnet2d("decoder.mid_block.resnets.0", cur, boc[3], &nxt));
+    f.free(cur.p);
+    cur = nxt;
+    UV_RUN(f.attention("decoder.mid_block.attentions.0", cur, &nxt, score_bytes(), &attn_chunks));
+    f.free(cur.p);
+    cur = nxt;
+    UV_RUN(f.resnet2d("decoder.mid_block.resnets.1", cur, boc[3], &nxt));
+    f.free(cur.p);
+    cur = nxt;
+    for (int b = 0; b < 4; ++b) {
+        const int Cout = boc[3 - b];
+        const std::string up = "decoder.up_blocks." + std::to_string(b);
+        for (int l = 0; l < cfg.layers_per_block + 1; ++l) {
+            UV_RUN(f.resnet2d(up + ".resnets." + std::to_string(l), cur, Cout, &nxt));
+            f.free(cur.p);
+            cur = nxt;
+        }
+        if (b < 3) {
+            UV_RUN(f.conv(cur, up + ".upsamplers.0.conv", Cout, 9, 1, 1, false, nullptr, &nxt));
+            f.free(cur.p);
+            cur = nxt;
+        }
+    }
+    half_t* n = f.alloc(cur.rows() * cur.C);
+    if (!n) return UV_ERR_STATE;
+    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "decoder.conv_norm_out", 1, n));
+    Act na{n, cur.imgs, cur.H, cur.W, cur.C};
+    f.free(cur.p);
+    UV_RUN(f.conv(na, "decoder.conv_out", cfg.out_channels, 9, 1, 0, false, nullptr, &nxt));
+    f.free(n);
+    UV_RUN(uv_launch_nhwc_to_ncfhw(nxt.p, cfg.out_channels, out, (int)imgs, cfg.out_channels, 1, nxt.H * nxt.W, s));
+    f.free(nxt.p);
+    f.free(f.gn_ws);
+    return UV_OK;
+}
+
+// x [imgs, in_channels, H, W] fp16 in [-1, 1] -> moments [imgs, 2*latent, H/8, W/8] fp16 (mean | logvar; the caller samples)
+int KlVae::encode(const half_t* xin, long imgs, int H, int Wd, half_t* moments, hipStream_t s) {
+    UV_REQUIRE(finalized, "klvae_encode: call univst_klvae_finalize after loading weights");
+    UV_REQUIRE(imgs > 0 && H > 0 && Wd > 0 && H % 8 == 0 && Wd % 8 == 0, "klvae_encode: %ld images of %d x %d (multiples of 8)", imgs, H, Wd);
+    UV_REQUIRE(((long)(H / 8) * (Wd / 8)) % 8 == 0, "klvae_encode: %d x %d pixels: the token count of the mid-block attention (H/8 * W/8) must be a multiple of 8", H, Wd);
+    const long g = group_of(imgs, H, Wd);
+    UV_RUN(arena.ensure(need_bytes(g, H, Wd)));
+    clear_missing();
+    passes = 0;
+    for (long i0 = 0; i0 < imgs; i0 += g, ++passes) {
+        const long n = imgs - i0 < g ? imgs - i0 : g;
+        UV_RUN(encode_pass(xin + i0 * cfg.in_channels * H * Wd, n, H, Wd, moments + i0 * 2 * cfg.latent_channels * (H / 8) * (Wd / 8), s));
+    }
+    return UV_OK;
+}
+
+int KlVae::encode_pass(const half_t* xin, long imgs, int H, int Wd, half_t* moments, hipStream_t s) {
+    const int* boc = cfg.block_out_channels;
+    VFwd f{*this, s};
+    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
+    if (!f.gn_ws) return UV_ERR_STATE;
+    const int Ip = (cfg.in_channels + 7) / 8 * 8;
+    Act x{f.alloc(imgs * H * Wd * Ip), (int)imgs, H, Wd, Ip};
+    if (!x.p) return UV_ERR_STATE;
+    UV_RUN(uv_launch_ncfhw_to_nhwc(xin, x.p, (int)imgs, cfg.in_channels, 1, H * Wd, Ip, s));
+    Act cur, nxt;
+    UV_RUN(f.conv(x, "encoder.conv_in", boc[0], 9, 1, 0, false, nullptr, &cur));
+    f.free(x.p);
+    for (int b = 0; b < 4; ++b) {
+        const std::string down = "encoder.down_blocks." + std::to_string(b);
+        for (int l = 0; l < cfg.layers_per_block; ++l) {
+            UV_RUN(f.resnet2d(down + ".resnets." + std::to_string(l), cur, boc[b], &nxt));
+            f.free(cur.p);
+            cur = nxt;
+        }
+        if (b < 3) {
+            UV_RUN(f.conv(cur, down + ".downsamplers.0.conv", boc[b], 9, 2, 0, true, nullptr, &nxt));
+            f.free(cur.p);
+            cur = nxt;
+        }
+    }
+    UV_RUN(f.resnet2d("encoder.mid_block.resnets.0", cur, boc[3], &nxt));
+    f.free(cur.p);
+    cur = nxt;
+    UV_RUN(f.attention("encoder.mid_block.attentions.0", cur, &nxt, score_bytes(), &attn_chunks));
+    f.free(cur.p);
+    cur = nxt;
+    UV_RUN(f.resnet2d("encoder.mid_block.resnets.1", cur, boc[3], &nxt));
+    f.free(cur.p);
+    cur = nxt;
+    half_t* n = f.alloc(cur.rows() * cur.C);
+    if (!n) return UV_ERR_STATE;
+    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "encoder.conv_norm_out", 1, n));
+    Act na{n, cur.imgs, cur.H, cur.W, cur.C};
+    f.free(cur.p);
+    UV_RUN(f.conv(na, "encoder.conv_out", 2 * cfg.latent_channels, 9, 1, 0, false, nullptr, &cur));
+    f.free(n);
+    if (kcfg.use_quant_conv) {
+        UV_RUN(f.conv(cur, "quant_conv", 2 * cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt));
+        f.free(cur.p);
+        cur = nxt;
+    }
+    UV_RUN(uv_launch_nhwc_to_ncfhw(cur.p, 2 * cfg.latent_channels, moments, (int)imgs, 2 * cfg.latent_channels, 1, cur.H * cur.W, s));
+    f.free(cur.p);
+    f.free(f.gn_ws);
     return UV_OK;
 }

@@ -2,7 +2,8 @@
 
 The CLIP / T5 text encoders (transformers) and the VAE (diffusers AutoencoderKL) are third-party models and stay stock
 PyTorch-ROCm modules by default (``UNIVST_TEXT_ENCODER=native`` runs the two CLIP towers on the native library, univst_amd.text.NativeCLIPText, and
-``UNIVST_T5_ENCODER=native`` the T5 encoder, univst_amd.text.NativeT5Encoder); they must be available locally — there is no hub access on the target boxes.  The MM-DiT, the processors, the
+``UNIVST_T5_ENCODER=native`` the T5 encoder, univst_amd.text.NativeT5Encoder, ``UNIVST_SD3_VAE=native`` the VAE, univst_amd.vae.NativeAutoencoderKL — with all
+three set nothing here needs diffusers); they must be available locally — there is no hub access on the target boxes.  The MM-DiT, the processors, the
 rectified-flow inversions and the transfer loop run on the native HIP library."""
 import json
 import os
@@ -49,26 +50,52 @@ def load_t5_encoder(pretrained_model_path, subfolder, weight_dtype):
     return T5EncoderModel.from_pretrained(pretrained_model_path, subfolder=subfolder).requires_grad_(False)
 
 
+def load_sd3_vae(pretrained_model_path, weight_dtype):
+    """``UNIVST_SD3_VAE=native``: the 16-channel AutoencoderKL on the native library (fp16 with fp32 accumulation, read from the local ``<model>/vae``
+    directory without importing diffusers; univst_amd.vae.NativeAutoencoderKL).  Default ``stock``: diffusers' AutoencoderKL, as the reference builds it."""
+    mode = os.environ.get("UNIVST_SD3_VAE", "stock")
+    if mode not in ("stock", "native"):
+        raise ValueError(f"UNIVST_SD3_VAE={mode!r}: 'stock' or 'native'")
+    if mode == "native":
+        if weight_dtype != torch.float16:
+            raise ValueError(f"UNIVST_SD3_VAE=native computes in fp16 only; weight_dtype is {weight_dtype}")
+        if not os.path.isdir(os.path.join(pretrained_model_path, "vae")):
+            raise FileNotFoundError(f"UNIVST_SD3_VAE=native needs a local directory {os.path.join(pretrained_model_path, 'vae')}")
+        from ...vae import NativeAutoencoderKL
+        return NativeAutoencoderKL.from_pretrained(pretrained_model_path, subfolder="vae")
+    try:
+        from diffusers import AutoencoderKL
+    except ImportError as e:
+        raise RuntimeError("UNIVST_SD3_VAE=stock (the default) needs `diffusers` for the SD3 VAE; UNIVST_SD3_VAE=native runs it on the native "
+                           "library without diffusers") from e
+    return AutoencoderKL.from_pretrained(pretrained_model_path, subfolder="vae").requires_grad_(False).to(weight_dtype).cuda()
+
+
+def _flow_match_scheduler():
+    """diffusers' FlowMatchEulerDiscreteScheduler where it can be imported, else the restated tables of univst_amd.schedulers (the arrangement
+    src/sd/_common.py has for DDIM)"""
+    try:
+        from diffusers import FlowMatchEulerDiscreteScheduler
+    except ImportError:
+        from ...schedulers import FlowMatchEulerDiscreteScheduler
+    return FlowMatchEulerDiscreteScheduler
+
+
 def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
     from transformers import CLIPTokenizer, T5TokenizerFast
     from ..sd._common import load_text_encoder
-    try:
-        from diffusers import AutoencoderKL, FlowMatchEulerDiscreteScheduler
-    except ImportError as e:  # pragma: no cover
-        raise RuntimeError("the CLI needs `diffusers` for the SD3 VAE (third-party model, not re-implemented); the native MM-DiT / pipeline "
-                           "classes themselves do not") from e
     from ...backbones.video_diffusion_sd3.pipelines.custom_pipeline import CustomStableDiffusion3Pipeline
     from ...backbones.video_diffusion_sd3.pnp_utils import CrossFrameProcessor
+    vae = load_sd3_vae(pretrained_model_path, weight_dtype)        # first: the stock branch without diffusers fails before anything is loaded
     sub = lambda cls, name: cls.from_pretrained(pretrained_model_path, subfolder=name)          # noqa: E731
     transformer = load_transformer(pretrained_model_path, weight_dtype)
     transformer.set_attn_processor({n: CrossFrameProcessor() for n in transformer.attn_processors})      # run_*_sd3.py:58-69
-    enc = lambda cls, name: sub(cls, name).requires_grad_(False).to(weight_dtype).cuda()         # noqa: E731
     clip = lambda name: load_text_encoder(pretrained_model_path, name, weight_dtype, projected=True).to(weight_dtype).cuda()      # noqa: E731
     return CustomStableDiffusion3Pipeline(
         tokenizer=sub(CLIPTokenizer, "tokenizer"), tokenizer_2=sub(CLIPTokenizer, "tokenizer_2"), tokenizer_3=sub(T5TokenizerFast, "tokenizer_3"),
         text_encoder=clip("text_encoder"), text_encoder_2=clip("text_encoder_2"),
-        text_encoder_3=load_t5_encoder(pretrained_model_path, "text_encoder_3", weight_dtype).to(weight_dtype).cuda(), vae=enc(AutoencoderKL, "vae"), transformer=transformer,
-        scheduler=sub(FlowMatchEulerDiscreteScheduler, "scheduler"))
+        text_encoder_3=load_t5_encoder(pretrained_model_path, "text_encoder_3", weight_dtype).to(weight_dtype).cuda(), vae=vae, transformer=transformer,
+        scheduler=sub(_flow_match_scheduler(), "scheduler"))
 
 
 def add_common_args(parser, weight_dtype=torch.float16):

@@ -172,3 +172,66 @@ def vae_state_dict(config=None, device="cuda", dtype=torch.float16, seed=7):
     norm("decoder.conv_norm_out", boc[0]); conv("decoder.conv_out", cfg["out_channels"], boc[0], 3, 3)
     conv("decoder.time_conv_out", cfg["out_channels"], cfg["out_channels"], 3, 1, 1)
     return sd
+
+
+SD3_VAE_CONFIG = dict(in_channels=3, out_channels=3, latent_channels=16, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
+                      norm_num_groups=32, scaling_factor=1.5305, shift_factor=0.0609, use_quant_conv=False, use_post_quant_conv=False)
+
+
+def klvae_state_dict(config=None, device="cuda", dtype=torch.float16, seed=7):
+    """Random-init state dict with the parameter names and shapes of diffusers' plain AutoencoderKL (the SD3 / SD3.5 VAE; SD-v1.5's image VAE with
+    both quant convs on).  Init scales are those of ``vae_state_dict``, so activations stay in range."""
+    cfg = dict(SD3_VAE_CONFIG if config is None else config)
+    boc, L, lat = cfg["block_out_channels"], cfg["layers_per_block"], cfg["latent_channels"]
+    g = torch.Generator(device=device).manual_seed(seed)
+    sd = {}
+
+    def rn(*shape):
+        return torch.randn(*shape, generator=g, device=device, dtype=torch.float32)
+
+    def conv(p, co, ci, k):
+        sd[p + ".weight"] = (rn(co, ci, k, k) / math.sqrt(ci * k * k)).to(dtype)
+        sd[p + ".bias"] = (0.02 * rn(co)).to(dtype)
+
+    def norm(p, c):
+        sd[p + ".weight"] = (1.0 + 0.1 * rn(c)).to(dtype)
+        sd[p + ".bias"] = (0.05 * rn(c)).to(dtype)
+
+    def resnet(p, ci, co):
+        norm(p + ".norm1", ci); conv(p + ".conv1", co, ci, 3); norm(p + ".norm2", co); conv(p + ".conv2", co, co, 3)
+        if ci != co:
+            conv(p + ".conv_shortcut", co, ci, 1)
+
+    def mid(p, c):
+        resnet(p + ".resnets.0", c, c)
+        a = p + ".attentions.0"
+        norm(a + ".group_norm", c)
+        for n in ("to_q", "to_k", "to_v", "to_out.0"):
+            sd[f"{a}.{n}.weight"] = (rn(c, c) / math.sqrt(c)).to(dtype)
+            sd[f"{a}.{n}.bias"] = (0.02 * rn(c)).to(dtype)
+        resnet(p + ".resnets.1", c, c)
+
+    conv("encoder.conv_in", boc[0], cfg["in_channels"], 3)
+    ci = boc[0]
+    for b in range(4):
+        for l in range(L):
+            resnet(f"encoder.down_blocks.{b}.resnets.{l}", ci, boc[b]); ci = boc[b]
+        if b < 3:
+            conv(f"encoder.down_blocks.{b}.downsamplers.0.conv", boc[b], boc[b], 3)
+    mid("encoder.mid_block", boc[3])
+    norm("encoder.conv_norm_out", boc[3]); conv("encoder.conv_out", 2 * lat, boc[3], 3)
+    if cfg.get("use_quant_conv", False):
+        conv("quant_conv", 2 * lat, 2 * lat, 1)
+    if cfg.get("use_post_quant_conv", False):
+        conv("post_quant_conv", lat, lat, 1)
+    conv("decoder.conv_in", boc[3], lat, 3)
+    mid("decoder.mid_block", boc[3])
+    ci = boc[3]
+    for b in range(4):
+        co = boc[3 - b]
+        for l in range(L + 1):
+            resnet(f"decoder.up_blocks.{b}.resnets.{l}", ci, co); ci = co
+        if b < 3:
+            conv(f"decoder.up_blocks.{b}.upsamplers.0.conv", co, co, 3)
+    norm("decoder.conv_norm_out", boc[0]); conv("decoder.conv_out", cfg["out_channels"], boc[0], 3)
+    return sd

@@ -1,0 +1,1 @@
+__path__ = __import__("pkgutil").extend_path(__path__, __name__)  # the rest of backbones.animatediff still resolves to the UniVST checkout behind this repository on the path

@@ -312,6 +312,47 @@ int univst_t5_attention(const void* qkv, const float* bias_table, int B, int S, 
 /* host only (no GPU): transformers' T5Attention._relative_position_bucket (bidirectional) for the deltas -(n-1) .. n-1 -> out[2n - 1] */
 int univst_debug_t5_buckets(int num_buckets, int max_distance, int n, int* out);
 
+/* ------------------------------------------------------------------ AnimateDiff motion-module handle (the `motion_module` behind every spatial transformer)
+ * AnimateDiff-v2's VanillaTemporalModule (backbones/animatediff/models/motion_module.py: per-frame GroupNorm, proj_in, TemporalTransformerBlocks of
+ * Temporal_Self attentions along the FRAME axis and a GEGLU feed-forward, proj_out, + input) as one graph of gfx950 kernels per call, on the
+ * library's own activation order: row (b * F + f) * N + n, frame-major NHWC (csrc/motion.hip).  Its Attention / FeedForward layers are diffusers'
+ * (third-party, restated from their published definition); tests/motion_ref.py is the yardstick and tests/test_motion_ref.py holds it to golden g20. */
+typedef struct univst_motion univst_motion;
+typedef struct {
+    int channels;                   /* 320 / 640 / 1280: num_heads * 40, 80 or 160 */
+    int num_heads;                  /* 8 */
+    int num_blocks;                 /* num_transformer_block: 1 */
+    int attn_per_block;             /* len(attention_block_types), all "Temporal_Self": 2 */
+    int norm_groups;                /* 32 */
+    int max_len;                    /* temporal_position_encoding_max_len: 24 / 32 (<= 32); the most frames a forward takes */
+    int position_encoding;          /* 1: the sinusoid table is added to the input of to_q / to_k / to_v */
+    float gn_eps;                   /* 1e-6 */
+    float ln_eps;                   /* 1e-5 */
+} univst_motion_cfg;
+/* refuses (before any GPU call, naming the field) a channels / num_heads other than 40, 80 or 160, channels that are no multiple of norm_groups,
+ * max_len outside 1..32 */
+int univst_motion_create(const univst_motion_cfg* cfg, univst_motion** out);
+int univst_motion_destroy(univst_motion* h);
+/* key = the module's state-dict name ("temporal_transformer.proj_in.weight", "temporal_transformer.transformer_blocks.0.attention_blocks.1.to_q.weight",
+ * "temporal_transformer.transformer_blocks.0.ff.net.0.proj.bias"); a checkpoint's "...attention_blocks.i.pos_encoder.pe" [1, max_len, channels]
+ * replaces the table computed from the formula; dtype 0 = fp16, 1 = fp32 */
+int univst_motion_load_tensor(univst_motion* h, const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, void* stream);
+/* checks every tensor the config calls for and derives the fused q|k|v weights (the score scale folded into the q rows), the GEGLU projection in
+ * the row order of univst_linear's geglu = 1, and per attention the projected position rows pe_qkv[f] = Wqkv pe[f] (fp32 accumulation, fp16 rows) */
+int univst_motion_finalize(univst_motion* h, void* stream);
+/* X, Y fp16 [B * F, N, channels] rows (Y may not alias X, both 16-byte aligned); F <= 32, and F <= max_len when position_encoding is on.  The first call at a (B, F, N) sizes the arena; later calls at that size
+ * neither allocate nor synchronise. */
+int univst_motion_forward(univst_motion* h, const void* X, void* Y, int B, int F, int N, void* stream);
+/* read-outs of a handle: "arena_high_water" (bytes), "weight_bytes" (loaded tensors plus the derived copies) */
+int univst_motion_query(univst_motion* h, const char* name, double* out);
+/* the module's attention on its own: softmax attention along the frame axis.  qkv fp16 rows q | k | v, 3 * heads * head_dim wide and ldx halfs apart,
+ * row (b * F + f) * N + n, q already carrying the score scale; pe_qkv NULL or fp16 [F][3 * heads * head_dim], row f added to every row of frame f as
+ * it is loaded (the sum rounded to fp16 once); bidirectional softmax over the F rows {(b, f', n)} of each (b, n, head) -> out fp16 rows in the same
+ * order, heads * head_dim wide and ldo apart.  The rows are read in place (no regrouped copy).  1 <= F <= 32, head_dim 40 / 80 / 160, ldx a
+ * multiple of 8 and ldo of 4, B * F * N < 2^31, N * heads <= 2^24, B <= 65535; anything else is UNIVST_ERR_ARG before any launch. */
+int univst_temporal_attention(const void* qkv, int64_t ldx, const void* pe_qkv, int B, int F, int N, int heads, int head_dim, void* out, int64_t ldo,
+                              void* stream);
+
 /* ------------------------------------------------------------------ stand-alone operators (also used by tests) */
 /* Y[M,N] = X[M,K] W[N,K]^T + bias + residual; geglu != 0: the diffusers GEGLU projection (FeedForward net[0], attention.py:241) — writes the
  * N/2 columns x * gelu(gate), W / bias rows pre-interleaved: geglu = 1 in blocks of [16 x rows | 16 gate rows] (any K), geglu = 2 in the

@@ -31,6 +31,11 @@ class T5Cfg(C.Structure):
                 ("num_buckets", C.c_int), ("max_distance", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class MotionCfg(C.Structure):
+    _fields_ = [("channels", C.c_int), ("num_heads", C.c_int), ("num_blocks", C.c_int), ("attn_per_block", C.c_int), ("norm_groups", C.c_int),
+                ("max_len", C.c_int), ("position_encoding", C.c_int), ("gn_eps", C.c_float), ("ln_eps", C.c_float)]
+
+
 class VaeCfg(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("latent_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -117,6 +122,13 @@ SIGNATURES = {
     "univst_t5_finalize": (_I, [_P, _P]),
     "univst_t5_encode": (_I, [_P, _P, _I, _I, _P, _P]),
     "univst_t5_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
+    "univst_motion_create": (_I, [_P, C.POINTER(_P)]),
+    "univst_motion_destroy": (_I, [_P]),
+    "univst_motion_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I, _P]),
+    "univst_motion_finalize": (_I, [_P, _P]),
+    "univst_motion_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "univst_motion_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
+    "univst_temporal_attention": (_I, [_P, C.c_int64, _P, _I, _I, _I, _I, _I, _P, C.c_int64, _P]),
     "univst_t5_attention": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "univst_debug_t5_buckets": (_I, [_I, _I, _I, C.POINTER(_I)]),
     "univst_raft_create": (_I, [C.POINTER(_P)]),
@@ -229,6 +241,27 @@ def _f16(t: torch.Tensor, name="tensor"):
 
 
 # --------------------------------------------------------------------------- stand-alone operator wrappers
+def temporal_attention(qkv, B, F, N, heads, head_dim, pe_qkv=None, out=None):
+    """softmax attention along the frame axis (univst_temporal_attention): qkv fp16 [B*F*N, >= 3*heads*head_dim] rows q | k | v in the order
+    (b*F + f)*N + n (row stride = qkv.stride(0); q carries the score scale), pe_qkv None or fp16 [F, 3*heads*head_dim] -> out fp16
+    [B*F*N, heads*head_dim] (or the rows of a given ``out``, stride out.stride(0))."""
+    Cw = heads * head_dim
+    if out is None:
+        out = torch.empty(qkv.shape[0], Cw, device=qkv.device, dtype=torch.float16)
+    for name, t in (("qkv", qkv), ("out", out)):
+        if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 2 and t.stride(1) == 1):
+            raise ValueError(f"temporal_attention: {name} must be fp16 CUDA/HIP rows with contiguous columns, got {t.dtype} {t.device} strides {t.stride()}")
+    if qkv.shape[0] < B * F * N or out.shape[0] < B * F * N:
+        raise ValueError(f"temporal_attention: B*F*N = {B * F * N} rows, qkv has {qkv.shape[0]} and out {out.shape[0]}")
+    if pe_qkv is not None:
+        _f16(pe_qkv, "pe_qkv")
+        if tuple(pe_qkv.shape) != (F, 3 * Cw):
+            raise ValueError(f"temporal_attention: pe_qkv must be [F, 3*heads*head_dim] = [{F}, {3 * Cw}], got {tuple(pe_qkv.shape)}")
+    check(load().univst_temporal_attention(ptr(qkv), qkv.stride(0), ptr(pe_qkv), B, F, N, heads, head_dim, ptr(out), out.stride(0), stream_ptr()),
+          "temporal_attention")
+    return out
+
+
 def linear(x, w, bias=None, residual=None, geglu=False, out=None):
     """y[M,N] = x[M,K] w[N,K]^T (+bias)(+residual); geglu: w/bias rows pre-interleaved (True / 1: [16 x | 16 gate] blocks; 2: the
     X-resident order for K = 320, see geglu_xres_permute), N/2 output columns."""

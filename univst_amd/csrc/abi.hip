@@ -14,6 +14,7 @@
 #include "raft.h"
 #include "clip.h"
 #include "t5.h"
+#include "motion.h"
 
 static thread_local char g_err[1024] = "";
 void uv_set_error(const char* fmt, ...) {
@@ -280,6 +281,50 @@ int univst_t5_attention(const void* qkv, const float* bias_table, int B, int Sq,
     return uv_launch_t5_attention(H(qkv), bias_table, B, Sq, heads, HM(out), S(s));
 }
 int univst_debug_t5_buckets(int num_buckets, int max_distance, int n, int* out) { return uv_t5_bucket_table(num_buckets, max_distance, n, out); }
+struct univst_motion {
+    Motion impl;
+};
+int univst_motion_create(const univst_motion_cfg* cfg, univst_motion** out) {
+    UV_REQUIRE(cfg && out, "motion_create: null argument");
+    UV_RUN(uv_motion_check_cfg(*cfg));
+    univst_motion* h = new (std::nothrow) univst_motion();
+    UV_REQUIRE(h, "motion_create: out of host memory");
+    h->impl.cfg = *cfg;
+    *out = h;
+    return UV_OK;
+}
+int univst_motion_destroy(univst_motion* h) {
+    delete h;
+    return UV_OK;
+}
+int univst_motion_load_tensor(univst_motion* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
+}
+int univst_motion_finalize(univst_motion* h, void* s) {
+    UV_REQUIRE(h, "null handle");
+    return h->impl.finalize(S(s));
+}
+int univst_motion_forward(univst_motion* h, const void* X, void* Y, int B, int F, int N, void* s) {
+    UV_REQUIRE(h && X && Y, "motion_forward: null argument");
+    return h->impl.forward(H(X), HM(Y), B, F, N, S(s));
+}
+int univst_motion_query(univst_motion* h, const char* name, double* out) {
+    UV_REQUIRE(h && name && out, "motion_query: null argument");
+    if (!strcmp(name, "arena_high_water")) {
+        *out = (double)h->impl.arena.high_water;
+        return UV_OK;
+    }
+    if (!strcmp(name, "weight_bytes")) {
+        *out = h->impl.weight_bytes();
+        return UV_OK;
+    }
+    uv_set_error("motion_query: unknown quantity '%s'", name);
+    return UV_ERR_ARG;
+}
+int univst_temporal_attention(const void* qkv, int64_t ldx, const void* pe_qkv, int B, int F, int N, int heads, int head_dim, void* out, int64_t ldo, void* s) {
+    return uv_launch_temporal_attention(H(qkv), ldx, H(pe_qkv), B, F, N, heads, head_dim, HM(out), ldo, S(s));
+}
 struct univst_vae {
     Vae impl;
 };

@@ -1,0 +1,42 @@
+// AnimateDiff motion-module handle internals and the frame-axis attention launcher (see motion.hip).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "../../include/univst.h"
+#include "model.h"
+
+constexpr int UV_MOTION_MAX_F = 32;      // two 16-frame tiles: all scores of a (pixel, head) stay in one wave's registers
+
+struct MotionAttn {       // one Temporal_Self attention: LayerNorm, fused q|k|v (no bias), position rows already projected, out projection
+    const half_t *ln_g, *ln_b, *qkv_w, *pe_qkv, *out_w, *out_b;
+};
+struct MotionBlock {      // one TemporalTransformerBlock, looked up once by finalize
+    std::vector<MotionAttn> attn;
+    const half_t *ffn_g, *ffn_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b;
+};
+
+struct Motion : WeightStore {
+    univst_motion_cfg cfg;
+    Arena arena;
+    bool finalized = false;
+    std::vector<MotionBlock> blocks;
+    const half_t *gn_g = nullptr, *gn_b = nullptr, *in_w = nullptr, *in_b = nullptr, *outp_w = nullptr, *outp_b = nullptr;
+    // activations of one (B, F, N), carved from the arena by the first forward at that size
+    int rB = 0, rF = 0, rN = 0;
+    half_t *x[2] = {nullptr, nullptr}, *h = nullptr, *qkv = nullptr, *att = nullptr, *ff = nullptr;
+    float *gn_ws = nullptr, *splitk = nullptr;
+    size_t splitk_bytes = 0;
+
+    ~Motion();
+    int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
+    int finalize(hipStream_t s);
+    int reserve(int B, int F, int N);
+    int forward(const half_t* X, half_t* Y, int B, int F, int N, hipStream_t s);
+    double weight_bytes() const;
+};
+
+int uv_motion_check_cfg(const univst_motion_cfg& c);
+// softmax attention along the frame axis of the fused q|k|v rows (row (b F + f) N + n, q already scaled): see univst_temporal_attention
+int uv_launch_temporal_attention(const half_t* qkv, long ldx, const half_t* pe_qkv, int B, int F, int N, int heads, int head_dim, half_t* out, long ldo,
+                                 hipStream_t s);

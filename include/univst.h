@@ -426,6 +426,16 @@ int univst_conv_nhwc_tapinner(const void* X1, const void* X2, int C1, int C2, in
 int univst_conv3x3_patch(const void* X1, const void* X2, int C1, int C2, int imgs, int Hs, int Ws, int upsample, const void* W32,
                          const void* bias, const void* rowbias, int rows_per_rowbias, const void* residual, void* Y, int Cout,
                          void* stream);
+/* The 3x3 conv over the nearest x2 upsampled input (UpsamplePseudo3D, resnet.py:123-175) as four 2x2-tap PHASE convs over the source image: output pixel
+ * (2y+a, 2x+b) sees only 2x2 distinct source pixels, so the weights of phase (a, b) are sums of the original taps (per axis {k0}, {k1+k2} for phase 0 and
+ * {k0+k1}, {k2} for phase 1) and the matrix work falls by 9/4.  univst_conv_up2_phase_weights derives the copy W4 [4][Cout][Cin/32][4][32] from the
+ * checkpoint's [Cout][Cin][3][3] weight (fp32 sums, one fp16 rounding; Cin % 32 == 0); univst_conv3x3_up2_phase runs conv_patch_kernel in its phase mode
+ * on X [imgs][Hs][Ws][C] -> Y [imgs][2Hs][2Ws][Cout] (bias only) and, with gn_out, leaves the GroupNorm statistics of gn_group_width-channel sub-groups
+ * per 16-row fragment: gn_out[Cout / width][rows / 16][2] fp32, fragment slot 4 s + phase for source fragment s.  UNIVST_ERR_ARG when the problem is not
+ * eligible for the phase form (C % 64, Cout % 320, whole source rows per 256/192-row tile, >= 150 tiles, no split-K): it never falls back silently. */
+int univst_conv_up2_phase_weights(const void* W_oihw, int Cout, int Cin, void* W4, void* stream);
+int univst_conv3x3_up2_phase(const void* X, int C, int imgs, int Hs, int Ws, const void* W4, const void* bias, void* Y, int Cout, float* gn_out,
+                             int gn_group_width, void* stream);
 /* A GroupNorm folded into the linear that consumes its output (the per-frame GroupNorm -> proj_in of a transformer block, attention.py:121-123): per
  * statistics unit s (rows_per_stat rows) the weight set W_sets[s][n][k] = fp16(W[n][k] * gamma_k * rstd_{s,g(k)}) and the fp32 bias
  * bias32[s][n] = bias[n] + sum_k W[n][k] * (beta_k - mean_{s,g(k)} * rstd * gamma_k); univst_linear_sets then runs on the RAW rows with the set of each
@@ -629,6 +639,7 @@ int univst_debug_delay_us(double us, void* stream);
 #define UNIVST_PLAN_TAPINNER 1024     /* univst_conv_nhwc_tapinner's k order */
 #define UNIVST_PLAN_Y_UNALIGNED 2048  /* the output is 8 bytes off a 16-byte boundary */
 #define UNIVST_PLAN_WORKSPACE 4096    /* the caller holds the split-K workspace (the UNet graph, RAFT) */
+#define UNIVST_PLAN_W4 8192           /* the phase weight copy of an upsampler conv beside the others (the UNet graph; univst_conv_up2_phase_weights) */
 #define UNIVST_PLAN_GEOM_3X3 0        /* 3x3 with padding 1 (taps = 9) or 1x1 (taps = 1) */
 #define UNIVST_PLAN_GEOM_PAD_END 1    /* 3x3 over an input padded at the bottom / right only (the VAE encoder's stride-2 conv) */
 #define UNIVST_PLAN_GEOM_FRAME 2      /* 3x1 (taps = 3) over image rows = frames, image columns = pixels (the VAE's Conv3d (3,1,1)) */

@@ -147,6 +147,8 @@ SIGNATURES = {
     "univst_conv_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
     "univst_conv_nhwc_tapinner": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
     "univst_conv3x3_patch": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "univst_conv_up2_phase_weights": (_I, [_P, _I, _I, _P, _P]),
+    "univst_conv3x3_up2_phase": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
     "univst_groupnorm_fold_linear": (_I, [_P, _I, _L, _I, _I, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "univst_linear_sets": (_I, [_P, _L, _P, _P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P]),
     "univst_groupnorm_workspace_bytes": (_L, [_L, _I, _I]),
@@ -400,6 +402,29 @@ def conv3x3_patch(x1, w_t32, bias=None, x2=None, rowbias=None, rows_per_rowbias=
     check(load().univst_conv3x3_patch(ptr(x1), ptr(x2), C1, C2, imgs, Hs, Ws, int(upsample), ptr(w_t32), ptr(bias), ptr(rowbias), rows_per_rowbias,
                                       ptr(residual), ptr(out), Cout, stream_ptr()), "conv3x3_patch")
     return out
+
+
+def conv_up2_phase_weights(w):
+    """[Cout, Cin, 3, 3] -> the phase copy [4, Cout, Cin/32, 4, 32] of an upsampler conv: per phase (a, b) of the output pixel (2y+a, 2x+b) the sums of the
+    original taps that fall on one of its 2x2 source pixels (fp32 sums, one fp16 rounding)."""
+    _f16(w)
+    Co, Ci = w.shape[:2]
+    w4 = torch.empty(4, Co, Ci // 32, 4, 32, device=w.device, dtype=torch.float16)
+    check(load().univst_conv_up2_phase_weights(ptr(w.contiguous()), Co, Ci, ptr(w4), stream_ptr()), "conv_up2_phase_weights")
+    return w4
+
+
+def conv3x3_up2_phase(x, w4, bias=None, gn_group_width=0):
+    """3x3 conv over the nearest x2 upsampled x [imgs, Hs, Ws, C] as four 2x2-tap phase convs (conv_patch_kernel's phase mode) -> [imgs, 2Hs, 2Ws, Cout];
+    with gn_group_width also the GroupNorm statistics [Cout / width, rows / 16, 2] of the stored rows.  Raises when the problem is not eligible."""
+    _f16(x), _f16(w4)
+    imgs, Hs, Ws, C_ = x.shape
+    Cout = w4.shape[1]
+    out = torch.empty(imgs, 2 * Hs, 2 * Ws, Cout, device=x.device, dtype=torch.float16)
+    gst = torch.zeros(Cout // gn_group_width, imgs * 4 * Hs * Ws // 16, 2, device=x.device, dtype=torch.float32) if gn_group_width else None
+    check(load().univst_conv3x3_up2_phase(ptr(x), C_, imgs, Hs, Ws, ptr(w4), ptr(bias), ptr(out), Cout, ptr(gst), gn_group_width, stream_ptr()),
+          "conv3x3_up2_phase")
+    return (out, gst) if gn_group_width else out
 
 
 def groupnorm_fold_linear(x, gamma, beta, groups, eps, rows_per_stat, w, bias=None):

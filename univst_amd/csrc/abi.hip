@@ -596,6 +596,27 @@ int univst_conv3x3_patch(const void* X1, const void* X2, int C1, int C2, int img
     g.R = H(R); g.ldr = Cout; g.Y = HM(Y); g.ldy = Cout;
     return uv_launch_gemm(g, 1, S(s));
 }
+int univst_conv_up2_phase_weights(const void* W_oihw, int Cout, int Cin, void* W4, void* s) {
+    UV_REQUIRE(W_oihw && W4, "conv_up2_phase_weights: null argument");
+    return uv_launch_conv_up2_phase_weights(H(W_oihw), HM(W4), Cout, Cin, S(s));
+}
+int univst_conv3x3_up2_phase(const void* X, int C, int imgs, int Hs, int Ws, const void* W4, const void* bias, void* Y, int Cout, float* gn_out,
+                             int gn_group_width, void* s) {
+    UV_REQUIRE(X && W4 && Y, "conv3x3_up2_phase: null argument");
+    UV_REQUIRE(!gn_out || (gn_group_width > 0 && Cout % gn_group_width == 0), "conv3x3_up2_phase: gn_group_width=%d must divide Cout=%d", gn_group_width, Cout);
+    GemmParams g;
+    g.X = H(X); g.C1 = C; g.Hs = Hs; g.Ws = Ws; g.up = 1; g.stride = 1; g.taps = 9;
+    g.Ho = 2 * Hs; g.Wo = 2 * Ws;
+    g.M = imgs * g.Ho * g.Wo; g.N = Cout; g.K = 9 * C;
+    g.W4 = H(W4); g.bias = H(bias); g.Y = HM(Y); g.ldy = Cout;
+    g.tapw = 3; g.pady = g.padx = 1;
+    int emitted = 0;
+    if (gn_out) { g.gn_out = gn_out; g.gn_gw = gn_group_width; g.gn_G = Cout / gn_group_width; g.gn_emitted = &emitted; }
+    const GemmPlan pl = uv_gemm_plan(g, 1, uv_num_cus());      // only the phase copy is given: the plan takes the phase form or names what is missing
+    UV_REQUIRE(pl.rc != UV_OK || (pl.phase && (!gn_out || pl.gn_emit)), "conv3x3_up2_phase: the problem does not take the phase form with these statistics "
+               "(C %% 64, Cout %% 320, whole source rows per tile, >= 150 tiles, statistics of 10 / 20 / 40-channel groups)");
+    return uv_launch_gemm(g, 1, S(s));
+}
 int univst_groupnorm_fold_linear(const void* X, int C, int64_t rows, int rows_per_stat, int groups, float eps, const void* gamma, const void* beta,
                                  const void* W, const void* bias, int N, void* W_sets, float* bias32, void* ws, void* s) {
     UV_REQUIRE(X && gamma && beta && W && W_sets && bias32 && ws && N > 0, "groupnorm_fold_linear: null argument");
@@ -702,6 +723,7 @@ int univst_debug_gemm_plan(int ncu, int mode, int M, int N, int K, int geglu, in
     g.X = h; g.Y = on(UNIVST_PLAN_Y_UNALIGNED) ? h + 4 : h;
     g.W = on(UNIVST_PLAN_W32_ONLY) ? nullptr : h;
     g.W32 = on(UNIVST_PLAN_W32_ONLY) || on(UNIVST_PLAN_W32) ? h : nullptr;
+    g.W4 = on(UNIVST_PLAN_W4) ? h : nullptr;
     g.N = N; g.geglu = geglu;
     const int No = geglu ? N / 2 : N;
     if (mode == 0) {

@@ -249,9 +249,13 @@ constexpr int EPI_LDW = 164;
 // 8 * 16 * 164 * 4 = 83968; per-wave scratch from 90112 (8 x 2560 B).  The 192-row tile has 128 KB of LDS, the 256-row one 144 KB.
 constexpr int EPI_STAT_SCRATCH = 90112;
 // cf: the block's LDS constants, cn = nb - n0, rw = first tile row of this wave; scratch: this wave's statistics scratch (LNF).
-template <int MJ, int LNF = 0>
+// PH (conv_patch_kernel's phase form of an upsampler conv: bias only, no residual / row bias): the tile's rows are SOURCE pixels of phase ph = 2a + b;
+// row m = (stacked source row r, column x) of width phw goes to output row (2r + a) * 2 phw + 2x + b, and its 16-row fragment's GroupNorm statistics
+// to slot 4 (m / 16) + ph — the slots of whole images stay the contiguous range the consumer walks.
+template <int MJ, int LNF = 0, bool PH = false>
 __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, const f4 (&acc)[10][MJ], float* slab, int mw, int nb, int lane,
-                                                  const float* cf, int cn, int rw = 0, float2* scratch = nullptr, half_t* hs = nullptr) {
+                                                  const float* cf, int cn, int rw = 0, float2* scratch = nullptr, half_t* hs = nullptr,
+                                                  int ph = 0, int phw = 1) {
     // hs: this wave's 16 x 160 fp16 scratch (5 KB) for the GroupNorm statistics of the stored tile (p.gn_out), else unused
     const int l15 = lane & 15, g = lane >> 4;
     const half_t* hb = reinterpret_cast<const half_t*>(cf + EPC_HALFS) + cn;
@@ -335,7 +339,12 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, const f4 
 #pragma unroll
                     for (int r = 0; r < 8; ++r) o[r] = (half_t)v[r];
                 }
-                *reinterpret_cast<h8*>(p.Y + (long)m * p.ldy + n) = o;
+                long mo = m;
+                if constexpr (PH) {
+                    const int r = m / phw;
+                    mo = ((long)(2 * r + (ph >> 1)) * (2 * phw)) + 2 * (m - r * phw) + (ph & 1);
+                }
+                *reinterpret_cast<h8*>(p.Y + mo * p.ldy + n) = o;
                 if (LNF != 1 && p.gn_out) *reinterpret_cast<h8*>(&hs[row * 160 + c]) = o;       // the stored values, row-major, for the group statistics below
                 if (LNF == 1) {           // (sum, sum of squares) of the 8 values AS STORED: what the consuming GEMM will read
                     float s1 = 0.f, s2 = 0.f;
@@ -398,7 +407,7 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, const f4 
                 }
                 if (l15 == 15 && mrow0 < p.M) {
                     // layout [sub-group][fragment]: the consumer's reduction walks the fragments of one sub-group — contiguous there
-                    float2* dst = reinterpret_cast<float2*>(p.gn_out) + (long)(nb / p.gn_gw + g * ngpl) * (p.M >> 4) + (mrow0 >> 4);
+                    float2* dst = reinterpret_cast<float2*>(p.gn_out) + (long)(nb / p.gn_gw + g * ngpl) * (p.M >> 4) + (PH ? 4 * (mrow0 >> 4) + ph : mrow0 >> 4);
 #pragma unroll
                     for (int gi = 0; gi < 4; ++gi)
                         if (gi < ngpl) dst[(long)gi * (p.M >> 4)] = float2{a1[gi], a2[gi]};
@@ -1182,6 +1191,13 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p) {
 // A tile may straddle image boundaries (192-row tiles do; at the 8x8 level a tile holds three or four whole images): ONE zero
 // row is inserted between two images, which serves as the bottom padding of the upper image and the top padding of the lower
 // one.  Image widths below 16 are fine as long as they divide 16 (a 16-pixel MFMA fragment then covers whole image rows).
+//
+// PHASE FORM of an upsampler conv (p.W4 set: a kernel argument, so the mode is uniform over the launch).  Over the nearest-x2 upsampled image output
+// pixel (2y+a, 2x+b) reads source rows {y-1, y} (a = 0) / {y, y+1} (a = 1), columns alike: each phase (a, b) is a stride-1 conv with 2x2 taps over the
+// SOURCE image whose weights are sums of the original taps — 4 instead of 9 MFMA passes per slab.  The tile's GEMM rows are then source pixels
+// (M / 4 per phase), the grid is 4 x (tiles of one phase) = the 9-tap grid, and the block index gives the phase.  The patch image is the one of a plain
+// conv at source geometry (patch (0,0) = row above, column left), which serves all four phases: tap (i, j) of phase (a, b) is patch offset
+// (a + i) PW + (b + j).  Both forms run ONE loop over (slab, tap) units; the tap offset is stepped, not divided out.
 template <int MJ>
 __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     constexpr int NF = 10, BMB = 64 * MJ, BNB = 320, LDSH = 64;
@@ -1199,13 +1215,20 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     const int l15 = lane & 15, g = lane >> 4;
     const int nt_n = p.N / BNB;
     int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int ntiles = nt_n * ((p.M + BMB - 1) / BMB);
-    const int split = lid / ntiles;                          // split-K over 64-channel slab pairs (p.ktps = 9 * pairs per split)
+    const bool ph4 = p.W4 != nullptr;
+    const int Mg = ph4 ? p.M >> 2 : p.M;                     // GEMM rows: output pixels, or the source pixels of one phase
+    const int ntiles = nt_n * ((Mg + BMB - 1) / BMB);
+    // split-K over 64-channel slab pairs (p.ktps = 9 * pairs per split); in the phase form (never split) the same index is the phase: phase-major, so the
+    // blocks in flight share one phase's weights (measured stand-alone against phase-minor order at the three UNet shapes: 0.5155 / 0.4763 / 0.1258 ms
+    // against 0.5237 / 0.4821 / 0.1273 ms)
+    const int split = lid / ntiles;
     lid -= split * ntiles;
+    const int ph = ph4 ? split : 0;
     const int tn = lid % nt_n, tm = lid / nt_n;
     const int m0 = tm * BMB, n0 = tn * BNB;
-    const int Wd = p.Wo, PW = Wd + 2, Himg = p.Ho;
-    const int rows_total = p.M / Wd;                         // image rows in the stack of all images
+    const int up = ph4 ? 0 : p.up;
+    const int Wd = ph4 ? p.Ws : p.Wo, PW = Wd + 2, Himg = ph4 ? p.Hs : p.Ho;
+    const int rows_total = Mg / Wd;                          // image rows in the stack of all images
     const int R = BMB / Wd;
     const int gr0 = m0 / Wd;                                 // first image row of the tile in the stack of all images
     // patch rows: [row above the tile | tile rows, with one zero row wherever two images meet | row below the tile].  In the
@@ -1234,7 +1257,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
         const int gr = gr0 - r0 + seg * Himg + pos;
         const bool ok = q < npieces && px >= 1 && px <= Wd && pos != Himg && gr < rows_total;      // pos == Himg: zero row (padding)
         const int img = gr / Himg, yy = gr - img * Himg;                 // fused nearest x2 upsample (p.up): source pixel = (y >> 1, x >> 1)
-        ppix[i] = ok ? (img * p.Hs + (yy >> p.up)) * p.Ws + ((px - 1) >> p.up) : -1;
+        ppix[i] = ok ? (img * p.Hs + (yy >> up)) * p.Ws + ((px - 1) >> up) : -1;
         pch[i] = (cst ^ (((pp >> 2) & 1) << 1)) * 8;
     }
     auto issue_patch = [&](int slab) {
@@ -1251,13 +1274,16 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     // ---- weight staging (as gemm_big_kernel): rows rb + 64 i, chunk kc, XOR-swizzled with the row
     const int rb = tid >> 3;
     const int kc = (tid & 7) ^ (rb & 7);
+    const int NT = ph4 ? 4 : 9, TW = ph4 ? 2 : 3;            // taps per slab, taps per patch row
+    const int Kw = ph4 ? 4 * (p.C1 + p.C2) : p.K;            // k extent of a weight row
+    const half_t* const Wsrc = ph4 ? p.W4 + (long)ph * p.N * Kw : p.W32;
     unsigned woff[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) woff[i] = (unsigned)((long)(n0 + rb + 64 * i) * p.K + kc * 8);
+    for (int i = 0; i < 5; ++i) woff[i] = (unsigned)((long)(n0 + rb + 64 * i) * Kw + kc * 8);
     auto issue_w = [&](int t) {
         half_t* dst = Wb + (t & 1) * WT + wave_u * 8 * LDSH;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) glds16(p.W32 + woff[i] + t * 64, dst + 64 * i * LDSH);
+        for (int i = 0; i < 5; ++i) glds16(Wsrc + woff[i] + t * 64, dst + 64 * i * LDSH);
     };
 
     // ---- fragment geometry: patch pixel (tap 0,0) of this lane's row in each of the wave's MJ fragments
@@ -1274,8 +1300,8 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     const int s_begin = p.splits > 1 ? split * (p.ktps / 9) * 2 : 0;
     const int s_end = p.splits > 1 ? (s_begin + (p.ktps / 9) * 2 < nslab_all ? s_begin + (p.ktps / 9) * 2 : nslab_all) : nslab_all;
     const int nslab = s_end - s_begin;                       // slabs of THIS block (an even number)
-    const int T = nslab * 9 / 2;
-    const int t_off = s_begin * 9 / 2;                       // first k tile of this block in the weight's k order
+    const int T = nslab * NT / 2;
+    const int t_off = s_begin * NT / 2;                      // first k tile of this block in the weight's k order
     issue_patch(s_begin);
     if (nslab > 1) issue_patch(s_begin + 1);
     issue_w(t_off);
@@ -1286,11 +1312,12 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
 #pragma unroll
         for (int j = 0; j < MJ; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
     int next_patch = 2;                                      // next slab to stage, relative to s_begin
-    int u_slab = s_begin, u_tap = 0;
+    const int delta0 = ph4 ? (ph >> 1) * PW + (ph & 1) : 0;  // patch offset of a slab's first tap
+    int u_slab = s_begin, u_tap = 0, u_kx = 0, u_delta = delta0;
     const int sw = l15 & 7;
     for (int t = 0; t < T; ++t) {
         __syncthreads();                  // vmcnt(0) + barrier: everything issued so far landed; tile t-1 is consumed everywhere
-        if (next_patch < nslab && 9 * (next_patch - 1) <= 2 * t) {     // slab next_patch-2 is fully consumed: refill its buffer
+        if (next_patch < nslab && NT * (next_patch - 1) <= 2 * t) {     // slab next_patch-2 is fully consumed: refill its buffer
             issue_patch(s_begin + next_patch);
             ++next_patch;
         }
@@ -1299,8 +1326,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
         for (int ks = 0; ks < 2; ++ks) {
             if (ks == 1 && t + 1 < T) issue_w(t_off + t + 1);                // next weight tile: before the second k-half (measured better than before the first)
             const half_t* Ps = Pb + (u_slab & 1) * PBUF;
-            const int ky = u_tap / 3, kx = u_tap - 3 * ky;
-            const int delta = ky * PW + kx;
+            const int delta = u_delta;
             const int ch = ((ks * 4 + g) ^ sw) * 8;
             h8 a[NF];
 #pragma unroll
@@ -1312,7 +1338,9 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
 #pragma unroll
                 for (int i = 0; i < NF; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], b, acc[i][j], 0, 0, 0);
             }
-            if (++u_tap == 9) { u_tap = 0; ++u_slab; }
+            ++u_delta;
+            if (++u_kx == TW) { u_kx = 0; u_delta += PW - TW; }
+            if (++u_tap == NT) { u_tap = 0; u_delta = delta0; ++u_slab; }
         }
     }
     if (p.splits > 1) {                   // split-K: raw fp32 partials; splitk_reduce_kernel runs the epilogue
@@ -1324,6 +1352,12 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < NF; ++i) *reinterpret_cast<f4*>(row + i * 16) = acc[i][j];
         }
+        return;
+    }
+    if (ph4) {                            // (the plan takes the phase form with the LDS row epilogue only)
+        __syncthreads();
+        gemm_epilogue_lds<MJ, 0, true>(p, acc, reinterpret_cast<float*>(smem) + wave * (16 * EPI_LDW), m0 + wm * 16 * MJ, n0 + wn * 160, lane, epc, wn * 160, 0, nullptr,
+                                       reinterpret_cast<half_t*>(reinterpret_cast<char*>(smem) + EPI_STAT_SCRATCH) + wave * 2560, ph, Wd);
         return;
     }
     if (p.epi_lds) {
@@ -1341,6 +1375,23 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     }
 }
 
+
+// [Co,Ci,3,3] -> [phase a*2+b][Co][Ci/32][tap i*2+j][32] (conv_patch_kernel's phase form, GemmParams::W4).  Per axis the original taps {k0}, {k1+k2}
+// (phase 0) and {k0+k1}, {k2} (phase 1) fall on the two source pixels a phase reads: fp32 sums, ONE fp16 rounding.
+__global__ void conv_up2_phase_weight_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int Co, int Ci) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)Co * Ci * 4;
+    if (i >= 4 * per) return;
+    const int j = (int)(i % 32), t = (int)((i / 32) % 4), q = (int)((i / 128) % (Ci / 32)), o = (int)((i / (4L * Ci)) % Co), ph = (int)(i / per);
+    const int a = ph >> 1, b = ph & 1, ti = t >> 1, tj = t & 1;
+    // taps of one axis that fall on source offset `tap` of phase `phs`: phase 0 {0}, {1, 2}; phase 1 {0, 1}, {2}
+    const int y0 = ti == 0 ? 0 : 1 + a, y1 = ti == 0 ? a : 2, x0 = tj == 0 ? 0 : 1 + b, x1 = tj == 0 ? b : 2;
+    const half_t* w = in + ((long)o * Ci + q * 32 + j) * 9;
+    float acc = 0.f;
+    for (int ky = y0; ky <= y1; ++ky)
+        for (int kx = x0; kx <= x1; ++kx) acc += (float)w[ky * 3 + kx];
+    out[i] = (half_t)acc;
+}
 
 // y[m][n] = sum_k act(x[m][k]) W[n][k] + b[n], M <= 8: one wave per output column (time embeddings).
 __global__ __launch_bounds__(256) void linear_small_kernel(const half_t* __restrict__ x, const half_t* __restrict__ W,
@@ -1432,8 +1483,17 @@ static int uv_pick_splits(long ntiles, int nk, long slots, int min_ktps, int max
 
 // LDS-patch 3x3 conv (conv_patch_kernel): whole image rows per tile, 16-pixel fragments inside one image row, patch <= 512 pixels
 static bool uv_conv_patch_eligible(const GemmParams& p, int bmb) {
-    return p.W32 && p.taps == 9 && p.stride == 1 && p.C1 % 32 == 0 && p.C2 % 32 == 0 && (p.C1 + p.C2) % 64 == 0 && p.N % 320 == 0 && (p.Wo % 16 == 0 || 16 % p.Wo == 0) &&
+    return (p.W32 || p.W4) && p.taps == 9 && p.stride == 1 && p.C1 % 32 == 0 && p.C2 % 32 == 0 && (p.C1 + p.C2) % 64 == 0 && p.N % 320 == 0 && (p.Wo % 16 == 0 || 16 % p.Wo == 0) &&
            bmb % p.Wo == 0 && (bmb / p.Wo + 2 + bmb / p.Wo / p.Ho + 1) * (p.Wo + 2) <= 512 && !p.geglu;
+}
+
+// The phase form of an upsampler conv on that kernel (GemmParams::W4): the tile's rows are SOURCE pixels, so the requirements of the patch image hold at
+// source geometry, every phase is a whole number of tiles, and the epilogue is bias (+ GroupNorm statistics: whole 16-pixel fragments per image) only.
+// The caller adds: the problem is patch-eligible at output geometry, no split-K, LDS row epilogue.
+static bool uv_conv_patch_phase_eligible(const GemmParams& p, int bmb) {
+    return p.W4 && p.up == 1 && p.taps == 9 && p.stride == 1 && p.C2 == 0 && p.C1 % 64 == 0 && p.N % 320 == 0 && p.Ho == 2 * p.Hs && p.Wo == 2 * p.Ws &&
+           (p.Ws % 16 == 0 || 16 % p.Ws == 0) && bmb % p.Ws == 0 && (p.Hs * p.Ws) % 16 == 0 &&
+           (bmb / p.Ws + 2 + bmb / p.Ws / p.Hs + 1) * (p.Ws + 2) <= 512 && (p.M / 4) % bmb == 0 && !p.R && !p.rowbias && !p.bias2 && !p.bias32 && !p.geglu;
 }
 
 // fewest 256x320 tiles a problem needs to take the big tile without split-K: measured cross-over (tools/bench_gemm_mid.py)
@@ -1566,6 +1626,8 @@ GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu) {
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     PLAN_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
     pl.block = 512;
+    // ALGORITHMIC flops: an upsampler conv in the phase form (pl.phase) executes 4 / 9 of them and is still charged 2 M N 9 Cin, as the attention class
+    // counts the reference's key multiplicities
     pl.flops = 2.0 * p.M * (double)p.N * p.K;
     if (p.geglu == 2) {                  // weights in the X-resident kernel's row order (geglu_xres_kernel)
         PLAN_REQUIRE(mode == 0 && p.K == XR_K && p.N % XR_BN == 0 && p.ldx % 8 == 0 && p.ldy % 8 == 0 && al16(p.X) && al16(p.W) && al16(p.Y) && al16(p.bias) &&
@@ -1592,7 +1654,7 @@ GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu) {
         PLAN_REQUIRE(p.K == p.taps * (p.C1 + p.C2), "conv: K=%d != taps*(C1+C2)", p.K);
         const bool sym3 = p.taps == 9 && p.pady == 1 && p.padx == 1;
         PLAN_REQUIRE(!p.korder || (sym3 && p.C1 % 64 == 0 && p.C2 % 64 == 0), "conv: tap-inner k order needs the 3x3 / padding-1 kernel and 64-channel slabs");
-        PLAN_REQUIRE(!p.W32 || sym3, "conv: the LDS-patch weight copy is for the 3x3 / padding-1 kernel");
+        PLAN_REQUIRE((!p.W32 && !p.W4) || sym3, "conv: the LDS-patch weight copy is for the 3x3 / padding-1 kernel");
     }
     uv_gemm_bytes(p, mode, &pl.bytes, &pl.aux_bytes);
     const int nk = (p.K + 63) / 64;
@@ -1629,7 +1691,11 @@ GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu) {
         if (sp >= 2 && nblk * sp >= 128) bsplits = sp;
     }
     const bool fills = nblk >= BIG_MIN_TILES || bsplits > 1;
-    const bool use_patch = mode == 1 && fills && uv_conv_patch_eligible(p, use192 ? 192 : 256);
+    const bool patch_ok = mode == 1 && fills && uv_conv_patch_eligible(p, use192 ? 192 : 256);
+    // the phase form of an upsampler conv: same kernel, same grid (4 phases x a quarter of the row tiles); a problem that gives the phase copy and is not
+    // eligible (split-K shapes, frame-shard ranks, a source width that does not divide the tile, a residual) keeps the 9-tap plan
+    const bool try_phase = patch_ok && bsplits <= 1 && uv_conv_patch_phase_eligible(p, use192 ? 192 : 256);
+    const bool use_patch = patch_ok && (p.W32 || try_phase);
     PLAN_REQUIRE(p.W || use_patch, "conv: only the [Cin/32][9][32] weight copy was given but the problem is not eligible for the LDS-patch kernel "
                  "(3x3, stride 1, whole image rows per 256/192-row tile, >= 150 tiles or a reduction long enough for split-K)");
     if (fills && big_shape_ok(p.N, p.K, xmax, ragged, conv_rag ? 256 : 640)) {
@@ -1664,6 +1730,8 @@ GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu) {
                          (!p.stats_out || (!p.geglu && p.N % 160 == 0)), "linear: LayerNorm fold on a problem the direct 256x320 path does not take");
             PLAN_REQUIRE(!(p.ln_stats && p.stats_out), "linear: a LayerNorm-folded linear cannot also emit row statistics");
         }
+        pl.phase = try_phase && pl.epi_lds == 1 && pl.splits == 1;
+        PLAN_REQUIRE(!use_patch || p.W32 || pl.phase, "conv: only the phase weight copy was given but the launch cannot take the phase form (16-byte aligned Y / bias rows)");
         pl.cls = mode == 0 ? UV_CLS_GEMM_BIG : (use_patch ? UV_CLS_CONV_PATCH : UV_CLS_CONV_BIG);
         pl.prof_sym = true;
         // 3x3 / stride 1 on whole image rows: input patch in LDS, k order [Cin/32][9][32] (p.W32)
@@ -1726,6 +1794,7 @@ int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
     q.tile_gm = pl.tile_gm;
     if (!pl.gn_emit) q.gn_out = nullptr;
     else if (q.gn_emitted) *q.gn_emitted = 1;
+    if (!pl.phase) q.W4 = nullptr;         // the kernel takes the phase form exactly when the pointer survives
     const bool own_ws = pl.ws_bytes && !(q.partial && q.partial_bytes >= pl.ws_bytes);      // no caller workspace (UNet arena) that holds the partials
     if (own_ws) UV_HIP(hipMallocAsync((void**)&q.partial, pl.ws_bytes, stream));
     uv_prof_begin(pl.cls, pl.flops, pl.bytes, stream, pl.prof_sym ? pl.sym : nullptr, pl.aux_bytes);
@@ -1754,6 +1823,13 @@ int uv_gemm_plan_text(const GemmParams& p0, int mode, int ncu, char* buf, int n)
     snprintf(buf, (size_t)n, "%s grid=%u block=%u splits=%d%s big_direct=%d fold_producer=%d fold_consumer=%d geglu_consumer=%d geglu_xres=%d", pl.sym, pl.grid,
              pl.block, pl.splits, pl.reduce_grid ? " +splitk_reduce" : "", (int)takes_big_direct(p.M, p.N, p.K, p.ldx), (int)fold_producer_ok(p.M, p.N, p.K, ncu),
              (int)fold_consumer_ok(p.M, p.N, p.K, false, ncu), (int)fold_consumer_ok(p.M, p.N, p.K, true, ncu), (int)geglu_xres_ok(p.N, p.K, p.M, ncu));
+    return UV_OK;
+}
+
+int uv_launch_conv_up2_phase_weights(const half_t* w_oihw, half_t* w4, int Co, int Ci, hipStream_t stream) {
+    UV_REQUIRE(w_oihw && w4 && Co > 0 && Ci > 0 && Ci % 32 == 0, "conv_up2_phase_weights: needs Cin %% 32 == 0 (Co=%d Ci=%d)", Co, Ci);
+    hipLaunchKernelGGL(conv_up2_phase_weight_kernel, dim3((unsigned)(((long)Co * Ci * 16 + 255) / 256)), dim3(256), 0, stream, w_oihw, w4, Co, Ci);
+    UV_LAUNCH_CHECK();
     return UV_OK;
 }
 

@@ -68,6 +68,11 @@ struct GemmParams {
     float ln_eps = 0.f;
     const float* ln_wsum = nullptr;    // [N] fp32: sum_k W'[n][k]
     const float* ln_bias = nullptr;    // [N] fp32: bias[n] + sum_k beta[k] W[n][k]
+    // optional PHASE copy of a 3x3 conv weight for up = 1 (uv_launch_conv_up2_phase_weights): [phase a*2+b][N][Cin/32][tap i*2+j][32].  Output pixel
+    // (2y+a, 2x+b) of a conv over the nearest-x2 upsampled image sees only 2x2 distinct source pixels, so each of the four phases is a stride-1 2x2-tap
+    // conv over the SOURCE image whose weights are sums of the original taps: 4 / 9 of the MFMA work.  conv_patch_kernel runs it as a block-uniform mode
+    // when the plan says so (GemmPlan::phase; uv_conv_patch_phase_eligible), else the launcher clears the pointer and the 9-tap form runs.
+    const half_t* W4 = nullptr;
 };
 
 struct AttnParams {
@@ -155,6 +160,7 @@ struct GemmPlan : UvLaunchPlan {
     bool prof_sym = false;           // the profiler is told sym (the 256x320 and X-resident kernels; the 128-wide path passes none)
     int splits = 1, ktps = 0, epi_lds = 0, tile_gn = 0, tile_gm = 0;     // the GemmParams fields "set by the launcher"
     bool gn_emit = false;            // gn_out survives and *gn_emitted is set
+    bool phase = false;              // conv_patch_kernel runs the four 2x2-tap phases of an upsampler conv (GemmParams::W4 survives)
     size_t ws_bytes = 0;             // fp32 partials of a split launch: the caller's workspace if it holds them, else stream-ordered scratch
     unsigned reduce_grid = 0;        // > 0: splitk_reduce_kernel follows
 };
@@ -169,6 +175,8 @@ std::string uv_attention_plan_symbols();
 
 int uv_num_cus();                            // compute units of the current device: the `ncu` uv_launch_gemm plans with
 int uv_launch_gemm(const GemmParams& p, int mode, hipStream_t stream);
+// [Co,Ci,3,3] -> the phase copy [4][Co][Ci/32][4][32] of an upsampler conv (GemmParams::W4): fp32 sums of the taps that fall on one source pixel, one fp16 rounding
+int uv_launch_conv_up2_phase_weights(const half_t* w_oihw, half_t* w4, int Co, int Ci, hipStream_t stream);
 bool uv_linear_takes_big_direct(long M, int N, int K, long ldx = 0);
 // LayerNorm fold around a plain linear: may it emit the row statistics of its output / apply those of its input?  (256x320 direct path,
 // or the 128-wide path when that runs the problem without split-K; the GEGLU consumer is 256x320 only)

@@ -255,6 +255,11 @@ int UNet::finalize(hipStream_t s) {
                 half_t* d3;
                 UV_RUN(derive(k + "#t32", {Co, Ci / 32, 9, 32}, &d3));
                 hipLaunchKernelGGL(permute_conv_weight_t32_kernel, dim3(nb((long)Co * Ci * 9)), dim3(256), 0, s, t.ptr, d3, Co, Ci);
+                if (k.find("upsamplers") != std::string::npos) {      // phase copy (GemmParams::W4): the conv over the nearest-x2 upsampled input as four 2x2-tap convs
+                    half_t* d4;
+                    UV_RUN(derive(k + "#ph4", {4, Co, Ci / 32, 4, 32}, &d4));
+                    UV_RUN(uv_launch_conv_up2_phase_weights(t.ptr, d4, Co, Ci, s));
+                }
             }
         } else if (ends(k, ".attn1.to_q.weight")) {
             std::string p = k.substr(0, k.size() - strlen("to_q.weight"));
@@ -576,6 +581,7 @@ struct Fwd {
         g.korder = (taps == 9 && g.C1 % 64 == 0 && g.C2 % 64 == 0 && u.find(p + ".weight#ti")) ? 1 : 0;
         g.W = W(p + (g.korder ? ".weight#ti" : ".weight#nhwc"));
         if (taps == 9 && stride == 1 && u.find(p + ".weight#t32")) g.W32 = W(p + ".weight#t32");
+        if (taps == 9 && stride == 1 && up == 1 && !b && u.find(p + ".weight#ph4")) g.W4 = W(p + ".weight#ph4");      // the plan takes it or keeps the 9-tap form
         g.bias = W(p + ".bias");
         g.rowbias = rowbias;
         g.ldrb = ldrb;

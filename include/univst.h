@@ -144,7 +144,14 @@ int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm);
  *             the two-phase attention; 0: issued on the forward's own stream (serial; A/B aid).  Results are identical.
  *   "emu_wire_gbps" / "emu_wire_lat_us" (default 0 = off / 3; bench.py --emulate-wire): with a callback communicator that moves nothing, every
  *             exchange occupies the forked stream for latency + (packs on this rank's busiest link) x pack bytes / rate — a 1-GPU box's stand-in for
- *             the xGMI transfer; the accumulated time is univst_unet_query("emu_wire_us"). */
+ *             the xGMI transfer; the accumulated time is univst_unet_query("emu_wire_us").
+ *   "kcat_fold" (default 3, env UNIVST_KCAT_FOLD): linear maps that only add into, or chain onto, a neighbouring GEMM run as extra K columns of it.
+ *             Bit 0 (value 1): proj_out of a spatial transformer (attention.py:151) rides behind the block's second feed-forward linear: one GEMM
+ *             [mid | h3] x [Wp W2 | Wp]^T with K = 5C over the two buffers (a 1x1 conv over their channel concat; weights composed at finalize,
+ *             univst_linear_compose) instead of ff.net.2 + residual followed by proj_out + residual; blocks with a trained temporal attention and banded
+ *             chains keep the two launches.  Bit 1 (value 2): reserved for a resnet's conv_shortcut as a one-tap tail of conv2 — NOT BUILT: the value is
+ *             accepted and the shortcut is launched separately, so 2 runs the graph of 0 and 3 the graph of 1.  0: the two launches everywhere.
+ *             Results differ by fp16 rounding only (one rounding per composed weight instead of one per element of the intermediate tensor). */
 int univst_unet_set_option(univst_unet* h, const char* name, int value);
 /* read-outs of a handle: "emu_wire_us" (modelled wire time issued since the last query; reading resets it), "arena_high_water" (bytes). */
 int univst_unet_query(univst_unet* h, const char* name, double* out);
@@ -436,6 +443,12 @@ int univst_conv3x3_patch(const void* X1, const void* X2, int C1, int C2, int img
 int univst_conv_up2_phase_weights(const void* W_oihw, int Cout, int Cin, void* W4, void* stream);
 int univst_conv3x3_up2_phase(const void* X, int C, int imgs, int Hs, int Ws, const void* W4, const void* bias, void* Y, int Cout, float* gn_out,
                              int gn_group_width, void* stream);
+/* Two chained linears with a residual in between, composed into one (the UNet's ff.net.2 -> proj_out, "kcat_fold"):
+ *   Wp (W2 m + b2 + tb + r) + bp = [Wp W2 | Wp] [m | r] + (Wp (b2 + tb) + bp)
+ * Wp [C][C], W2 [C][K2], b2 / tb / bp [C] fp16 (tb may be null) -> W_out [C][K2 + C] fp16 = [Wp W2 | Wp] and bias_out [C] fp16.  Products and sums are
+ * accumulated in fp32 from the fp16 operands and rounded to fp16 once.  C and K2 multiples of 8. */
+int univst_linear_compose(const void* Wp, const void* W2, const void* b2, const void* tb, const void* bp, int C, int K2, void* W_out, void* bias_out,
+                          void* stream);
 /* A GroupNorm folded into the linear that consumes its output (the per-frame GroupNorm -> proj_in of a transformer block, attention.py:121-123): per
  * statistics unit s (rows_per_stat rows) the weight set W_sets[s][n][k] = fp16(W[n][k] * gamma_k * rstd_{s,g(k)}) and the fp32 bias
  * bias32[s][n] = bias[n] + sum_k W[n][k] * (beta_k - mean_{s,g(k)} * rstd * gamma_k); univst_linear_sets then runs on the RAW rows with the set of each

@@ -148,6 +148,7 @@ SIGNATURES = {
     "univst_conv_nhwc_tapinner": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
     "univst_conv3x3_patch": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
     "univst_conv_up2_phase_weights": (_I, [_P, _I, _I, _P, _P]),
+    "univst_linear_compose": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "univst_conv3x3_up2_phase": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
     "univst_groupnorm_fold_linear": (_I, [_P, _I, _L, _I, _I, _F, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "univst_linear_sets": (_I, [_P, _L, _P, _P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P]),
@@ -402,6 +403,19 @@ def conv3x3_patch(x1, w_t32, bias=None, x2=None, rowbias=None, rows_per_rowbias=
     check(load().univst_conv3x3_patch(ptr(x1), ptr(x2), C1, C2, imgs, Hs, Ws, int(upsample), ptr(w_t32), ptr(bias), ptr(rowbias), rows_per_rowbias,
                                       ptr(residual), ptr(out), Cout, stream_ptr()), "conv3x3_patch")
     return out
+
+
+def linear_compose(wp, w2, b2, tb, bp):
+    """Wp [C, C], W2 [C, K2], biases [C] (tb may be None) -> ([Wp W2 | Wp] as [C, K2 + C], Wp (b2 + tb) + bp as [C]): the second linear of a chain with a
+    residual in between folded into the first one's K loop (fp32 accumulation, one fp16 rounding)."""
+    for t in (wp, w2, b2, bp):
+        _f16(t)
+    C_, K2 = w2.shape
+    w = torch.empty(C_, K2 + C_, device=wp.device, dtype=torch.float16)
+    b = torch.empty(C_, device=wp.device, dtype=torch.float16)
+    check(load().univst_linear_compose(ptr(wp.contiguous()), ptr(w2.contiguous()), ptr(b2), ptr(tb), ptr(bp), C_, K2, ptr(w), ptr(b), stream_ptr()),
+          "linear_compose")
+    return w, b
 
 
 def conv_up2_phase_weights(w):

@@ -60,6 +60,7 @@ int univst_unet_create(const univst_unet_cfg* cfg, univst_unet** out) {
     UV_REQUIRE(h, "unet_create: out of host memory");
     h->impl.cfg = *cfg;
     if (const char* e = getenv("UNIVST_LN_FOLD")) h->impl.ln_fold = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
+    if (const char* e = getenv("UNIVST_KCAT_FOLD")) h->impl.kcat_fold = atoi(e) < 0 ? 0 : (atoi(e) > 3 ? 3 : atoi(e));
     if (const char* e = getenv("UNIVST_GN_PRODUCER")) h->impl.gn_producer = atoi(e) != 0;
     if (const char* e = getenv("UNIVST_GN_FOLD")) h->impl.gn_fold = atoi(e) != 0;
     if (const char* e = getenv("UNIVST_ATTN2_PRE")) h->impl.attn2_fused = atoi(e) ? 2 : 1;
@@ -77,6 +78,11 @@ int univst_unet_set_option(univst_unet* h, const char* name, int value) {
     }
     if (!strcmp(name, "gn_fold")) {
         h->impl.gn_fold = value != 0;
+        return UV_OK;
+    }
+    if (!strcmp(name, "kcat_fold")) {
+        UV_REQUIRE(value >= 0 && value <= 3, "unet_set_option: kcat_fold is 0, 1 (proj_out), 2 (conv_shortcut) or 3 (both)");
+        h->impl.kcat_fold = value;
         return UV_OK;
     }
     if (!strcmp(name, "attn2_fused")) {
@@ -595,6 +601,9 @@ int univst_conv3x3_patch(const void* X1, const void* X2, int C1, int C2, int img
     g.bias = H(bias); g.rowbias = H(rowbias); g.rows_per_rb = rows_per_rb > 0 ? rows_per_rb : 1;
     g.R = H(R); g.ldr = Cout; g.Y = HM(Y); g.ldy = Cout;
     return uv_launch_gemm(g, 1, S(s));
+}
+int univst_linear_compose(const void* Wp, const void* W2, const void* b2, const void* tb, const void* bp, int C, int K2, void* W_out, void* bias_out, void* s) {
+    return uv_launch_linear_compose(H(Wp), H(W2), H(b2), H(tb), H(bp), C, K2, HM(W_out), HM(bias_out), S(s));
 }
 int univst_conv_up2_phase_weights(const void* W_oihw, int Cout, int Cin, void* W4, void* s) {
     UV_REQUIRE(W_oihw && W4, "conv_up2_phase_weights: null argument");

@@ -58,3 +58,6 @@ struct WeightStore {
 int uv_derive_conv_layouts(WeightStore& st, const std::string& key, hipStream_t s);
 // out[i] = fp16(in[i] * f)
 int uv_launch_scale_f16(const half_t* in, half_t* out, long n, float f, hipStream_t s);
+// [Wp W2 | Wp] and Wp (b2 + tb) + bp: two chained linears with a residual in between as ONE linear over K2 + C columns (include/univst.h univst_linear_compose)
+int uv_launch_linear_compose(const half_t* Wp, const half_t* W2, const half_t* b2, const half_t* tb, const half_t* bp, int C, int K2, half_t* W_out,
+                             half_t* bias_out, hipStream_t s);

@@ -29,6 +29,26 @@ __global__ void scale_f16_kernel(const half_t* __restrict__ in, half_t* __restri
     if (i < n) out[i] = (half_t)((float)in[i] * f);
 }
 
+// Two chained linears composed into one (uv_launch_linear_compose): out[n][k] = sum_j Wp[n][j] W2[j][k] for k < K2, Wp[n][k - K2] for the C columns behind
+// them, and (column K2 + C of the grid) the bias Wp (b2 + tb) + bp.  fp32 accumulation in j order, one fp16 rounding.  Runs once per handle: plain FMAs,
+// consecutive threads on consecutive k (W2 rows read coalesced, the Wp element is a broadcast).
+__global__ void linear_compose_kernel(const half_t* __restrict__ Wp, const half_t* __restrict__ W2, const half_t* __restrict__ b2, const half_t* __restrict__ tb,
+                                      const half_t* __restrict__ bp, int C, int K2, half_t* __restrict__ Wout, half_t* __restrict__ bout) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, n = blockIdx.y;
+    const half_t* wp = Wp + (long)n * C;
+    if (k < K2) {
+        float acc = 0.f;
+        for (int j = 0; j < C; ++j) acc = fmaf((float)wp[j], (float)W2[(long)j * K2 + k], acc);
+        Wout[(long)n * (K2 + C) + k] = (half_t)acc;
+    } else if (k < K2 + C) {
+        Wout[(long)n * (K2 + C) + k] = wp[k - K2];
+    } else if (k == K2 + C) {
+        float acc = 0.f;
+        for (int j = 0; j < C; ++j) acc = fmaf((float)wp[j], (float)b2[j] + (tb ? (float)tb[j] : 0.f), acc);
+        bout[n] = (half_t)(acc + (float)bp[n]);
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ arena
@@ -179,6 +199,15 @@ int uv_derive_conv_layouts(WeightStore& st, const std::string& key, hipStream_t 
 
 int uv_launch_scale_f16(const half_t* in, half_t* out, long n, float f, hipStream_t s) {
     hipLaunchKernelGGL(scale_f16_kernel, dim3(nb(n)), dim3(256), 0, s, in, out, n, f);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+
+int uv_launch_linear_compose(const half_t* Wp, const half_t* W2, const half_t* b2, const half_t* tb, const half_t* bp, int C, int K2, half_t* W_out,
+                             half_t* bias_out, hipStream_t s) {
+    UV_REQUIRE(Wp && W2 && b2 && bp && W_out && bias_out && C > 0 && K2 > 0 && C % 8 == 0 && K2 % 8 == 0 && C <= 65535,
+               "linear_compose: null argument, or C=%d / K2=%d not a positive multiple of 8, or C above 65535 (one grid row per output row)", C, K2);
+    hipLaunchKernelGGL(linear_compose_kernel, dim3((unsigned)((K2 + C + 1 + 255) / 256), (unsigned)C), dim3(256), 0, s, Wp, W2, b2, tb, bp, C, K2, W_out, bias_out);
     UV_LAUNCH_CHECK();
     return UV_OK;
 }

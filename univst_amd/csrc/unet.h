@@ -18,6 +18,7 @@ struct UNet : WeightStore {
     int gn_fold = 1;          // the transformer blocks' per-frame GroupNorm folded into proj_in where the weight copies are cheap (round 5; 0: the apply pass)
     int attn2_fused = 2;      // the text cross-attention of a block as one launch where fused.hip serves the shape (round 5): 2 = with the self-attention's out projection in front, 1 = attn2 alone, 0 = q projection + attention + out projection
     int ln_fold = 2;          // transformer-block LayerNorms folded into the neighbouring linears: 0 none, 1 norm1 + norm2, 2 also norm3 (default since round 4; UNIVST_LN_FOLD)
+    int kcat_fold = 3;        // bit 0: proj_out as extra K columns of ff.net.2 — one K = 5C GEMM over the channel concat [mid | h3] with the composed weight "proj_out#kcat" (finalize) instead of two launches; bit 1: reserved for conv_shortcut as a tail of conv2, NOT BUILT (the graph launches the shortcut separately whatever the bit says) (UNIVST_KCAT_FOLD)
     unsigned* d_counter = nullptr;
     // TRAINED temporal layers (fine-tuned 3-D checkpoints): the units whose *_temporal* parameters differ from the identity
     // initialisation (found on the device at finalize).  Empty for 2-D-initialised weights: the graph then skips them exactly.

@@ -414,6 +414,28 @@ int UNet::finalize(hipStream_t s) {
             temporal_attn_active[pre] = 1;
         }
     }
+    // proj_out folded into ff.net.2 (kcat_fold; Fwd::transformer): nothing non-linear lies between the two, so
+    //   Wp (W2 mid + b2 + tb + h3) + bp = [Wp W2 | Wp] [mid | h3] + (Wp (b2 + tb) + bp)
+    // is ONE GEMM with K = 5C over the row [mid | h3].  Product and bias are accumulated in fp32 from the fp16 weights and rounded to fp16 once (the
+    // bias too: the 128-wide kernel and the split-K reduction, which run the deep levels, have no fp32 bias).  Keys as Fwd::conv looks them up.
+    // Derived whatever kcat_fold says (the option may change after finalize), but not for a block with a trained temporal attention, which never takes
+    // the fold.  Cost: C x 5C fp16 per block beside the retained ff.net.2 / proj_out weights — 124 MB for the 16 blocks of SD-v1.5.
+    for (const std::string& k : keys) {
+        if (!ends(k, ".transformer_blocks.0.ff.net.2.weight")) continue;
+        const std::string b = k.substr(0, k.size() - strlen(".ff.net.2.weight")), p = b.substr(0, b.size() - strlen(".transformer_blocks.0"));
+        const WTensor *w2 = find(k), *wp = find(p + ".proj_out.weight#nhwc");
+        if (!wp) wp = find(p + ".proj_out.weight");
+        const WTensor *b2 = find(b + ".ff.net.2.bias"), *tb = find(b + ".attn_temporal.to_out.0.bias"), *bp = find(p + ".proj_out.bias");
+        if (temporal_attn_active.count(b) || !wp || !b2 || !tb || !bp || w2->shape.size() != 2) continue;            // (the graph reports what is missing)
+        const long C = w2->shape[0], K2 = w2->shape[1];
+        long nwp = 1;
+        for (long v : wp->shape) nwp *= v;
+        if (wp->shape[0] != C || nwp != C * C || C % 8 != 0 || K2 != 4 * C || b2->shape[0] != C || tb->shape[0] != C || bp->shape[0] != C) continue;
+        half_t *wo, *bo;
+        UV_RUN(derive(p + ".proj_out#kcat.weight#nhwc", {C, 1, K2 + C}, &wo));
+        UV_RUN(derive(p + ".proj_out#kcat.bias", {C}, &bo));
+        UV_RUN(uv_launch_linear_compose(wp->ptr, w2->ptr, b2->ptr, tb->ptr, bp->ptr, (int)C, (int)K2, wo, bo, s));
+    }
     UV_LAUNCH_CHECK();
     UV_HIP(hipStreamSynchronize(s));
     finalized = true;
@@ -961,6 +983,14 @@ struct Fwd {
         const bool qs2 = u.find(b + ".attn2.to_q.weight#qs") != nullptr;
         const std::string wq2 = b + (qs2 ? ".attn2.to_q.weight#qs" : ".attn2.to_q.weight");
         const bool t_attn = u.temporal_attn_active.count(b) != 0;
+        // proj_out as extra K columns of ff.net.2 (kcat_fold; weights composed at finalize): ONE GEMM with K = 5C over the row [mid | h3] — residual = the
+        // block's input, GroupNorm statistics as proj_out leaves them — replaces ff.net.2 + residual and proj_out + residual: one launch and the round trip
+        // of h4 less per block.  The two halves of the row stay the two buffers they are (a 1x1 conv over the channel concat [mid | h3], as conv_shortcut
+        // runs over [x | skip]): a contiguous 5C-wide buffer needs 5 units of the first-fit arena in one piece where this graph needs 4 + 1, and
+        // raised its high-water mark.  Not with a trained temporal attention (it sits between the two linears) and not with a banded chain.
+        const std::string pkc = p + ".proj_out#kcat";
+        const bool kcat = (u.kcat_fold & 1) && !t_attn && nbands == 1 && C % 8 == 0 && u.find(pkc + ".weight#nhwc") && u.find(pkc + ".bias") &&
+                          rows * 16 * C < (1L << 31);           // (the conv kernels' 32-bit offsets into the wider source)
         UV_RUN(linear(text, u.cfg.cross_attention_dim, (long)B * text_len, u.cfg.cross_attention_dim, b + ".attn2.kv#fused", "",
                    2 * C, kv, 2 * C));
         // round 5, second step: the self-attention's out projection rides in FRONT of the fused text cross-attention (fused.hip, PRE): h2 = to_out(attn1) + h
@@ -1052,6 +1082,7 @@ struct Fwd {
                 UV_RUN(linear(h3 + o, C, brows, C, wff + "#ln", "", 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1, nullptr, lb));
             }
             if (nbands == 1 && lnst) free(lnst);
+            if (kcat) continue;           // ff.net.2 runs inside the K = 5C GEMM behind the loop
             if (!h4 && !(h4 = alloc(rows * C))) return UV_ERR_STATE;
             UV_RUN(linear(mid, 4 * C, brows, 4 * C, b + ".ff.net.2.weight", b + ".ff.net.2.bias", C, h4 + o, C, h3 + o, C, t_attn ? nullptr : tb));
         }
@@ -1062,6 +1093,14 @@ struct Fwd {
             free(kv);
             free(h2);
             if (lnst) free(lnst);
+        }
+        if (kcat) {
+            free(t0);
+            Act am{mid, x.imgs, x.H, x.W, 4 * C}, a3{h3, x.imgs, x.H, x.W, C};
+            UV_RUN(conv(am, &a3, pkc, C, 1, 1, 0, nullptr, x.p, out, 0, true));
+            free(mid);
+            free(h3);
+            return UV_OK;
         }
         free(mid);
         free(h3);

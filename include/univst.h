@@ -153,7 +153,9 @@ int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm);
  *             accepted and the shortcut is launched separately, so 2 runs the graph of 0 and 3 the graph of 1.  0: the two launches everywhere.
  *             Results differ by fp16 rounding only (one rounding per composed weight instead of one per element of the intermediate tensor). */
 int univst_unet_set_option(univst_unet* h, const char* name, int value);
-/* read-outs of a handle: "emu_wire_us" (modelled wire time issued since the last query; reading resets it), "arena_high_water" (bytes). */
+/* read-outs of a handle: "emu_wire_us" (modelled wire time issued since the last query; reading resets it), "arena_high_water" (bytes),
+ * "arena_bytes" (the size of the activation slab: it changes only when a reserve / forward had to replace it by a larger one), "motion_active"
+ * (handles of univst_unet_create_animatediff: the number of motion modules finalize found with a non-zero proj_out). */
 int univst_unet_query(univst_unet* h, const char* name, double* out);
 
 /* ------------------------------------------------------------------ temporal VAE handle
@@ -359,6 +361,35 @@ int univst_motion_query(univst_motion* h, const char* name, double* out);
  * multiple of 8 and ldo of 4, B * F * N < 2^31, N * heads <= 2^24, B <= 65535; anything else is UNIVST_ERR_ARG before any launch. */
 int univst_temporal_attention(const void* qkv, int64_t ldx, const void* pe_qkv, int B, int F, int N, int heads, int head_dim, void* out, int64_t ldo,
                               void* stream);
+
+/* ------------------------------------------------------------------ AnimateDiff UNet3D: a univst_unet of another kind
+ * backbones/animatediff/models/unet.py as animatediff-v2.yaml configures it: the SD-v1.5 2-D UNet run per frame (InflatedConv3d, per-frame
+ * InflatedGroupNorm, attn1 with ONE key source — the frame itself —, no attn_temp, no temporal convs) with a motion module (above) behind every
+ * resnet / transformer pair: layers_per_block per down block, layers_per_block + 1 per up block, one in the mid block between its transformer and its
+ * second resnet (unet_blocks.py:271-276, :382-421, :621-667).  The result is a univst_unet: load_tensor / finalize / reserve / forward / set_option /
+ * query / destroy serve it.  State-dict names are the reference's ("down_blocks.i.resnets.j.*", "...attentions.j.transformer_blocks.0.*",
+ * "down_blocks.i.motion_modules.j.temporal_transformer.*", "up_blocks.i.motion_modules.j.*", "mid_block.motion_modules.0.*", "conv_norm_out.*",
+ * "...pos_encoder.pe").
+ *   create   refuses (no GPU call, naming the field) a level width with width / motion.num_heads outside {40, 80, 160} or no multiple of
+ *            motion.norm_groups, for every level that has motion modules.
+ *   finalize finds on the device the modules whose proj_out (weight and bias) is still all zeros (zero_initialize: no motion checkpoint loaded):
+ *            they are skipped EXACTLY, so a UNet with 2-D weights only equals the per-frame 2-D UNet.  A module none of whose tensors was loaded
+ *            counts as such a module.
+ *   forward  refuses F > 32, F > motion.max_len with position encoding on, and a non-NULL feat_out (this UNet has no feature tap).
+ *            PnP: the same 8 decoder attn1 layers and the same univst_pnp; the window is pnp_utils.py:45 of this backbone,
+ *            eta1 * 50 <= idx < eta2 * 50 (exclusive at the top, eta1 scaled); outside it the registered forward equals the stock one bit for bit;
+ *            alpha / gamma come from the caller (the reference has 0.8 and 2.0).
+ *   univst_unet_set_comm / univst_unet_set_comm_native return UNIVST_ERR_UNSUPPORTED: the frame-axis attention needs every frame on one rank.
+ * The motion chain runs on the UNet's arena and split-K workspace (no per-module arena); univst_unet_query("arena_high_water") reports the mark.
+ * Option "motion_fold" (univst_unet_set_option): 0 = the chain as univst_motion_forward runs it (default).  1 (GroupNorm statistics from the producer's
+ * epilogue folded into proj_in, LayerNorms folded into q|k|v and the GEGLU projection) is NOT BUILT: the value is refused with UNIVST_ERR_UNSUPPORTED. */
+typedef struct {
+    int inflated_groupnorm;      /* 1: resnet / output GroupNorms per frame (resnet.py:21-29); 0: over all frames (the 5-D route of the SD graph) */
+    int motion_levels_mask;      /* bit l: level l has motion modules (motion_module_resolutions [1,2,4,8] -> 15); 0 = use_motion_module false */
+    int motion_mid_block;        /* 1: mid_block.motion_modules.0 exists */
+    univst_motion_cfg motion;    /* channels is ignored (taken per level); the rest as univst_motion_create checks it, per level's width */
+} univst_animatediff_cfg;
+int univst_unet_create_animatediff(const univst_unet_cfg* cfg, const univst_animatediff_cfg* ad, univst_unet** out);
 
 /* ------------------------------------------------------------------ stand-alone operators (also used by tests) */
 /* Y[M,N] = X[M,K] W[N,K]^T + bias + residual; geglu != 0: the diffusers GEGLU projection (FeedForward net[0], attention.py:241) — writes the

@@ -36,6 +36,10 @@ class MotionCfg(C.Structure):
                 ("max_len", C.c_int), ("position_encoding", C.c_int), ("gn_eps", C.c_float), ("ln_eps", C.c_float)]
 
 
+class AnimateDiffCfg(C.Structure):
+    _fields_ = [("inflated_groupnorm", C.c_int), ("motion_levels_mask", C.c_int), ("motion_mid_block", C.c_int), ("motion", MotionCfg)]
+
+
 class VaeCfg(C.Structure):
     _fields_ = [("in_channels", C.c_int), ("out_channels", C.c_int), ("latent_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -73,6 +77,7 @@ SIGNATURES = {
     "univst_abi_version": (_I, []),
     "univst_sd3_shift_window": (_I, [_I, C.c_double, C.c_double, C.POINTER(_I), C.POINTER(_F)]),
     "univst_unet_create": (_I, [C.POINTER(UnetCfg), C.POINTER(_P)]),
+    "univst_unet_create_animatediff": (_I, [C.POINTER(UnetCfg), C.POINTER(AnimateDiffCfg), C.POINTER(_P)]),
     "univst_unet_destroy": (_I, [_P]),
     "univst_unet_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(_L), _I, _P]),
     "univst_unet_finalize": (_I, [_P, _P]),

@@ -4,7 +4,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <new>
+#include <string>
 
 #include "../../include/univst.h"
 #include "comm.h"
@@ -69,8 +71,69 @@ int univst_unet_create(const univst_unet_cfg* cfg, univst_unet** out) {
     *out = h;
     return UV_OK;
 }
+int univst_unet_create_animatediff(const univst_unet_cfg* cfg, const univst_animatediff_cfg* ad, univst_unet** out) {
+    UV_REQUIRE(cfg && ad && out, "unet_create_animatediff: null argument");
+    UV_REQUIRE(ad->inflated_groupnorm == 0 || ad->inflated_groupnorm == 1, "unet_create_animatediff: inflated_groupnorm %d (0 or 1)", ad->inflated_groupnorm);
+    UV_REQUIRE(ad->motion_levels_mask >= 0 && ad->motion_levels_mask <= 15, "unet_create_animatediff: motion_levels_mask %d (bits 0..3: one per level)", ad->motion_levels_mask);
+    UV_REQUIRE(ad->motion_mid_block == 0 || ad->motion_mid_block == 1, "unet_create_animatediff: motion_mid_block %d (0 or 1)", ad->motion_mid_block);
+    UV_REQUIRE(cfg->layers_per_block > 0 && cfg->layers_per_block <= 64, "unet_create_animatediff: layers_per_block %d", cfg->layers_per_block);
+    const bool any = ad->motion_levels_mask != 0 || ad->motion_mid_block;
+    if (any) {
+        UV_REQUIRE(ad->motion.num_heads >= 1 && ad->motion.norm_groups >= 1, "unet_create_animatediff: motion.num_heads %d and motion.norm_groups %d must be positive",
+                   ad->motion.num_heads, ad->motion.norm_groups);
+        for (int l = 0; l < 4; ++l) {
+            if (!((ad->motion_levels_mask >> l) & 1) && !(l == 3 && ad->motion_mid_block)) continue;
+            const int c = cfg->block_out_channels[l];
+            const int d = c % ad->motion.num_heads == 0 ? c / ad->motion.num_heads : 0;
+            UV_REQUIRE(d == 40 || d == 80 || d == 160,
+                       "unet_create_animatediff: block_out_channels[%d]=%d with motion.num_heads %d is no head dim the frame-axis attention has (40, 80, 160)", l, c,
+                       ad->motion.num_heads);
+            UV_REQUIRE(c % ad->motion.norm_groups == 0, "unet_create_animatediff: block_out_channels[%d]=%d is no multiple of motion.norm_groups %d", l, c,
+                       ad->motion.norm_groups);
+            univst_motion_cfg mc = ad->motion;
+            mc.channels = c;
+            UV_RUN(uv_motion_check_cfg(mc));
+        }
+    }
+    univst_unet* h = nullptr;
+    UV_RUN(univst_unet_create(cfg, &h));
+    h->impl.animatediff = true;
+    h->impl.ad = *ad;
+    auto add = [&](const std::string& key, int width) {
+        std::unique_ptr<Motion> m(new (std::nothrow) Motion());
+        if (!m) return false;
+        m->cfg = ad->motion;
+        m->cfg.channels = width;
+        h->impl.motions[key] = std::move(m);
+        return true;
+    };
+    bool ok = true;
+    for (int l = 0; l < 4 && ok; ++l) {
+        if (!((ad->motion_levels_mask >> l) & 1)) continue;
+        for (int j = 0; j < cfg->layers_per_block && ok; ++j) ok = add("down_blocks." + std::to_string(l) + ".motion_modules." + std::to_string(j), cfg->block_out_channels[l]);
+        for (int j = 0; j <= cfg->layers_per_block && ok; ++j) ok = add("up_blocks." + std::to_string(3 - l) + ".motion_modules." + std::to_string(j), cfg->block_out_channels[l]);
+    }
+    if (ok && ad->motion_mid_block) ok = add("mid_block.motion_modules.0", cfg->block_out_channels[3]);
+    if (!ok) {
+        delete h;
+        uv_set_error("unet_create_animatediff: out of host memory");
+        return UV_ERR_STATE;
+    }
+    *out = h;
+    return UV_OK;
+}
 int univst_unet_set_option(univst_unet* h, const char* name, int value) {
     UV_REQUIRE(h && name, "unet_set_option: null argument");
+    if (!strcmp(name, "motion_fold")) {
+        UV_REQUIRE(h->impl.animatediff, "unet_set_option: motion_fold belongs to a handle of univst_unet_create_animatediff");
+        UV_REQUIRE(value == 0 || value == 1, "unet_set_option: motion_fold is 0 or 1");
+        if (value == 1) {
+            uv_set_error("unet_set_option: motion_fold = 1 (the motion modules' norms folded into their GEMMs) is not built; the chain runs unfolded (0)");
+            return UV_ERR_UNSUPPORTED;
+        }
+        h->impl.motion_fold = 0;
+        return UV_OK;
+    }
     if (!strcmp(name, "ln_fold")) {
         UV_REQUIRE(value >= 0 && value <= 2, "unet_set_option: ln_fold is 0, 1 or 2");
         h->impl.ln_fold = value;
@@ -127,6 +190,14 @@ int univst_unet_query(univst_unet* h, const char* name, double* out) {
         *out = (double)h->impl.arena.high_water;
         return UV_OK;
     }
+    if (!strcmp(name, "arena_bytes")) {          // the slab's size: changes only when a forward / reserve had to replace it by a larger one
+        *out = (double)h->impl.arena.size;
+        return UV_OK;
+    }
+    if (!strcmp(name, "motion_active")) {        // AnimateDiff handles: the motion modules finalize found with a non-zero proj_out
+        *out = (double)h->impl.motion_active.size();
+        return UV_OK;
+    }
     uv_set_error("unet_query: unknown quantity '%s'", name);
     return UV_ERR_ARG;
 }
@@ -154,6 +225,10 @@ int univst_unet_forward(univst_unet* h, const void* sample, float t, const void*
 int univst_unet_set_comm(univst_unet* h, int rank, int world, void* comm_ws, int64_t comm_ws_bytes, univst_allreduce_fn ar,
                          univst_kv_exchange_fn kv, void* user) {
     UV_REQUIRE(h && world >= 1 && rank >= 0 && rank < world, "set_comm: bad rank/world");
+    if (h->impl.animatediff) {
+        uv_set_error("set_comm: the AnimateDiff UNet cannot be frame-sharded: its frame-axis attention needs every frame on one rank");
+        return UV_ERR_UNSUPPORTED;
+    }
     UV_REQUIRE(world == 1 || (comm_ws && comm_ws_bytes >= (1 << 17) && ar && kv), "set_comm: world > 1 needs a workspace and both callbacks");
     h->impl.comm_ws = (char*)comm_ws;
     h->impl.comm_ws_bytes = comm_ws_bytes;
@@ -168,6 +243,10 @@ int univst_unet_set_comm(univst_unet* h, int rank, int world, void* comm_ws, int
 
 int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm) {
     UV_REQUIRE(h && comm, "set_comm_native: null argument");
+    if (h->impl.animatediff) {
+        uv_set_error("set_comm_native: the AnimateDiff UNet cannot be frame-sharded: its frame-axis attention needs every frame on one rank");
+        return UV_ERR_UNSUPPORTED;
+    }
     return uv_unet_attach_comm(h->impl, comm);
 }
 

@@ -1,4 +1,5 @@
-// AnimateDiff motion-module handle internals and the frame-axis attention launcher (see motion.hip).
+// AnimateDiff motion-module handle internals and the frame-axis attention launcher (see motion.hip).  A Motion is a handle of its own
+// (univst_motion_*) or one of the modules an AnimateDiff UNet handle owns (unet.h UNet::motions).
 #pragma once
 #include <string>
 #include <vector>
@@ -14,6 +15,16 @@ struct MotionAttn {       // one Temporal_Self attention: LayerNorm, fused q|k|v
 struct MotionBlock {      // one TemporalTransformerBlock, looked up once by finalize
     std::vector<MotionAttn> attn;
     const half_t *ffn_g, *ffn_b, *ff1_w, *ff1_b, *ff2_w, *ff2_b;
+};
+
+struct MotionBufs {       // the activations of one chain run, supplied by whoever owns the memory (Motion::reserve, or the UNet graph's arena)
+    half_t *x[2] = {nullptr, nullptr};      // [M, C] each: the residual stream, ping-pong
+    half_t *h = nullptr;                    // [M, C]: normalised rows
+    half_t *att = nullptr;                  // [M, C]: attention output (may alias h: the q|k|v projection has consumed h by then)
+    half_t *qkv = nullptr;                  // [M, 3C]
+    half_t *ff = nullptr;                   // [M, 4C] (may alias qkv: the two are never live together)
+    float *gn_ws = nullptr, *splitk = nullptr;
+    size_t splitk_bytes = 0;
 };
 
 struct Motion : WeightStore {
@@ -33,6 +44,9 @@ struct Motion : WeightStore {
     int finalize(hipStream_t s);
     int reserve(int B, int F, int N);
     int forward(const half_t* X, half_t* Y, int B, int F, int N, hipStream_t s);
+    // the chain of forward() over caller-supplied buffers (who: the entry point named in messages); no allocation, no synchronisation
+    int check_shape(const char* who, int B, int F, int N) const;
+    int run(const half_t* X, half_t* Y, int B, int F, int N, const MotionBufs& b, hipStream_t s);
     double weight_bytes() const;
 };
 

@@ -11,6 +11,9 @@
 //
 // The position rows: to_q / to_k / to_v have no bias, so W (x + pe_f) = W x + W pe_f.  finalize projects the table once (pe_qkv[f] = Wqkv pe[f],
 // fp32 accumulation, fp16 rows) and the attention kernel adds row f to every q|k|v row of frame f as it loads it.
+//
+// Two owners of the activations: univst_motion_forward carves them from the handle's own arena (Motion::reserve); the AnimateDiff UNet3D graph
+// (unet.hip Fwd::motion) calls Motion::run with buffers of ITS arena and its split-K workspace, so the 21 modules of a UNet hold no arena at all.
 #include <math.h>
 #include <string.h>
 
@@ -398,41 +401,56 @@ int Motion::reserve(int B, int F, int N) {
     return UV_OK;
 }
 
+int Motion::check_shape(const char* who, int B, int F, int N) const {
+    UV_REQUIRE(finalized, "%s: call the handle's finalize after loading weights", who);
+    UV_REQUIRE(B >= 1 && B <= 65535 && N >= 1, "%s: B=%d (1..65535), N=%d (>= 1)", who, B, N);
+    UV_REQUIRE(F >= 1 && F <= UV_MOTION_MAX_F, "%s: F=%d frames (1..%d: what the attention kernel holds)", who, F, UV_MOTION_MAX_F);
+    UV_REQUIRE(!cfg.position_encoding || F <= cfg.max_len, "%s: F=%d frames (1..max_len %d: the position table has max_len rows)", who, F, cfg.max_len);
+    UV_REQUIRE((long)B * F * N < (1L << 31) / 8, "%s: B * F * N = %ld rows (at most 2^28)", who, (long)B * F * N);
+    return UV_OK;
+}
+
 int Motion::forward(const half_t* X, half_t* Y, int B, int F, int N, hipStream_t s) {
     UV_REQUIRE(finalized, "motion_forward: call univst_motion_finalize after loading weights");
-    UV_REQUIRE(X && Y && B >= 1 && B <= 65535 && N >= 1, "motion_forward: B=%d (1..65535), N=%d (>= 1)", B, N);
-    UV_REQUIRE(F >= 1 && F <= UV_MOTION_MAX_F, "motion_forward: F=%d frames (1..%d: what the attention kernel holds)", F, UV_MOTION_MAX_F);
-    UV_REQUIRE(!cfg.position_encoding || F <= cfg.max_len, "motion_forward: F=%d frames (1..max_len %d: the position table has max_len rows)", F, cfg.max_len);
-    UV_REQUIRE((long)B * F * N < (1L << 31) / 8, "motion_forward: B * F * N = %ld rows (at most 2^28)", (long)B * F * N);
+    UV_REQUIRE(X && Y, "motion_forward: null X / Y");
+    UV_RUN(check_shape("motion_forward", B, F, N));
     UV_RUN(reserve(B, F, N));
+    MotionBufs b;
+    b.x[0] = x[0]; b.x[1] = x[1]; b.h = h; b.att = att; b.qkv = qkv; b.ff = ff;
+    b.gn_ws = gn_ws; b.splitk = splitk; b.splitk_bytes = splitk_bytes;
+    return run(X, Y, B, F, N, b, s);
+}
+
+int Motion::run(const half_t* X, half_t* Y, int B, int F, int N, const MotionBufs& b, hipStream_t s) {
     const long M = (long)B * F * N;
     const int C = cfg.channels;
     const int ncu = uv_num_cus();
     auto linear = [&](const half_t* Xi, int K, const half_t* Wt, const half_t* bias, int Nn, half_t* Yo, const half_t* R, int geglu) {
-        const GemmParams g = lin_params(Xi, M, K, Wt, bias, Nn, Yo, R, geglu, splitk, splitk_bytes);
-        // the arena holds what reserve() planned: a launch that wanted more (an operand of another alignment) would allocate behind the caller's back
+        const GemmParams g = lin_params(Xi, M, K, Wt, bias, Nn, Yo, R, geglu, b.splitk, b.splitk_bytes);
+        // the workspace holds what its owner planned: a launch that wanted more (an operand of another alignment) would allocate behind the caller's back
         const GemmPlan pl = uv_gemm_plan(g, 0, ncu);
-        if (pl.rc == UV_OK && pl.ws_bytes > splitk_bytes) {
-            uv_set_error("motion_forward: the %d x %d linear plans %zu bytes of split-K partials, the arena reserved %zu (X / Y must be 16-byte aligned)", Nn, K,
-                         pl.ws_bytes, splitk_bytes);
+        if (pl.rc == UV_OK && pl.ws_bytes > b.splitk_bytes) {
+            uv_set_error("motion_forward: the %d x %d linear plans %zu bytes of split-K partials, the workspace holds %zu (X / Y must be 16-byte aligned)", Nn, K,
+                         pl.ws_bytes, b.splitk_bytes);
             return UV_ERR_STATE;
         }
         return uv_launch_gemm(g, 0, s);
     };
-    UV_RUN(uv_launch_groupnorm(X, nullptr, C, 0, M, N, cfg.norm_groups, cfg.gn_eps, gn_g, gn_b, 0, h, gn_ws, s));
+    half_t* const x[2] = {b.x[0], b.x[1]};
+    UV_RUN(uv_launch_groupnorm(X, nullptr, C, 0, M, N, cfg.norm_groups, cfg.gn_eps, gn_g, gn_b, 0, b.h, b.gn_ws, s));
     int cur = 0;
-    UV_RUN(linear(h, C, in_w, in_b, C, x[cur], nullptr, 0));
+    UV_RUN(linear(b.h, C, in_w, in_b, C, x[cur], nullptr, 0));
     for (const MotionBlock& bk : blocks) {
         for (const MotionAttn& a : bk.attn) {
-            UV_RUN(uv_launch_layernorm(x[cur], C, h, C, a.ln_g, a.ln_b, M, C, cfg.ln_eps, s));
-            UV_RUN(linear(h, C, a.qkv_w, nullptr, 3 * C, qkv, nullptr, 0));
-            UV_RUN(uv_launch_temporal_attention(qkv, 3L * C, a.pe_qkv, B, F, N, cfg.num_heads, C / cfg.num_heads, att, C, s));
-            UV_RUN(linear(att, C, a.out_w, a.out_b, C, x[cur ^ 1], x[cur], 0));
+            UV_RUN(uv_launch_layernorm(x[cur], C, b.h, C, a.ln_g, a.ln_b, M, C, cfg.ln_eps, s));
+            UV_RUN(linear(b.h, C, a.qkv_w, nullptr, 3 * C, b.qkv, nullptr, 0));
+            UV_RUN(uv_launch_temporal_attention(b.qkv, 3L * C, a.pe_qkv, B, F, N, cfg.num_heads, C / cfg.num_heads, b.att, C, s));
+            UV_RUN(linear(b.att, C, a.out_w, a.out_b, C, x[cur ^ 1], x[cur], 0));
             cur ^= 1;
         }
-        UV_RUN(uv_launch_layernorm(x[cur], C, h, C, bk.ffn_g, bk.ffn_b, M, C, cfg.ln_eps, s));
-        UV_RUN(linear(h, C, bk.ff1_w, bk.ff1_b, 8 * C, ff, nullptr, 1));
-        UV_RUN(linear(ff, 4 * C, bk.ff2_w, bk.ff2_b, C, x[cur ^ 1], x[cur], 0));
+        UV_RUN(uv_launch_layernorm(x[cur], C, b.h, C, bk.ffn_g, bk.ffn_b, M, C, cfg.ln_eps, s));
+        UV_RUN(linear(b.h, C, bk.ff1_w, bk.ff1_b, 8 * C, b.ff, nullptr, 1));
+        UV_RUN(linear(b.ff, 4 * C, bk.ff2_w, bk.ff2_b, C, x[cur ^ 1], x[cur], 0));
         cur ^= 1;
     }
     return linear(x[cur], C, outp_w, outp_b, C, Y, X, 0);

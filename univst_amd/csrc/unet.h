@@ -1,10 +1,12 @@
 // UNet handle internals (see unet.hip).
 #pragma once
+#include <memory>
 #include <string>
 #include <unordered_map>
 
 #include "../../include/univst.h"
 #include "model.h"
+#include "motion.h"
 
 struct UNet : WeightStore {
     univst_unet_cfg cfg;
@@ -19,6 +21,13 @@ struct UNet : WeightStore {
     int attn2_fused = 2;      // the text cross-attention of a block as one launch where fused.hip serves the shape (round 5): 2 = with the self-attention's out projection in front, 1 = attn2 alone, 0 = q projection + attention + out projection
     int ln_fold = 2;          // transformer-block LayerNorms folded into the neighbouring linears: 0 none, 1 norm1 + norm2, 2 also norm3 (default since round 4; UNIVST_LN_FOLD)
     int kcat_fold = 3;        // bit 0: proj_out as extra K columns of ff.net.2 — one K = 5C GEMM over the channel concat [mid | h3] with the composed weight "proj_out#kcat" (finalize) instead of two launches; bit 1: reserved for conv_shortcut as a tail of conv2, NOT BUILT (the graph launches the shortcut separately whatever the bit says) (UNIVST_KCAT_FOLD)
+    // AnimateDiff UNet3D (univst_unet_create_animatediff): the per-frame 2-D graph with a motion module behind every resnet / transformer pair.
+    // The modules keep their own weight stores (keys below "<block>.motion_modules.<j>."); their chains run on THIS handle's arena and split-K workspace.
+    bool animatediff = false;
+    univst_animatediff_cfg ad = {};
+    std::unordered_map<std::string, std::unique_ptr<Motion>> motions;     // "down_blocks.0.motion_modules.1" -> module (created by create, every configured slot)
+    std::unordered_map<std::string, int> motion_active;                   // the modules whose proj_out is not all zeros (found on the device at finalize)
+    int motion_fold = 0;      // reserved: the module's GroupNorm / LayerNorms folded into the neighbouring GEMMs — NOT BUILT (set_option refuses 1)
     unsigned* d_counter = nullptr;
     // TRAINED temporal layers (fine-tuned 3-D checkpoints): the units whose *_temporal* parameters differ from the identity
     // initialisation (found on the device at finalize).  Empty for 2-D-initialised weights: the graph then skips them exactly.

@@ -9,6 +9,10 @@
 // resnet.py:335-394, pnp_utils.py:20-111.  Dead work of the reference that is skipped because it is an
 // exact identity for 2-D-initialised weights (verified at finalize): temporal conv1d (dirac, resnet.py:53-55)
 // and temporal attention (zero to_out weight => adds its bias, attention.py:233).
+//
+// The same graph serves the AnimateDiff UNet3D (univst_unet_create_animatediff; backbones/animatediff/models/unet.py, unet_blocks.py:271-276,
+// :382-421, :621-667, resnet.py:10-29, attention.py:327-371, pnp_utils.py:18-109 of that backbone): GroupNorms per frame, attn1 over the frame's own
+// keys, no attn_temp / temporal convs, and a motion module (motion.hip) behind every resnet / transformer pair, its chain on this handle's arena.
 #include <math.h>
 #include <string.h>
 
@@ -192,6 +196,17 @@ int UNet::comm_streams() {
 }
 
 int UNet::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
+    if (animatediff && key) {      // "<block>.motion_modules.<j>.<the module's own key>" goes to that module's store
+        const std::string k(key);
+        const size_t pos = k.find(".motion_modules.");
+        if (pos != std::string::npos) {
+            const size_t dot = k.find('.', pos + strlen(".motion_modules."));
+            auto it = dot == std::string::npos ? motions.end() : motions.find(k.substr(0, dot));
+            UV_REQUIRE(it != motions.end(), "unet_load_tensor: key %s: the config of this handle (motion_levels_mask / motion_mid_block) has no such motion module", key);
+            finalized = false;
+            return it->second->load_tensor(key + dot + 1, dev_ptr, dtype, shape, ndim, s);
+        }
+    }
     UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
     finalized = false;
     return UV_OK;
@@ -426,18 +441,48 @@ int UNet::finalize(hipStream_t s) {
         const WTensor *w2 = find(k), *wp = find(p + ".proj_out.weight#nhwc");
         if (!wp) wp = find(p + ".proj_out.weight");
         const WTensor *b2 = find(b + ".ff.net.2.bias"), *tb = find(b + ".attn_temporal.to_out.0.bias"), *bp = find(p + ".proj_out.bias");
-        if (temporal_attn_active.count(b) || !wp || !b2 || !tb || !bp || w2->shape.size() != 2) continue;            // (the graph reports what is missing)
+        if (temporal_attn_active.count(b) || !wp || !b2 || (!tb && !animatediff) || !bp || w2->shape.size() != 2) continue;            // (the graph reports what is missing; the AnimateDiff block has no attn_temporal)
         const long C = w2->shape[0], K2 = w2->shape[1];
         long nwp = 1;
         for (long v : wp->shape) nwp *= v;
-        if (wp->shape[0] != C || nwp != C * C || C % 8 != 0 || K2 != 4 * C || b2->shape[0] != C || tb->shape[0] != C || bp->shape[0] != C) continue;
+        if (wp->shape[0] != C || nwp != C * C || C % 8 != 0 || K2 != 4 * C || b2->shape[0] != C || (tb && tb->shape[0] != C) || bp->shape[0] != C) continue;
         half_t *wo, *bo;
         UV_RUN(derive(p + ".proj_out#kcat.weight#nhwc", {C, 1, K2 + C}, &wo));
         UV_RUN(derive(p + ".proj_out#kcat.bias", {C}, &bo));
-        UV_RUN(uv_launch_linear_compose(wp->ptr, w2->ptr, b2->ptr, tb->ptr, bp->ptr, (int)C, (int)K2, wo, bo, s));
+        UV_RUN(uv_launch_linear_compose(wp->ptr, w2->ptr, b2->ptr, tb ? tb->ptr : nullptr, bp->ptr, (int)C, (int)K2, wo, bo, s));
     }
     UV_LAUNCH_CHECK();
     UV_HIP(hipStreamSynchronize(s));
+    // the motion modules: derived layouts of each, and which of them do anything — a proj_out (weight and bias) that is still all zeros
+    // (zero_initialize: no motion checkpoint loaded) makes the module proj_out(h) + x = x, and the graph skips it exactly
+    motion_active.clear();
+    if (!motions.empty()) {
+        std::vector<std::string> mk;
+        for (auto& kv : motions)
+            if (!kv.second->weights.empty()) mk.push_back(kv.first);      // (a module none of whose tensors was loaded: as if zero-initialised)
+        unsigned* dc = nullptr;
+        UV_HIP(hipMalloc(&dc, (mk.size() + 1) * sizeof(unsigned)));
+        int rc = hipMemsetAsync(dc, 0, (mk.size() + 1) * sizeof(unsigned), s) == hipSuccess ? UV_OK : UV_ERR_HIP;
+        for (size_t i = 0; i < mk.size() && !rc; ++i) {
+            Motion& m = *motions[mk[i]];
+            rc = m.finalize(s);
+            if (rc) break;
+            for (const char* nm : {"temporal_transformer.proj_out.weight", "temporal_transformer.proj_out.bias"}) {
+                const WTensor* t = m.find(nm);
+                long n = 1;
+                for (long v : t->shape) n *= v;
+                hipLaunchKernelGGL(count_nonzero_kernel, dim3(nb(n)), dim3(256), 0, s, t->ptr, n, dc + i);
+            }
+        }
+        std::vector<unsigned> hm(mk.size() + 1, 0);
+        if (!rc && hipMemcpyAsync(hm.data(), dc, hm.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) rc = UV_ERR_HIP;
+        if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = UV_ERR_HIP;
+        (void)hipFree(dc);
+        if (rc == UV_ERR_HIP) uv_set_error("unet_finalize: a HIP call failed while inspecting the motion modules");
+        if (rc) return rc;
+        for (size_t i = 0; i < mk.size(); ++i)
+            if (hm[i]) motion_active[mk[i]] = 1;
+    }
     finalized = true;
     return UV_OK;
 }
@@ -447,6 +492,8 @@ int UNet::reserve(int B, int F, int H, int Wd) {
     // activations (28 level-0-sized tensors at the high-water mark of the graph) + the small workspaces + split-K partials + the pool of the
     // producers' GroupNorm statistics (Fwd::gst_pool: rows0 / 16 fragments x 32 sub-group slots x 64 tensors x (sum, sumsq) fp32 = 1 KB per row)
     size_t need = (size_t)rows0 * cfg.block_out_channels[0] * 2 * 28 + (64u << 20) + UV_SPLITK_WS_BYTES + (gn_producer ? (size_t)rows0 * 1024 : 0);
+    // a motion chain holds 9 level-sized tensors (x0, x1, h, the 4C-wide q|k|v / hidden buffer, the output, its input) where a transformer block's peak is 8
+    if (animatediff) need += (size_t)rows0 * cfg.block_out_channels[0] * 2 * 4;
     UV_RUN(arena.ensure(need));
     // K/V source tables for this (B,F)
     long key = ((long)B << 20) | F | ((long)rank << 40) | ((long)world << 50);
@@ -516,6 +563,8 @@ int UNet::reserve(int B, int F, int H, int Wd) {
         }
         for (auto* v : {&t2s, &t2p, &c2s, &c2p})
             for (int x : *v) t.push_back(x);
+        if (animatediff)                              // (never sharded: this block sits at 13 BF) attn1 of the per-frame UNet: one key source, the frame itself
+            for (int i = 0; i < B * F; ++i) t.push_back(i);
         int* d;
         UV_HIP(hipMalloc(&d, t.size() * sizeof(int)));
         UV_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -535,7 +584,9 @@ struct Fwd {
     const int *idx_stock = nullptr, *idx_pnp = nullptr, *idx_text = nullptr, *cnt_stock = nullptr, *cnt_pnp = nullptr;
     const float *lw_stock = nullptr, *lw_pnp = nullptr;
     const int *idx2_stock = nullptr, *idx2_pnp = nullptr, *cnt2_stock = nullptr, *cnt2_pnp = nullptr;   // halo phase (ranks > 0 of a frame shard)
+    const int* idx_self = nullptr;     // AnimateDiff: the identity table (frame i reads the keys of frame i)
     float* gn_ws = nullptr;
+    float* mgn_ws = nullptr;           // AnimateDiff: GroupNorm partials of the motion modules (their own group count)
     float* sk_ws = nullptr;        // split-K fp32 partials (UV_SPLITK_WS_BYTES)
     half_t* temb_all = nullptr;    // [B, temb_total]: every resnet's time_emb_proj(SiLU(emb)), one launch per forward
     float* ad_ws = nullptr;
@@ -804,7 +855,7 @@ struct Fwd {
     // resnet.py:335-394
     int resblock(const std::string& p, const Act& x, const Act* skip, int Cout, Act* out) {
         const int Cin = x.C + (skip ? skip->C : 0);
-        const int rps = F * x.H * x.W;
+        const int rps = (u.animatediff && u.ad.inflated_groupnorm ? 1 : F) * x.H * x.W;      // InflatedGroupNorm (resnet.py:21-29): per frame
         half_t* n1 = alloc(x.rows() * Cin);
         if (!n1) return UV_ERR_STATE;
         UV_RUN(groupnorm(x, skip, rps, u.cfg.norm_eps, p + ".norm1", 1, n1, true));
@@ -894,7 +945,9 @@ struct Fwd {
         if (fold) UV_RUN(linear(h, C, rows, C, wqkv + "#ln", "", 3 * C, qkv, 3 * C, nullptr, 0, nullptr, 0, nullptr, lnst));
         else UV_RUN(linear(t0, C, rows, C, wqkv, "", 3 * C, qkv, 3 * C));
         const bool registered = pnp_layer && pnp && pnp->registered;
-        const bool shift = registered && pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f;
+        // AnimateDiff's closure (pnp_utils.py:45 of that backbone): eta1 * 50 <= idx < eta2 * 50, evaluated in double as Python does
+        const bool shift = registered && (u.animatediff ? (double)pnp->idx >= (double)pnp->eta1 * 50.0 && (double)pnp->idx < (double)pnp->eta2 * 50.0
+                                                        : pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f);
         float beta = 0.f;
         if (shift) {
             UV_REQUIRE(B == 3, "PnP attention shift needs the three-branch batch (B=3), got B=%d", B);
@@ -909,6 +962,12 @@ struct Fwd {
         ap.src_cnt = registered ? cnt_pnp : cnt_stock;
         ap.src_logw = registered ? lw_pnp : lw_stock;
         ap.nsrc = registered ? 2 : 3;
+        if (u.animatediff) {      // plain per-frame self-attention (attention.py:344: no video_length, no key frames), registered or not
+            ap.src_idx = idx_self;
+            ap.src_cnt = nullptr;
+            ap.src_logw = nullptr;
+            ap.nsrc = 1;
+        }
         ap.BF = x.imgs; ap.Nq = N; ap.Nkv = N; ap.heads = heads; ap.d = d;
         ap.scale_log2e = 1.4426950408889634f / sqrtf((float)d);
         ap.q_prescaled = qs;
@@ -978,8 +1037,8 @@ struct Fwd {
         half_t *h3 = nullptr, *h4 = nullptr, *q2 = nullptr, *mid = nullptr;
         if (!h2 || !kv) return UV_ERR_STATE;
         half_t *gm2 = W(b + ".norm2.weight"), *bt2 = W(b + ".norm2.bias"), *gm3 = W(b + ".norm3.weight"), *bt3 = W(b + ".norm3.bias");
-        half_t* tb = W(b + ".attn_temporal.to_out.0.bias");
-        if (!gm2 || !bt2 || !gm3 || !bt3 || !tb) return u.missing_error("unet");
+        half_t* tb = u.animatediff ? nullptr : W(b + ".attn_temporal.to_out.0.bias");      // (the AnimateDiff block has no attn_temp)
+        if (!gm2 || !bt2 || !gm3 || !bt3 || (!tb && !u.animatediff)) return u.missing_error("unet");
         const bool qs2 = u.find(b + ".attn2.to_q.weight#qs") != nullptr;
         const std::string wq2 = b + (qs2 ? ".attn2.to_q.weight#qs" : ".attn2.to_q.weight");
         const bool t_attn = u.temporal_attn_active.count(b) != 0;
@@ -1141,6 +1200,49 @@ struct Fwd {
         free(h4);
         return UV_OK;
     }
+
+    // The motion module `p` ("down_blocks.0.motion_modules.1") behind a resnet / transformer pair (unet_blocks.py:411): x becomes module(x), its old
+    // buffer released.  A module whose proj_out is all zeros is the identity and is skipped.  The chain (Motion::run) takes its buffers from this
+    // graph's arena for the length of the call: x0, x1, h (the attention writes its output over h), ONE 4C-wide buffer that is q|k|v during the
+    // attentions and the GEGLU hidden tensor behind them, and the output.
+    int motion(const std::string& p, Act* x) {
+        auto it = u.motions.find(p);
+        if (it == u.motions.end() || !u.motion_active.count(p)) return UV_OK;
+        Motion& m = *it->second;
+        const long M = x->rows();
+        const int C = x->C, N = x->H * x->W;
+        UV_REQUIRE(m.cfg.channels == C, "%s: the module is %d channels wide, the activation %d", p.c_str(), m.cfg.channels, C);
+        UV_RUN(m.check_shape("forward", B, F, N));
+        MotionBufs b;
+        b.x[0] = alloc(M * C);
+        b.x[1] = alloc(M * C);
+        b.h = alloc(M * C);
+        half_t* wide = alloc(M * 4 * C);
+        half_t* y = alloc(M * C);
+        if (!b.x[0] || !b.x[1] || !b.h || !wide || !y) {
+            for (half_t* q : {b.x[0], b.x[1], b.h, wide, y})
+                if (q) free(q);
+            return UV_ERR_STATE;
+        }
+        b.att = b.h;
+        b.qkv = b.ff = wide;
+        b.gn_ws = mgn_ws;
+        b.splitk = sk_ws;
+        b.splitk_bytes = UV_SPLITK_WS_BYTES;
+        const int rc = m.run(x->p, y, B, F, N, b, s);      // (a chain that fails half-way gives its buffers back too: the handle stays usable)
+        free(b.x[0]);
+        free(b.x[1]);
+        free(b.h);
+        free(wide);
+        if (rc) {
+            free(y);
+            return rc;
+        }
+        free(x->p);
+        x->p = y;
+        x->gst = nullptr;
+        return UV_OK;
+    }
 };
 
 int UNet::forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int Wd, int text_len,
@@ -1154,6 +1256,13 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     }
     UV_REQUIRE(B >= 1 && B <= 8 && F >= 1 && H >= 8 && Wd >= 8 && H % 8 == 0 && Wd % 8 == 0,
                "forward: unsupported geometry B=%d F=%d H=%d W=%d (H, W multiples of 8; B <= 8)", B, F, H, Wd);
+    if (animatediff) {
+        UV_REQUIRE(F <= UV_MOTION_MAX_F, "forward: F=%d frames (the AnimateDiff UNet takes at most %d: what the frame-axis attention holds)", F, UV_MOTION_MAX_F);
+        UV_REQUIRE(!ad.motion.position_encoding || motions.empty() || F <= ad.motion.max_len,
+                   "forward: F=%d frames exceed motion.max_len %d (the position table has max_len rows)", F, ad.motion.max_len);
+        UV_REQUIRE(!feat_out, "forward: feat_out must be NULL: the AnimateDiff UNet has no feature tap");
+        UV_REQUIRE(world == 1, "forward: the AnimateDiff UNet cannot be frame-sharded (world=%d)", world);
+    }
     UV_RUN(reserve(B, F, H, Wd));
     clear_missing();
     const int* boc = cfg.block_out_channels;
@@ -1179,6 +1288,13 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     f.ad_ws = (float*)arena.alloc((size_t)F * 2 * boc[3] * 2 * sizeof(float) + 1024);
     f.sk_ws = (float*)arena.alloc(UV_SPLITK_WS_BYTES);
     UV_REQUIRE(f.gn_ws && f.ad_ws && f.sk_ws, "forward: arena too small");
+    if (animatediff) {
+        f.idx_self = tab + BF_ * 13;
+        if (!motions.empty()) {       // (without modules the motion config is not validated and not used)
+            f.mgn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats(B * F, ad.motion.norm_groups) * sizeof(float) + 256);
+            UV_REQUIRE(f.mgn_ws, "forward: arena too small");
+        }
+    }
     if (gn_producer) {             // statistics of up to 64 level-0-sized tensors: [rows/16][G][2] fp32 each (3 MB per tensor at 3 x 16 x 64 x 64: 201 MB, counted in
                                    // reserve()); taken AFTER the mandatory workspaces, so it is the part that degrades first (consumers fall back to their own pass)
         f.gst_left = (size_t)(((long)B * F * H * Wd + 15) / 16) * cfg.norm_num_groups * 2 * 64;
@@ -1233,6 +1349,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
                 f.free(x.p);
                 x = z;
             }
+            if (animatediff) UV_RUN(f.motion(p + ".motion_modules." + std::to_string(j), &x));
             skips.push_back(x);
         }
         if (i != 3) {
@@ -1248,6 +1365,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         UV_RUN(f.resblock("mid_block.resnets.0", x, nullptr, boc[3], &y));
         UV_RUN(f.transformer("mid_block.attentions.0", y, false, cfg.attention_heads[3], &z));
         f.free(y.p);
+        if (animatediff) UV_RUN(f.motion("mid_block.motion_modules.0", &z));
         UV_RUN(f.resblock("mid_block.resnets.1", z, nullptr, boc[3], &w));
         f.free(z.p);
         x = w;   // previous x is skips.back(), still owned by the skip list
@@ -1272,6 +1390,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
                 f.free(x.p);
                 x = z;
             }
+            if (animatediff) UV_RUN(f.motion(p + ".motion_modules." + std::to_string(j), &x));
         }
         if (i != 3) {
             Act y;
@@ -1285,7 +1404,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     // ---- out
     half_t* n = f.alloc(x.rows() * x.C);
     if (!n) return UV_ERR_STATE;
-    UV_RUN(f.groupnorm(x, nullptr, F * x.H * x.W, cfg.norm_eps, "conv_norm_out", 1, n, true));
+    UV_RUN(f.groupnorm(x, nullptr, (animatediff && ad.inflated_groupnorm ? 1 : F) * x.H * x.W, cfg.norm_eps, "conv_norm_out", 1, n, true));
     Act na{n, x.imgs, x.H, x.W, x.C}, y;
     UV_RUN(f.conv(na, nullptr, "conv_out", cfg.out_channels, 9, 1, 0, nullptr, nullptr, &y));
     UV_RUN(uv_launch_nhwc_to_ncfhw(y.p, cfg.out_channels, eps_out, B, cfg.out_channels, F, H * Wd, s));

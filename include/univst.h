@@ -153,9 +153,10 @@ int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm);
  *             accepted and the shortcut is launched separately, so 2 runs the graph of 0 and 3 the graph of 1.  0: the two launches everywhere.
  *             Results differ by fp16 rounding only (one rounding per composed weight instead of one per element of the intermediate tensor). */
 int univst_unet_set_option(univst_unet* h, const char* name, int value);
-/* read-outs of a handle: "emu_wire_us" (modelled wire time issued since the last query; reading resets it), "arena_high_water" (bytes),
- * "arena_bytes" (the size of the activation slab: it changes only when a reserve / forward had to replace it by a larger one), "motion_active"
- * (handles of univst_unet_create_animatediff: the number of motion modules finalize found with a non-zero proj_out). */
+/* read-outs of a handle.  Every *_query below answers "arena_high_water" (bytes), "arena_bytes" (the size of the activation slab: it changes only when
+ * a reserve / forward had to replace it by a larger one) and "weight_bytes" (loaded tensors plus the copies finalize derives; a UNet's own store, without
+ * its motion modules').  This one adds "emu_wire_us" (modelled wire time issued since the last query; reading resets it) and "motion_active" (handles of
+ * univst_unet_create_animatediff: the number of motion modules finalize found with a non-zero proj_out). */
 int univst_unet_query(univst_unet* h, const char* name, double* out);
 
 /* ------------------------------------------------------------------ temporal VAE handle
@@ -211,7 +212,7 @@ int univst_klvae_decode(univst_klvae* h, const void* z, int64_t imgs, int lat_h,
 /* AutoencoderKL.encode(x).latent_dist.parameters: x [imgs, in_channels, H, W] in [-1, 1] -> moments [imgs, 2*latent, H/8, W/8] (mean | logvar; the caller
  * samples).  H, W multiples of 8, H/8 * W/8 a multiple of 8 */
 int univst_klvae_encode(univst_klvae* h, const void* x, int64_t imgs, int H, int W, void* moments, void* stream);
-/* read-outs of a handle: "arena_high_water" (bytes), "arena_bytes" (the arena's size = the need of the largest group so far: the supported way to size
+/* read-outs of a handle: the shared names of univst_unet_query ("arena_bytes" = the need of the largest group so far: the supported way to size
  * pass_bytes — run a group of g images once, read it, and give it as pass_bytes to get groups of g at that image size), "attn_chunks" (chunks per
  * frame of the attention in the last call), "passes" (groups the last call ran its batch in) */
 int univst_klvae_query(univst_klvae* h, const char* name, double* out);
@@ -276,7 +277,7 @@ int univst_clip_finalize(univst_clip* h, void* stream);
  * [B, projection_dim or C] (text_embeds / pooler_output); NULL skips an output.  The first call at a (B, S) sizes the arena; later calls at that
  * size neither allocate nor synchronise. */
 int univst_clip_encode(univst_clip* h, const int64_t* ids, int B, int S, void* last_hidden, void* hidden_states, void* pooled, void* stream);
-/* read-outs of a handle: "arena_high_water" (bytes), "splitk_bytes" (the split-K workspace the arena holds for the linears of the last (B, S)) */
+/* read-outs of a handle: the shared names of univst_unet_query, "splitk_bytes" (the split-K workspace the arena holds for the linears of the last (B, S)) */
 int univst_clip_query(univst_clip* h, const char* name, double* out);
 /* the tower's attention on its own (tests): qkv fp16 [B * S, 3 * heads * 64] = q | k | v rows, q already scaled by 1/8; causal softmax over
  * the S <= 80 positions of each (batch, head) -> out fp16 [B * S, heads * 64] */
@@ -311,8 +312,8 @@ int univst_t5_finalize(univst_t5* h, void* stream);
 /* ids int64 [B, S] (1 <= S <= 512; an id outside [0, vocab) is clamped) -> last_hidden fp16 [B, S, d_model] (after final_layer_norm).  The first
  * call at a (B, S) sizes the arena; later calls at that size neither allocate nor synchronise. */
 int univst_t5_encode(univst_t5* h, const int64_t* ids, int B, int S, void* last_hidden, void* stream);
-/* read-outs of a handle: "arena_high_water" (bytes), "splitk_bytes" (the split-K workspace the arena holds for the linears of the last (B, S)),
- * "weight_bytes" (loaded tensors plus the fused copies and the bias table) */
+/* read-outs of a handle: the shared names of univst_unet_query ("weight_bytes" counts the fused copies and the bias table), "splitk_bytes" (the
+ * split-K workspace the arena holds for the linears of the last (B, S)) */
 int univst_t5_query(univst_t5* h, const char* name, double* out);
 /* the encoder's attention on its own (tests): qkv fp16 [B * S, 3 * heads * 64] = q | k | v rows (no scaling is applied), bias_table fp32
  * [heads][1023] indexed by (key position - query position) + 511; bidirectional softmax over the S <= 512 positions of each (batch, head)
@@ -352,7 +353,7 @@ int univst_motion_finalize(univst_motion* h, void* stream);
 /* X, Y fp16 [B * F, N, channels] rows (Y may not alias X, both 16-byte aligned); F <= 32, and F <= max_len when position_encoding is on.  The first call at a (B, F, N) sizes the arena; later calls at that size
  * neither allocate nor synchronise. */
 int univst_motion_forward(univst_motion* h, const void* X, void* Y, int B, int F, int N, void* stream);
-/* read-outs of a handle: "arena_high_water" (bytes), "weight_bytes" (loaded tensors plus the derived copies) */
+/* read-outs of a handle: the shared names of univst_unet_query */
 int univst_motion_query(univst_motion* h, const char* name, double* out);
 /* the module's attention on its own: softmax attention along the frame axis.  qkv fp16 rows q | k | v, 3 * heads * head_dim wide and ldx halfs apart,
  * row (b * F + f) * N + n, q already carrying the score scale; pe_qkv NULL or fp16 [F][3 * heads * head_dim], row f added to every row of frame f as

@@ -234,6 +234,7 @@ def test_second_forward_is_deterministic_and_allocates_nothing():
     b = m(x, 481, txt).sample
     assert torch.equal(a, b)
     assert hw > 0 and m.native_query("arena_high_water") == hw and m.native_query("arena_bytes") == size
+    assert m.native_query("weight_bytes") > 0 and size >= hw      # the read-outs every handle answers
     with pytest.raises(RuntimeError, match="not built"):
         m.set_native_option("motion_fold", 1)
     assert "motion_fold" not in getattr(m, "_native_options", {}), "a refused value is not recorded: the next rebuild would raise on it"

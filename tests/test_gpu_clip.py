@@ -223,6 +223,25 @@ def test_create_refuses_unsupported_towers():
         NativeCLIPText.from_state_dict(sd, hf_config(cfg))
 
 
+def test_finalize_names_a_tensor_whose_shape_the_config_does_not_give():
+    """mlp.fc1.weight [I, C] replaced by its transpose [C, I] (I = 512, C = 128): finalize names the key and says what is wrong with it"""
+    from univst_amd.text import NativeCLIPText
+    c = case("tiny-gelu")
+    sd = dict(c.sd)
+    key = "text_model.encoder.layers.1.mlp.fc1.weight"
+    sd[key] = sd[key].t().contiguous()
+    with pytest.raises(RuntimeError, match="which the config does not give") as e:
+        NativeCLIPText.from_state_dict(sd, hf_config(c.cfg))
+    assert "encoder.layers.1.mlp.fc1.weight" in str(e.value)
+
+
+def test_shared_readouts():
+    """the read-outs every handle answers: the weights are counted and the slab holds the high-water mark"""
+    c = case("tiny-gelu")
+    c.enc(c.ids)
+    assert c.enc.query("weight_bytes") > 0 and c.enc.query("arena_bytes") >= c.enc.query("arena_high_water") > 0
+
+
 _CHILD = """
 import sys, torch
 sys.path.insert(0, {root!r})

@@ -105,6 +105,7 @@ def test_decode_matches_restated_definition(nat, cfg_name, n, h, w):
     assert got.shape == (n, 3, 8 * h, 8 * w) and got.dtype == torch.float16
     _hold(f"decode_{cfg_name}_{n}x{h}x{w}", got, sd, z, cfg, R.decode)
     assert v.query("attn_chunks") == 1 and v.query("passes") == 1
+    assert v.query("weight_bytes") > 0 and v.query("arena_bytes") >= v.query("arena_high_water") > 0      # the read-outs every handle answers
     assert v.decode(z, return_dict=False)[0].equal(got)
 
 

@@ -249,6 +249,26 @@ def test_arena_is_sized_once_per_shape():
     assert torch.equal(c.mod(xa), ya)
 
 
+def test_finalize_names_a_tensor_whose_shape_the_config_does_not_give():
+    """ff.net.2.weight [C, 4C] given as [C, 2C] at C = 320: finalize names the key and says what is wrong with it"""
+    from univst_amd.motion import NativeMotionModule
+    c = case(320)
+    sd = dict(c.sd)
+    key = "temporal_transformer.transformer_blocks.0.ff.net.2.weight"
+    assert tuple(sd[key].shape) == (320, 1280)
+    sd[key] = sd[key][:, :640].contiguous()
+    with pytest.raises(RuntimeError, match="which the config does not give") as e:
+        NativeMotionModule(sd, config=c.conf)
+    assert key in str(e.value)
+
+
+def test_shared_readouts():
+    """the read-outs every handle answers: the weights are counted and the slab holds the high-water mark"""
+    c = case(320)
+    c.mod(c.x["F7_3x5"])
+    assert c.mod.query("weight_bytes") > 0 and c.mod.query("arena_bytes") >= c.mod.query("arena_high_water") > 0
+
+
 def test_more_frames_than_the_position_table_are_refused():
     from univst_amd import _native
     c = case(320)

@@ -226,6 +226,25 @@ def test_create_and_finalize_refuse_what_is_not_supported():
         NativeT5Encoder.from_state_dict(sd, R.hf_config(cfg))
 
 
+def test_finalize_names_a_tensor_whose_shape_the_config_does_not_give():
+    """DenseReluDense.wo.weight [d_model, d_ff] replaced by its transpose (64 x 128 -> 128 x 64): finalize names the key and says what is wrong with it"""
+    from univst_amd.text import NativeT5Encoder
+    c = case("tiny")
+    sd = dict(c.sd)
+    key = "encoder.block.1.layer.1.DenseReluDense.wo.weight"
+    sd[key] = sd[key].t().contiguous()
+    with pytest.raises(RuntimeError, match="which the config does not give") as e:
+        NativeT5Encoder.from_state_dict(sd, R.hf_config(c.cfg))
+    assert key in str(e.value)
+
+
+def test_shared_readouts():
+    """the read-outs every handle answers: the weights are counted and the slab holds the high-water mark"""
+    c = case("tiny")
+    c.enc(c.ids)
+    assert c.enc.query("weight_bytes") > 0 and c.enc.query("arena_bytes") >= c.enc.query("arena_high_water") > 0
+
+
 # ------------------------------------------------------------------------------------------------------------ the pipeline hook
 def test_pipeline_encode_prompt_uses_the_native_t5_encoder():
     """CustomStableDiffusion3Pipeline.encode_prompt with NativeT5Encoder as text_encoder_3 (native CLIP towers, stub tokenizers): the T5 rows of the

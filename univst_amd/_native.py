@@ -227,9 +227,9 @@ def load():
     return _lib
 
 
-def check(rc: int, what: str = ""):
+def check(rc: int, what: str = "", lib=None):
     if rc != 0:
-        msg = load().univst_last_error().decode(errors="replace")
+        msg = (lib or load()).univst_last_error().decode(errors="replace")
         raise RuntimeError(f"libunivst_hip {what} failed (code {rc}): {msg}")
 
 
@@ -246,6 +246,99 @@ def _f16(t: torch.Tensor, name="tensor"):
         raise ValueError(f"{name}: expected a contiguous fp16 CUDA/HIP tensor, got {t.dtype} {t.device} "
                          f"contiguous={t.is_contiguous()}")
     return t
+
+
+# --------------------------------------------------------------------------- model handles
+def build_handle(lib, kind, create_args, items, stream, synchronize, *, other_dtype, device=None, create=None, load_what=None):
+    """A loaded handle of ``univst_<kind>_*``: create (``create``: another entry than ``univst_<kind>_create``), one ``load_tensor`` per (key, tensor) of
+    ``items`` on ``stream`` (the raw pointer), ``finalize`` where the ABI has one, and ``synchronize()`` for that stream, since the sources may be
+    temporaries.  fp16 and fp32 tensors go up as they are, every other dtype as ``other_dtype``; ``device`` moves host tensors first.  Whatever raises on
+    the way, the handle is destroyed before the exception goes on.  ``load_what``: the prefix of a failed load's message (default
+    ``<kind>_load_tensor``).  ``lib``, ``stream`` and ``synchronize`` are arguments so that a stub can drive this without a GPU."""
+    create = create or f"univst_{kind}_create"
+    h = C.c_void_p()
+    check(getattr(lib, create)(*create_args, C.byref(h)), create[len("univst_"):], lib)
+    try:
+        load_tensor, finalize = getattr(lib, f"univst_{kind}_load_tensor"), getattr(lib, f"univst_{kind}_finalize", None)
+        for key, t in items:
+            t = t.detach() if device is None else t.detach().to(device=device)
+            t = t.to(t.dtype if t.dtype in (torch.float16, torch.float32) else other_dtype).contiguous()
+            shape = (C.c_int64 * max(1, t.dim()))(*t.shape)      # (a 0-dim tensor still gets a valid pointer)
+            check(load_tensor(h, key.encode(), t.data_ptr(), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), stream),
+                  f"{load_what or kind + '_load_tensor'}({key})", lib)
+        if finalize is not None:
+            check(finalize(h, stream), f"{kind}_finalize", lib)
+        synchronize()
+    except BaseException:
+        getattr(lib, f"univst_{kind}_destroy")(h)
+        raise
+    return h
+
+
+def load_handle(kind, create_args, items, **kw):
+    """``build_handle`` on the library and torch's current stream"""
+    return build_handle(load(), kind, create_args, items, stream_ptr(), torch.cuda.current_stream().synchronize, **kw)
+
+
+class NativeHandle:
+    """What the wrappers of a model handle share: the handle ``_h`` of ``univst_<_kind>_*`` is destroyed with the object, ``query`` reads it out, and
+    ``_gpu_only`` refuses what is not a device tensor (``_noun``: the model's name in that message)."""
+    _kind = _noun = None
+    _h = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                getattr(load(), f"univst_{self._kind}_destroy")(h)
+            except Exception:      # interpreter shutdown: the module's own attributes may already be gone
+                pass
+            self._h = None
+
+    def query(self, name):
+        """a read-out of the handle (include/univst.h ``univst_<kind>_query``): ``arena_high_water``, ``arena_bytes``, ``weight_bytes`` and the handle's own"""
+        out = C.c_double()
+        check(getattr(load(), f"univst_{self._kind}_query")(self._h, name.encode(), C.byref(out)), f"{self._kind}_query({name})")
+        return int(out.value)
+
+    def _gpu_only(self, t, what):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.{what}: the native {self._noun} runs on the GPU only (no CPU / eager fallback); got "
+                               f"{'a ' + str(t.device) + ' tensor' if torch.is_tensor(t) else type(t).__name__}")
+        return t
+
+    @staticmethod
+    def merge_config(defaults, config, keep_none=False):
+        """``defaults`` with the entries a dict or an object ``config`` has for its keys; other keys are dropped, and so are ``None`` values unless
+        ``keep_none``"""
+        cfg = dict(defaults)
+        if config is not None:
+            for k in defaults:
+                if (k in config) if isinstance(config, dict) else hasattr(config, k):
+                    v = config[k] if isinstance(config, dict) else getattr(config, k)
+                    if v is not None or keep_none:
+                        cfg[k] = v
+        return cfg
+
+
+class NativeModuleFacade(NativeHandle):
+    """``NativeHandle`` plus what the call sites touch of an nn.Module, for the wrappers that are none"""
+
+    @property
+    def dtype(self):
+        return torch.float16
+
+    def to(self, *a, **k):
+        return self
+
+    def cuda(self, *a, **k):
+        return self
+
+    def requires_grad_(self, *a, **k):
+        return self
+
+    def eval(self):
+        return self
 
 
 # --------------------------------------------------------------------------- stand-alone operator wrappers

@@ -347,18 +347,9 @@ class UNet3DConditionModel(nn.Module):
         cfg = _native.UnetCfg(c.in_channels, c.out_channels, (C.c_int * 4)(*c.block_out_channels), c.layers_per_block, c.cross_attention_dim,
                               (C.c_int * 4)(*self._heads_per_level), c.norm_num_groups, c.norm_eps, int(c.flip_sin_to_cos), float(c.freq_shift))
         ad = _native.AnimateDiffCfg(int(bool(c.use_inflated_groupnorm)), self._motion_mask, int(self._motion_mid), self._motion_cfg())
-        h = C.c_void_p()
-        _native.check(lib.univst_unet_create_animatediff(C.byref(cfg), C.byref(ad), C.byref(h)), "unet_create_animatediff")
+        h = _native.load_handle("unet", (C.byref(cfg), C.byref(ad)), self.state_dict().items(), other_dtype=torch.float32,
+                                create="univst_unet_create_animatediff", load_what="load_tensor")
         try:
-            stream = _native.stream_ptr()
-            for name, t in self.state_dict().items():
-                t, dt = (t, 0) if t.dtype == torch.float16 else (t.float(), 1)
-                t = t.contiguous()
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                _native.check(lib.univst_unet_load_tensor(h, name.encode(), t.data_ptr(), dt, shape, t.dim(), stream), f"load_tensor({name})")
-                del t
-            torch.cuda.current_stream().synchronize()   # sources may be temporaries
-            _native.check(lib.univst_unet_finalize(h, stream), "unet_finalize")
             for k, v in list(getattr(self, "_native_options", {}).items()):
                 if lib.univst_unet_set_option(h, k.encode(), int(v)) != 0:
                     del self._native_options[k]      # (recorded before a handle existed: refused now, and not to be met again by the next rebuild)

@@ -374,25 +374,10 @@ class UNetPseudo3DConditionModel(nn.Module):
         cfg = _native.UnetCfg(c.in_channels, c.out_channels, (C.c_int * 4)(*c.block_out_channels), c.layers_per_block,
                               c.cross_attention_dim, (C.c_int * 4)(*self._heads_per_level), c.norm_num_groups, c.norm_eps,
                               int(c.flip_sin_to_cos), float(c.freq_shift))
-        h = C.c_void_p()
-        _native.check(lib.univst_unet_create(C.byref(cfg), C.byref(h)), "unet_create")
-        stream = _native.stream_ptr()
-        for name, t in self.state_dict().items():
-            if t.dtype == torch.float16:
-                dt = 0
-            elif t.dtype == torch.float32:
-                dt = 1
-            else:
-                t, dt = t.float(), 1
-            t = t.contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _native.check(lib.univst_unet_load_tensor(h, name.encode(), t.data_ptr(), dt, shape, t.dim(), stream),
-                          f"load_tensor({name})")
-        torch.cuda.current_stream().synchronize()   # sources may be temporaries
-        _native.check(lib.univst_unet_finalize(h, stream), "unet_finalize")
+        h = _native.load_handle("unet", (C.byref(cfg),), self.state_dict().items(), other_dtype=torch.float32, load_what="load_tensor")
+        self._native_handle = h      # (owned from here on: __del__ / the next rebuild destroys it, also when an option below is refused)
         for k, v in getattr(self, "_native_options", {}).items():
             _native.check(lib.univst_unet_set_option(h, k.encode(), int(v)), f"unet_set_option({k})")
-        self._native_handle = h
         self._native_sum = self._content_checksum()
         self._native_dirty = False
         self._native_fp = fp

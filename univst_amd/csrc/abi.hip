@@ -35,6 +35,29 @@ struct univst_unet {
     UNet impl;
 };
 
+// destroy / load_tensor / finalize of a handle struct univst_<name> { <Model> impl; }: the same three entries for every fp16 handle
+#define UV_HANDLE_ABI(name)                                                                                                                        \
+    int univst_##name##_destroy(univst_##name* h) {                                                                                                \
+        delete h;                                                                                                                                  \
+        return UV_OK;                                                                                                                              \
+    }                                                                                                                                              \
+    int univst_##name##_load_tensor(univst_##name* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {        \
+        UV_REQUIRE(h, "null handle");                                                                                                              \
+        return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));                                                                              \
+    }                                                                                                                                              \
+    int univst_##name##_finalize(univst_##name* h, void* s) {                                                                                      \
+        UV_REQUIRE(h, "null handle");                                                                                                              \
+        return h->impl.finalize(S(s));                                                                                                             \
+    }
+// the read-outs every fp16 handle answers (the *_query entries try this first, then their own names)
+static bool model_query(const Model& m, const char* name, double* out) {
+    if (!strcmp(name, "arena_high_water")) *out = (double)m.arena.high_water;
+    else if (!strcmp(name, "arena_bytes")) *out = (double)m.arena.size;      // the slab's size: changes only when a forward / reserve had to replace it by a larger one
+    else if (!strcmp(name, "weight_bytes")) *out = m.weight_bytes();
+    else return false;
+    return true;
+}
+
 extern "C" {
 
 const char* univst_last_error(void) { return g_err; }
@@ -186,14 +209,7 @@ int univst_unet_query(univst_unet* h, const char* name, double* out) {
         h->impl.emu_wire_us = 0.0;
         return UV_OK;
     }
-    if (!strcmp(name, "arena_high_water")) {
-        *out = (double)h->impl.arena.high_water;
-        return UV_OK;
-    }
-    if (!strcmp(name, "arena_bytes")) {          // the slab's size: changes only when a forward / reserve had to replace it by a larger one
-        *out = (double)h->impl.arena.size;
-        return UV_OK;
-    }
+    if (model_query(h->impl, name, out)) return UV_OK;
     if (!strcmp(name, "motion_active")) {        // AnimateDiff handles: the motion modules finalize found with a non-zero proj_out
         *out = (double)h->impl.motion_active.size();
         return UV_OK;
@@ -201,18 +217,7 @@ int univst_unet_query(univst_unet* h, const char* name, double* out) {
     uv_set_error("unet_query: unknown quantity '%s'", name);
     return UV_ERR_ARG;
 }
-int univst_unet_destroy(univst_unet* h) {
-    delete h;
-    return UV_OK;
-}
-int univst_unet_load_tensor(univst_unet* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
-}
-int univst_unet_finalize(univst_unet* h, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.finalize(S(s));
-}
+UV_HANDLE_ABI(unet)
 int univst_unet_reserve(univst_unet* h, int B, int F, int Hh, int W) {
     UV_REQUIRE(h, "null handle");
     return h->impl.reserve(B, F, Hh, W);
@@ -285,28 +290,14 @@ int univst_clip_create(const univst_clip_cfg* cfg, univst_clip** out) {
     *out = h;
     return UV_OK;
 }
-int univst_clip_destroy(univst_clip* h) {
-    delete h;
-    return UV_OK;
-}
-int univst_clip_load_tensor(univst_clip* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
-}
-int univst_clip_finalize(univst_clip* h, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.finalize(S(s));
-}
+UV_HANDLE_ABI(clip)
 int univst_clip_encode(univst_clip* h, const int64_t* ids, int B, int Sq, void* last_hidden, void* hidden_states, void* pooled, void* s) {
     UV_REQUIRE(h && ids, "clip_encode: null argument");
     return h->impl.encode(ids, B, Sq, HM(last_hidden), HM(hidden_states), HM(pooled), S(s));
 }
 int univst_clip_query(univst_clip* h, const char* name, double* out) {
     UV_REQUIRE(h && name && out, "clip_query: null argument");
-    if (!strcmp(name, "arena_high_water")) {
-        *out = (double)h->impl.arena.high_water;
-        return UV_OK;
-    }
+    if (model_query(h->impl, name, out)) return UV_OK;
     if (!strcmp(name, "splitk_bytes")) {
         *out = (double)h->impl.splitk_bytes;
         return UV_OK;
@@ -329,34 +320,16 @@ int univst_t5_create(const univst_t5_cfg* cfg, univst_t5** out) {
     *out = h;
     return UV_OK;
 }
-int univst_t5_destroy(univst_t5* h) {
-    delete h;
-    return UV_OK;
-}
-int univst_t5_load_tensor(univst_t5* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
-}
-int univst_t5_finalize(univst_t5* h, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.finalize(S(s));
-}
+UV_HANDLE_ABI(t5)
 int univst_t5_encode(univst_t5* h, const int64_t* ids, int B, int Sq, void* last_hidden, void* s) {
     UV_REQUIRE(h && ids && last_hidden, "t5_encode: null argument");
     return h->impl.encode(ids, B, Sq, HM(last_hidden), S(s));
 }
 int univst_t5_query(univst_t5* h, const char* name, double* out) {
     UV_REQUIRE(h && name && out, "t5_query: null argument");
-    if (!strcmp(name, "arena_high_water")) {
-        *out = (double)h->impl.arena.high_water;
-        return UV_OK;
-    }
+    if (model_query(h->impl, name, out)) return UV_OK;
     if (!strcmp(name, "splitk_bytes")) {
         *out = (double)h->impl.splitk_bytes;
-        return UV_OK;
-    }
-    if (!strcmp(name, "weight_bytes")) {
-        *out = h->impl.weight_bytes();
         return UV_OK;
     }
     uv_set_error("t5_query: unknown quantity '%s'", name);
@@ -378,32 +351,14 @@ int univst_motion_create(const univst_motion_cfg* cfg, univst_motion** out) {
     *out = h;
     return UV_OK;
 }
-int univst_motion_destroy(univst_motion* h) {
-    delete h;
-    return UV_OK;
-}
-int univst_motion_load_tensor(univst_motion* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
-}
-int univst_motion_finalize(univst_motion* h, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.finalize(S(s));
-}
+UV_HANDLE_ABI(motion)
 int univst_motion_forward(univst_motion* h, const void* X, void* Y, int B, int F, int N, void* s) {
     UV_REQUIRE(h && X && Y, "motion_forward: null argument");
     return h->impl.forward(H(X), HM(Y), B, F, N, S(s));
 }
 int univst_motion_query(univst_motion* h, const char* name, double* out) {
     UV_REQUIRE(h && name && out, "motion_query: null argument");
-    if (!strcmp(name, "arena_high_water")) {
-        *out = (double)h->impl.arena.high_water;
-        return UV_OK;
-    }
-    if (!strcmp(name, "weight_bytes")) {
-        *out = h->impl.weight_bytes();
-        return UV_OK;
-    }
+    if (model_query(h->impl, name, out)) return UV_OK;
     uv_set_error("motion_query: unknown quantity '%s'", name);
     return UV_ERR_ARG;
 }
@@ -428,18 +383,7 @@ int univst_vae_create(const univst_vae_cfg* cfg, univst_vae** out) {
     *out = h;
     return UV_OK;
 }
-int univst_vae_destroy(univst_vae* h) {
-    delete h;
-    return UV_OK;
-}
-int univst_vae_load_tensor(univst_vae* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
-}
-int univst_vae_finalize(univst_vae* h, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.finalize(S(s));
-}
+UV_HANDLE_ABI(vae)
 int univst_vae_decode(univst_vae* h, const void* z, int64_t imgs, int num_frames, int lat_h, int lat_w, void* out, void* s) {
     UV_REQUIRE(h && z && out, "vae_decode: null argument");
     return h->impl.decode(H(z), imgs, num_frames, lat_h, lat_w, HM(out), S(s));
@@ -476,18 +420,7 @@ int univst_klvae_create(const univst_klvae_cfg* cfg, univst_klvae** out) {
     *out = h;
     return UV_OK;
 }
-int univst_klvae_destroy(univst_klvae* h) {
-    delete h;
-    return UV_OK;
-}
-int univst_klvae_load_tensor(univst_klvae* h, const char* key, const void* p, int dtype, const int64_t* shape, int ndim, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.load_tensor(key, p, dtype, shape, ndim, S(s));
-}
-int univst_klvae_finalize(univst_klvae* h, void* s) {
-    UV_REQUIRE(h, "null handle");
-    return h->impl.finalize(S(s));
-}
+UV_HANDLE_ABI(klvae)
 int univst_klvae_decode(univst_klvae* h, const void* z, int64_t imgs, int lat_h, int lat_w, void* out, void* s) {
     UV_REQUIRE(h && z && out, "klvae_decode: null argument");
     return h->impl.decode(H(z), imgs, lat_h, lat_w, HM(out), S(s));
@@ -498,14 +431,7 @@ int univst_klvae_encode(univst_klvae* h, const void* x, int64_t imgs, int Hh, in
 }
 int univst_klvae_query(univst_klvae* h, const char* name, double* out) {
     UV_REQUIRE(h && name && out, "klvae_query: null argument");
-    if (!strcmp(name, "arena_high_water")) {
-        *out = (double)h->impl.arena.high_water;
-        return UV_OK;
-    }
-    if (!strcmp(name, "arena_bytes")) {
-        *out = (double)h->impl.arena.size;
-        return UV_OK;
-    }
+    if (model_query(h->impl, name, out)) return UV_OK;
     if (!strcmp(name, "attn_chunks")) {
         *out = (double)h->impl.attn_chunks;
         return UV_OK;

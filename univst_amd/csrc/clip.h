@@ -12,10 +12,8 @@ struct ClipLayer {      // the weights of one encoder layer, looked up once by f
     const half_t *ln1_g, *ln1_b, *qkv_w, *qkv_b, *out_w, *out_b, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
 };
 
-struct Clip : WeightStore {
+struct Clip : Model {
     univst_clip_cfg cfg;
-    Arena arena;
-    bool finalized = false;
     std::vector<ClipLayer> layers;
     const half_t *tok = nullptr, *pos = nullptr, *fln_g = nullptr, *fln_b = nullptr, *proj = nullptr;
     // activations of one (B, S), carved from the arena by the first encode at that size
@@ -24,7 +22,7 @@ struct Clip : WeightStore {
     float* splitk = nullptr;
     size_t splitk_bytes = 0;
 
-    ~Clip();
+    Clip() : Model("clip") {}
     int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
     int finalize(hipStream_t s);
     int reserve(int B, int S);

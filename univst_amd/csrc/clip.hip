@@ -221,24 +221,6 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const int64_t* __restric
     for (int c = threadIdx.x * 8; c < C; c += 256 * 8) *reinterpret_cast<h8*>(out + (long)b * C + c) = *reinterpret_cast<const h8*>(src + c);
 }
 
-GemmParams lin_params(const half_t* X, long M, int K, const half_t* Wt, const half_t* bias, int N, half_t* Y, const half_t* R, float* ws, size_t ws_bytes) {
-    GemmParams g;
-    g.X = X;
-    g.ldx = K;
-    g.M = (int)M;
-    g.K = K;
-    g.N = N;
-    g.W = Wt;
-    g.bias = bias;
-    g.Y = Y;
-    g.ldy = N;
-    g.R = R;
-    g.ldr = N;
-    g.partial = ws;
-    g.partial_bytes = ws_bytes;
-    return g;
-}
-
 }  // namespace
 
 int uv_launch_clip_attention(const half_t* qkv, int B, int S, int heads, half_t* out, hipStream_t s) {
@@ -263,16 +245,10 @@ int uv_clip_check_cfg(const univst_clip_cfg& c) {
     return UV_OK;
 }
 
-Clip::~Clip() {
-    if (arena.base) (void)hipFree(arena.base);
-}
-
 int Clip::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
     UV_REQUIRE(key, "clip_load_tensor: null key");
     if (!strncmp(key, "text_model.", 11)) key += 11;      // checkpoints (and CLIPTextModelWithProjection) prefix the tower's keys; text_projection.weight is top level
-    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
-    finalized = false;
-    return UV_OK;
+    return Model::load_tensor(key, dev_ptr, dtype, shape, ndim, s);
 }
 
 int Clip::finalize(hipStream_t s) {
@@ -280,49 +256,32 @@ int Clip::finalize(hipStream_t s) {
     clear_missing();
     layers.clear();
     const int C = cfg.hidden_size, I = cfg.intermediate_size;
-    auto shaped = [&](const std::string& k, std::vector<long> want) -> const half_t* {
-        const WTensor* t = find(k);
-        if (!t) {
-            (void)W(k);      // records the missing key
-            return nullptr;
-        }
-        if (t->shape != want) {
-            uv_set_error("clip_finalize: %s has %zu dims / first dim %ld, which the config does not give", k.c_str(), t->shape.size(), t->shape[0]);
-            return nullptr;
-        }
-        return t->ptr;
-    };
-#define CLIP_W(dst, key, ...)                                         \
-    do {                                                              \
-        (dst) = shaped((key), {__VA_ARGS__});                         \
-        if (!(dst)) return missing.empty() ? UV_ERR_ARG : missing_error("clip"); \
-    } while (0)
-    CLIP_W(tok, "embeddings.token_embedding.weight", cfg.vocab_size, C);
-    CLIP_W(pos, "embeddings.position_embedding.weight", cfg.max_positions, C);
-    CLIP_W(fln_g, "final_layer_norm.weight", C);
-    CLIP_W(fln_b, "final_layer_norm.bias", C);
+    UV_SHAPED(tok, "embeddings.token_embedding.weight", cfg.vocab_size, C);
+    UV_SHAPED(pos, "embeddings.position_embedding.weight", cfg.max_positions, C);
+    UV_SHAPED(fln_g, "final_layer_norm.weight", C);
+    UV_SHAPED(fln_b, "final_layer_norm.bias", C);
     proj = nullptr;
-    if (cfg.projection_dim) CLIP_W(proj, "text_projection.weight", cfg.projection_dim, C);
+    if (cfg.projection_dim) UV_SHAPED(proj, "text_projection.weight", cfg.projection_dim, C);
     for (int l = 0; l < cfg.num_layers; ++l) {
         const std::string p = "encoder.layers." + std::to_string(l) + ".";
         ClipLayer L;
-        CLIP_W(L.ln1_g, p + "layer_norm1.weight", C);
-        CLIP_W(L.ln1_b, p + "layer_norm1.bias", C);
-        CLIP_W(L.ln2_g, p + "layer_norm2.weight", C);
-        CLIP_W(L.ln2_b, p + "layer_norm2.bias", C);
-        CLIP_W(L.out_w, p + "self_attn.out_proj.weight", C, C);
-        CLIP_W(L.out_b, p + "self_attn.out_proj.bias", C);
-        CLIP_W(L.fc1_w, p + "mlp.fc1.weight", I, C);
-        CLIP_W(L.fc1_b, p + "mlp.fc1.bias", I);
-        CLIP_W(L.fc2_w, p + "mlp.fc2.weight", C, I);
-        CLIP_W(L.fc2_b, p + "mlp.fc2.bias", C);
+        UV_SHAPED(L.ln1_g, p + "layer_norm1.weight", C);
+        UV_SHAPED(L.ln1_b, p + "layer_norm1.bias", C);
+        UV_SHAPED(L.ln2_g, p + "layer_norm2.weight", C);
+        UV_SHAPED(L.ln2_b, p + "layer_norm2.bias", C);
+        UV_SHAPED(L.out_w, p + "self_attn.out_proj.weight", C, C);
+        UV_SHAPED(L.out_b, p + "self_attn.out_proj.bias", C);
+        UV_SHAPED(L.fc1_w, p + "mlp.fc1.weight", I, C);
+        UV_SHAPED(L.fc1_b, p + "mlp.fc1.bias", I);
+        UV_SHAPED(L.fc2_w, p + "mlp.fc2.weight", C, I);
+        UV_SHAPED(L.fc2_b, p + "mlp.fc2.bias", C);
         const half_t *qw, *kw, *vw, *qb, *kb, *vb;
-        CLIP_W(qw, p + "self_attn.q_proj.weight", C, C);
-        CLIP_W(kw, p + "self_attn.k_proj.weight", C, C);
-        CLIP_W(vw, p + "self_attn.v_proj.weight", C, C);
-        CLIP_W(qb, p + "self_attn.q_proj.bias", C);
-        CLIP_W(kb, p + "self_attn.k_proj.bias", C);
-        CLIP_W(vb, p + "self_attn.v_proj.bias", C);
+        UV_SHAPED(qw, p + "self_attn.q_proj.weight", C, C);
+        UV_SHAPED(kw, p + "self_attn.k_proj.weight", C, C);
+        UV_SHAPED(vw, p + "self_attn.v_proj.weight", C, C);
+        UV_SHAPED(qb, p + "self_attn.q_proj.bias", C);
+        UV_SHAPED(kb, p + "self_attn.k_proj.bias", C);
+        UV_SHAPED(vb, p + "self_attn.v_proj.bias", C);
         // fused q|k|v projection [3C, C] + [3C]; the attention scale d^-0.5 = 1/8 rides on the q rows (a power of two: exact in fp16 short of
         // underflow), which leaves the kernel the factor log2(e) only
         half_t *fw, *fb;
@@ -338,7 +297,6 @@ int Clip::finalize(hipStream_t s) {
         L.qkv_b = fb;
         layers.push_back(L);
     }
-#undef CLIP_W
     UV_HIP(hipStreamSynchronize(s));
     finalized = true;
     return UV_OK;
@@ -350,37 +308,12 @@ int Clip::reserve(int B, int S) {
     rB = rS = 0;
     const long M = (long)B * S;
     const int C = cfg.hidden_size, I = cfg.intermediate_size;
-    // split-K partials of the four linears, as the GEMM launcher will plan them
-    splitk_bytes = 0;
-    const int shapes[4][2] = {{3 * C, C}, {C, C}, {I, C}, {C, I}};
-    for (auto& nk : shapes) {      // (the plan looks at pointers for null and alignment only: the 256-aligned embedding table stands in for all of them)
-        half_t* any = const_cast<half_t*>(tok);
-        const GemmPlan pl = uv_gemm_plan(lin_params(any, M, nk[1], any, any, nk[0], any, any, nullptr, 0), 0, uv_num_cus());
-        if (pl.rc != UV_OK) {
-            uv_set_error("%s", pl.err);
-            return pl.rc;
-        }
-        if (pl.ws_bytes > splitk_bytes) splitk_bytes = pl.ws_bytes;
-    }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t mc = al((size_t)M * C * 2);
-    const size_t need = 7 * mc + al((size_t)M * 3 * C * 2) + al((size_t)M * I * 2) + al((size_t)B * C * 2) + al(splitk_bytes) + 4096;
-    UV_RUN(arena.ensure(need));
-    auto take = [&](size_t bytes) { return bytes ? arena.alloc(bytes) : nullptr; };
-    x[0] = (half_t*)take(mc);
-    x[1] = (half_t*)take(mc);
-    h = (half_t*)take(mc);
-    att = (half_t*)take(mc);
-    mid = (half_t*)take(mc);
-    last = (half_t*)take(mc);
-    qkv = (half_t*)take((size_t)M * 3 * C * 2);
-    ff = (half_t*)take((size_t)M * I * 2);
-    prow = (half_t*)take((size_t)B * C * 2);
-    splitk = (float*)take(splitk_bytes);
-    if (!x[0] || !x[1] || !h || !att || !mid || !last || !qkv || !ff || !prow || (splitk_bytes && !splitk)) {
-        uv_set_error("clip: activation arena exhausted (%zu bytes)", arena.size);
-        return UV_ERR_STATE;
-    }
+    // split-K partials of the four linears (q|k|v, out + residual, fc1, fc2 + residual), as the GEMM launcher will plan them; the 256-aligned embedding table
+    // stands in for the operands
+    UV_RUN(uv_plan_splitk_bytes(M, tok, {{3 * C, C, 0, 1, 0}, {C, C, 0, 1, 1}, {I, C, 0, 1, 0}, {C, I, 0, 1, 1}}, &splitk_bytes));
+    const size_t mc = (size_t)M * C * 2;
+    UV_RUN(carve({{&x[0], mc}, {&x[1], mc}, {&h, mc}, {&att, mc}, {&mid, mc}, {&last, mc}, {&qkv, (size_t)M * 3 * C * 2}, {&ff, (size_t)M * I * 2},
+                  {&prow, (size_t)B * C * 2}, {&splitk, splitk_bytes}}));
     rB = B;
     rS = S;
     return UV_OK;
@@ -393,7 +326,7 @@ int Clip::encode(const int64_t* ids, int B, int S, half_t* last_hidden, half_t* 
     const long M = (long)B * S;
     const int C = cfg.hidden_size, I = cfg.intermediate_size, L = cfg.num_layers;
     auto linear = [&](const half_t* X, int K, const half_t* Wt, const half_t* bias, int N, half_t* Y, const half_t* R) {
-        return uv_launch_gemm(lin_params(X, M, K, Wt, bias, N, Y, R, splitk, splitk_bytes), 0, s);
+        return uv_launch_gemm(lin_params(X, M, K, Wt, N, Y, bias, R, 0, splitk, splitk_bytes), 0, s);
     };
     // residual stream l: the caller's hidden_states[l] when it wants them, else two arena buffers in turn
     auto xl = [&](int l) { return hidden_states ? hidden_states + (long)l * M * C : x[l & 1]; };

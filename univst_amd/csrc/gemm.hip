@@ -1773,6 +1773,20 @@ GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu) {
 }
 #undef PLAN_REQUIRE
 
+int uv_plan_splitk_bytes(long M, const half_t* any, std::initializer_list<LinearShape> linears, size_t* ws_bytes) {
+    *ws_bytes = 0;
+    half_t* a = const_cast<half_t*>(any);
+    for (const LinearShape& l : linears) {
+        const GemmPlan pl = uv_gemm_plan(lin_params(a, M, l.K, a, l.N, a, l.bias ? a : nullptr, l.residual ? a : nullptr, l.geglu), 0, uv_num_cus());
+        if (pl.rc != UV_OK) {
+            uv_set_error("%s", pl.err);
+            return pl.rc;
+        }
+        if (pl.ws_bytes > *ws_bytes) *ws_bytes = pl.ws_bytes;
+    }
+    return UV_OK;
+}
+
 int uv_launch_gemm(const GemmParams& p0, int mode, hipStream_t stream) {
     GemmParams q = with_conv_defaults(p0, mode);
     const GemmPlan pl = uv_gemm_plan(q, mode, uv_num_cus());

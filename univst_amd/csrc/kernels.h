@@ -1,6 +1,7 @@
 // Internal launcher interface shared by the kernel translation units, the UNet graph and the C ABI.
 #pragma once
 #include "common.h"
+#include <initializer_list>
 #include <string>
 
 struct GemmParams {
@@ -74,6 +75,28 @@ struct GemmParams {
     // when the plan says so (GemmPlan::phase; uv_conv_patch_phase_eligible), else the launcher clears the pointer and the 9-tap form runs.
     const half_t* W4 = nullptr;
 };
+
+// A row-major linear Y[M, N] = X[M, K] W[N, K]^T (+ bias) (+ R): contiguous rows everywhere; the GEGLU epilogue writes (and adds a residual of) N / 2
+// columns.  ws: the caller's split-K workspace, or none.  The one description of such a linear: reserve (uv_plan_splitk_bytes) and launch both build it here.
+inline GemmParams lin_params(const half_t* X, long M, int K, const half_t* W, int N, half_t* Y, const half_t* bias = nullptr, const half_t* R = nullptr,
+                             int geglu = 0, float* ws = nullptr, size_t ws_bytes = 0) {
+    GemmParams g;
+    g.X = X;
+    g.ldx = K;
+    g.M = (int)M;
+    g.K = K;
+    g.N = N;
+    g.W = W;
+    g.bias = bias;
+    g.Y = Y;
+    g.ldy = geglu ? N / 2 : N;
+    g.R = R;
+    g.ldr = g.ldy;
+    g.geglu = geglu;
+    g.partial = ws;
+    g.partial_bytes = ws_bytes;
+    return g;
+}
 
 struct AttnParams {
     const half_t* q = nullptr;   // row (bf*Nq + i), head h at column h*d
@@ -166,6 +189,13 @@ struct GemmPlan : UvLaunchPlan {
 };
 struct AttnPlan : UvLaunchPlan {};
 GemmPlan uv_gemm_plan(const GemmParams& p, int mode, int ncu);       // p: conv geometry defaults filled in; ncu: compute units of the device
+// The split-K workspace a handle reserves for its linears over M rows: the largest ws_bytes uv_gemm_plan gives any of them on this device, or the
+// plan's error.  `any`: a 16-byte aligned device pointer that stands in for every operand a row says is there (the plan looks at pointers for null
+// and alignment only).
+struct LinearShape {
+    int N, K, geglu, bias, residual;
+};
+int uv_plan_splitk_bytes(long M, const half_t* any, std::initializer_list<LinearShape> linears, size_t* ws_bytes);
 AttnPlan uv_attention_plan(const AttnParams& p);
 // one line of text, `<symbol> grid=<blocks> block=<threads> splits=<s>[ +splitk_reduce]` (+ the predicates below for the GEMM), or the plan's error
 int uv_gemm_plan_text(const GemmParams& p, int mode, int ncu, char* buf, int n);

@@ -1,6 +1,9 @@
-// Plumbing shared by the model handles (unet.hip, vae.hip; raft.hip takes nb() and the slab helper only): the fp16 weight store with its
-// derived layouts, the activation arena and the weight-preparation kernels (model.hip).
+// Plumbing shared by the model handles (model.hip): the fp16 weight store with its derived layouts, the activation arena, the weight-preparation
+// kernels, and Model — the base of every fp16 handle (Clip, T5, Motion, Vae / KlVae, UNet): store + owned arena slab + finalized flag, load_tensor,
+// weight_bytes, the shape-checked weight lookup of finalize (shaped / UV_SHAPED) and the fixed-buffer arena carve of reserve (carve).  raft.hip keeps
+// its fp32 store and takes nb() and the slab helper only.  Nothing here needs the GEMM: model.hip links with tools/arena_check.cpp alone.
 #pragma once
+#include <initializer_list>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -52,6 +55,36 @@ struct WeightStore {
     int derive(const std::string& k, std::vector<long> shape, half_t** out);      // replaces a derived tensor of that key
     void clear_derived();
 };
+
+// What the fp16 handles share on top of the store.  `who` names the handle in messages ("clip": "clip_finalize: ...", "clip: weight ... was never
+// loaded", and the carve's message when the arena cannot hold the list).
+struct Model : WeightStore {
+    const char* const who;
+    Arena arena;                   // the slab is the handle's: freed by ~Model (Arena itself owns nothing: tools/arena_check.cpp points it at host memory)
+    bool finalized = false;
+
+    explicit Model(const char* who_) : who(who_) {}
+    ~Model();
+    int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);      // load() + finalized = false
+    double weight_bytes() const;                                                                                         // loaded + derived tensors
+    // finalize's lookup: the tensor of that key when its shape is `want`; else null with the missing key recorded or the shape error set (shaped_error)
+    const half_t* shaped(const std::string& key, std::initializer_list<long> want);
+    int shaped_error() const;
+    // reserve's carve for a fixed list of buffers: the slab holds the aligned sizes of that list + 4096, *dst are allocated in list order (0 bytes: null)
+    struct Buf {
+        void** dst;
+        size_t bytes;
+        template <class T>
+        Buf(T** d, size_t b) : dst(reinterpret_cast<void**>(d)), bytes(b) {}
+    };
+    int carve(std::initializer_list<Buf> bufs);
+};
+// dst = shaped(key, {dims...}), or return the error from the handle's finalize
+#define UV_SHAPED(dst, key, ...)                 \
+    do {                                         \
+        (dst) = shaped((key), {__VA_ARGS__});    \
+        if (!(dst)) return shaped_error();       \
+    } while (0)
 
 // conv weight [Co][Ci][taps...] -> "key#nhwc" [Co][taps][CiP] (input channels zero padded to 8) and, where taps == 9 && Ci % 64 == 0,
 // the tap-inner "key#ti" [Co][Ci/64][9][64] (GemmParams::korder = 1)

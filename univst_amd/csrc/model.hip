@@ -1,4 +1,4 @@
-// The handle plumbing the model graphs share (model.h): weight store, activation arena, weight-preparation kernels.  All of it runs at load,
+// The handle plumbing the model graphs share (model.h): weight store, activation arena, the Model base, weight-preparation kernels.  All of it runs at load,
 // finalize and reserve time, or as a hash lookup in front of a launch; nothing here is on the per-step path.
 #include "model.h"
 
@@ -177,6 +177,57 @@ int WeightStore::derive(const std::string& k, std::vector<long> shape, half_t** 
 void WeightStore::clear_derived() {
     for (auto& kv : derived) (void)hipFree(kv.second.ptr);
     derived.clear();
+}
+
+// ------------------------------------------------------------------------------------------ what the fp16 handles share
+Model::~Model() {
+    if (arena.base) (void)hipFree(arena.base);
+}
+
+int Model::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
+    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
+    finalized = false;
+    return UV_OK;
+}
+
+double Model::weight_bytes() const {
+    double n = 0;
+    for (const auto* m : {&weights, &derived})
+        for (const auto& kv : *m) {
+            double e = 1;
+            for (long v : kv.second.shape) e *= (double)v;
+            n += e * sizeof(half_t);
+        }
+    return n;
+}
+
+const half_t* Model::shaped(const std::string& key, std::initializer_list<long> want) {
+    const WTensor* t = find(key);
+    if (!t) {
+        (void)W(key);      // records the missing key
+        return nullptr;
+    }
+    if (t->shape != std::vector<long>(want)) {
+        uv_set_error("%s_finalize: %s has %zu dims / first dim %ld, which the config does not give", who, key.c_str(), t->shape.size(), t->shape[0]);
+        return nullptr;
+    }
+    return t->ptr;
+}
+
+int Model::shaped_error() const { return missing.empty() ? UV_ERR_ARG : missing_error(who); }
+
+int Model::carve(std::initializer_list<Buf> bufs) {
+    size_t need = 4096;
+    for (const Buf& b : bufs) need += (b.bytes + 255) & ~size_t(255);
+    UV_RUN(arena.ensure(need));
+    for (const Buf& b : bufs) {
+        *b.dst = b.bytes ? arena.alloc(b.bytes) : nullptr;
+        if (b.bytes && !*b.dst) {
+            uv_set_error("%s: activation arena exhausted (%zu bytes)", who, arena.size);
+            return UV_ERR_STATE;
+        }
+    }
+    return UV_OK;
 }
 
 // ------------------------------------------------------------------------------------------ weight preparation

@@ -27,10 +27,8 @@ struct MotionBufs {       // the activations of one chain run, supplied by whoev
     size_t splitk_bytes = 0;
 };
 
-struct Motion : WeightStore {
+struct Motion : Model {
     univst_motion_cfg cfg;
-    Arena arena;
-    bool finalized = false;
     std::vector<MotionBlock> blocks;
     const half_t *gn_g = nullptr, *gn_b = nullptr, *in_w = nullptr, *in_b = nullptr, *outp_w = nullptr, *outp_b = nullptr;
     // activations of one (B, F, N), carved from the arena by the first forward at that size
@@ -39,15 +37,13 @@ struct Motion : WeightStore {
     float *gn_ws = nullptr, *splitk = nullptr;
     size_t splitk_bytes = 0;
 
-    ~Motion();
-    int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
+    Motion() : Model("motion") {}
     int finalize(hipStream_t s);
     int reserve(int B, int F, int N);
     int forward(const half_t* X, half_t* Y, int B, int F, int N, hipStream_t s);
     // the chain of forward() over caller-supplied buffers (who: the entry point named in messages); no allocation, no synchronisation
     int check_shape(const char* who, int B, int F, int N) const;
     int run(const half_t* X, half_t* Y, int B, int F, int N, const MotionBufs& b, hipStream_t s);
-    double weight_bytes() const;
 };
 
 int uv_motion_check_cfg(const univst_motion_cfg& c);

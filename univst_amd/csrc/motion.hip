@@ -159,26 +159,6 @@ __global__ __launch_bounds__(256) void motion_geglu_rows_kernel(const half_t* __
     out[i] = in[(long)src * cols + c];
 }
 
-GemmParams lin_params(const half_t* X, long M, int K, const half_t* Wt, const half_t* bias, int N, half_t* Y, const half_t* R, int geglu, float* ws,
-                      size_t ws_bytes) {
-    GemmParams g;
-    g.X = X;
-    g.ldx = K;
-    g.M = (int)M;
-    g.K = K;
-    g.N = N;
-    g.W = Wt;
-    g.bias = bias;
-    g.Y = Y;
-    g.ldy = geglu ? N / 2 : N;
-    g.R = R;
-    g.ldr = g.ldy;
-    g.geglu = geglu;
-    g.partial = ws;
-    g.partial_bytes = ws_bytes;
-    return g;
-}
-
 template <int D, int KT>
 void ta_launch(const half_t* qkv, long ldx, const half_t* pe, int B, int F, int N, int heads, half_t* out, long ldo, hipStream_t s) {
     constexpr int WAVES = ta_waves(D, KT);
@@ -233,58 +213,19 @@ int uv_motion_check_cfg(const univst_motion_cfg& c) {
     return UV_OK;
 }
 
-Motion::~Motion() {
-    if (arena.base) (void)hipFree(arena.base);
-}
-
-double Motion::weight_bytes() const {
-    double n = 0;
-    for (const auto* m : {&weights, &derived})
-        for (const auto& kv : *m) {
-            double e = 1;
-            for (long v : kv.second.shape) e *= (double)v;
-            n += e * sizeof(half_t);
-        }
-    return n;
-}
-
-int Motion::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
-    UV_REQUIRE(key, "motion_load_tensor: null key");
-    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
-    finalized = false;
-    return UV_OK;
-}
-
 int Motion::finalize(hipStream_t s) {
     clear_derived();
     clear_missing();
     blocks.clear();
     const long C = cfg.channels, L = cfg.max_len;
     const int d = cfg.channels / cfg.num_heads;
-    auto shaped = [&](const std::string& k, std::vector<long> want) -> const half_t* {
-        const WTensor* t = find(k);
-        if (!t) {
-            (void)W(k);      // records the missing key
-            return nullptr;
-        }
-        if (t->shape != want) {
-            uv_set_error("motion_finalize: %s has %zu dims / first dim %ld, which the config does not give", k.c_str(), t->shape.size(), t->shape[0]);
-            return nullptr;
-        }
-        return t->ptr;
-    };
-#define MOTION_W(dst, key, ...)                                                      \
-    do {                                                                             \
-        (dst) = shaped((key), {__VA_ARGS__});                                        \
-        if (!(dst)) return missing.empty() ? UV_ERR_ARG : missing_error("motion");   \
-    } while (0)
     const std::string tt = "temporal_transformer.";
-    MOTION_W(gn_g, tt + "norm.weight", C);
-    MOTION_W(gn_b, tt + "norm.bias", C);
-    MOTION_W(in_w, tt + "proj_in.weight", C, C);
-    MOTION_W(in_b, tt + "proj_in.bias", C);
-    MOTION_W(outp_w, tt + "proj_out.weight", C, C);
-    MOTION_W(outp_b, tt + "proj_out.bias", C);
+    UV_SHAPED(gn_g, tt + "norm.weight", C);
+    UV_SHAPED(gn_b, tt + "norm.bias", C);
+    UV_SHAPED(in_w, tt + "proj_in.weight", C, C);
+    UV_SHAPED(in_b, tt + "proj_in.bias", C);
+    UV_SHAPED(outp_w, tt + "proj_out.weight", C, C);
+    UV_SHAPED(outp_b, tt + "proj_out.bias", C);
     // the sinusoid of PositionalEncoding (d_model = C): pe[f][2i] = sin(f w_i), pe[f][2i + 1] = cos(f w_i), w_i = 10000^(-2i / C)
     std::vector<half_t> pe_host;
     if (cfg.position_encoding) {
@@ -301,14 +242,14 @@ int Motion::finalize(hipStream_t s) {
         for (int i = 0; i < cfg.attn_per_block; ++i) {
             const std::string a = p + "attention_blocks." + std::to_string(i) + ".";
             MotionAttn A;
-            MOTION_W(A.ln_g, p + "norms." + std::to_string(i) + ".weight", C);
-            MOTION_W(A.ln_b, p + "norms." + std::to_string(i) + ".bias", C);
-            MOTION_W(A.out_w, a + "to_out.0.weight", C, C);
-            MOTION_W(A.out_b, a + "to_out.0.bias", C);
+            UV_SHAPED(A.ln_g, p + "norms." + std::to_string(i) + ".weight", C);
+            UV_SHAPED(A.ln_b, p + "norms." + std::to_string(i) + ".bias", C);
+            UV_SHAPED(A.out_w, a + "to_out.0.weight", C, C);
+            UV_SHAPED(A.out_b, a + "to_out.0.bias", C);
             const half_t *qw, *kw, *vw;
-            MOTION_W(qw, a + "to_q.weight", C, C);
-            MOTION_W(kw, a + "to_k.weight", C, C);
-            MOTION_W(vw, a + "to_v.weight", C, C);
+            UV_SHAPED(qw, a + "to_q.weight", C, C);
+            UV_SHAPED(kw, a + "to_k.weight", C, C);
+            UV_SHAPED(vw, a + "to_v.weight", C, C);
             // fused q|k|v projection [3C, C]; the score scale d^-0.5 rides on the q rows, which leaves the kernel the factor log2(e) only
             half_t* fw;
             UV_RUN(derive(a + "#qkv_w", {3 * C, C}, &fw));
@@ -320,7 +261,7 @@ int Motion::finalize(hipStream_t s) {
             if (cfg.position_encoding) {
                 // the table: a checkpoint's pos_encoder.pe [1, max_len, C] when it was loaded, else the formula; then pe_qkv[f] = Wqkv pe[f]
                 const half_t* pe = nullptr;
-                if (find(a + "pos_encoder.pe")) MOTION_W(pe, a + "pos_encoder.pe", 1, L, C);
+                if (find(a + "pos_encoder.pe")) UV_SHAPED(pe, a + "pos_encoder.pe", 1, L, C);
                 else {
                     half_t* dpe;
                     UV_RUN(derive(a + "#pe", {L, C}, &dpe));
@@ -329,18 +270,18 @@ int Motion::finalize(hipStream_t s) {
                 }
                 half_t* pq;
                 UV_RUN(derive(a + "#pe_qkv", {L, 3 * C}, &pq));
-                UV_RUN(uv_launch_gemm(lin_params(pe, L, (int)C, fw, nullptr, (int)(3 * C), pq, nullptr, 0, nullptr, 0), 0, s));
+                UV_RUN(uv_launch_gemm(lin_params(pe, L, (int)C, fw, (int)(3 * C), pq), 0, s));
                 A.pe_qkv = pq;
             }
             Bk.attn.push_back(A);
         }
-        MOTION_W(Bk.ffn_g, p + "ff_norm.weight", C);
-        MOTION_W(Bk.ffn_b, p + "ff_norm.bias", C);
-        MOTION_W(Bk.ff2_w, p + "ff.net.2.weight", C, 4 * C);
-        MOTION_W(Bk.ff2_b, p + "ff.net.2.bias", C);
+        UV_SHAPED(Bk.ffn_g, p + "ff_norm.weight", C);
+        UV_SHAPED(Bk.ffn_b, p + "ff_norm.bias", C);
+        UV_SHAPED(Bk.ff2_w, p + "ff.net.2.weight", C, 4 * C);
+        UV_SHAPED(Bk.ff2_b, p + "ff.net.2.bias", C);
         const half_t *w1, *b1;
-        MOTION_W(w1, p + "ff.net.0.proj.weight", 8 * C, C);
-        MOTION_W(b1, p + "ff.net.0.proj.bias", 8 * C);
+        UV_SHAPED(w1, p + "ff.net.0.proj.weight", 8 * C, C);
+        UV_SHAPED(b1, p + "ff.net.0.proj.bias", 8 * C);
         // GEGLU projection in the row order of the `geglu = 1` epilogue: 16 value rows, then their 16 gate rows
         half_t *gw, *gb;
         UV_RUN(derive(p + "ff.net.0.proj.weight#geglu", {8 * C, C}, &gw));
@@ -352,7 +293,6 @@ int Motion::finalize(hipStream_t s) {
         Bk.ff1_b = gb;
         blocks.push_back(Bk);
     }
-#undef MOTION_W
     UV_HIP(hipStreamSynchronize(s));      // (pe_host is read by the copies above until here)
     finalized = true;
     return UV_OK;
@@ -364,37 +304,12 @@ int Motion::reserve(int B, int F, int N) {
     rB = rF = rN = 0;
     const long M = (long)B * F * N;
     const int C = cfg.channels;
-    // split-K partials of the linears, as the GEMM launcher will plan them
-    splitk_bytes = 0;
-    // {N, K, geglu, bias, residual} of proj_in, q|k|v, to_out / proj_out, ff1, ff2, with the null pattern forward() passes
-    const int shapes[5][5] = {{C, C, 0, 1, 0}, {3 * C, C, 0, 0, 0}, {C, C, 0, 1, 1}, {8 * C, C, 1, 1, 0}, {C, 4 * C, 0, 1, 1}};
-    for (auto& nk : shapes) {      // (the plan looks at pointers for null and 16-byte alignment only: the 256-aligned norm weight stands in for the non-null ones;
-                                   //  forward() holds every launch to what is reserved here)
-        half_t* any = const_cast<half_t*>(gn_g);
-        const GemmPlan pl = uv_gemm_plan(lin_params(any, M, nk[1], any, nk[3] ? any : nullptr, nk[0], any, nk[4] ? any : nullptr, nk[2], nullptr, 0), 0, uv_num_cus());
-        if (pl.rc != UV_OK) {
-            uv_set_error("%s", pl.err);
-            return pl.rc;
-        }
-        if (pl.ws_bytes > splitk_bytes) splitk_bytes = pl.ws_bytes;
-    }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t mc = al((size_t)M * C * 2), gnb = (size_t)uv_groupnorm_workspace_floats(B * F, cfg.norm_groups) * sizeof(float);
-    const size_t need = 4 * mc + al((size_t)M * 3 * C * 2) + al((size_t)M * 4 * C * 2) + al(gnb) + al(splitk_bytes) + 4096;
-    UV_RUN(arena.ensure(need));
-    auto take = [&](size_t bytes) { return bytes ? arena.alloc(bytes) : nullptr; };
-    x[0] = (half_t*)take(mc);
-    x[1] = (half_t*)take(mc);
-    h = (half_t*)take(mc);
-    att = (half_t*)take(mc);
-    qkv = (half_t*)take((size_t)M * 3 * C * 2);
-    ff = (half_t*)take((size_t)M * 4 * C * 2);
-    gn_ws = (float*)take(gnb);
-    splitk = (float*)take(splitk_bytes);
-    if (!x[0] || !x[1] || !h || !att || !qkv || !ff || (gnb && !gn_ws) || (splitk_bytes && !splitk)) {
-        uv_set_error("motion: activation arena exhausted (%zu bytes)", arena.size);
-        return UV_ERR_STATE;
-    }
+    // split-K partials of the linears, as the GEMM launcher will plan them: {N, K, geglu, bias, residual} of proj_in, q|k|v, to_out / proj_out, ff1, ff2, with
+    // the null pattern run() passes; the 256-aligned norm weight stands in for the operands (run() holds every launch to what is reserved here)
+    UV_RUN(uv_plan_splitk_bytes(M, gn_g, {{C, C, 0, 1, 0}, {3 * C, C, 0, 0, 0}, {C, C, 0, 1, 1}, {8 * C, C, 1, 1, 0}, {C, 4 * C, 0, 1, 1}}, &splitk_bytes));
+    const size_t mc = (size_t)M * C * 2;
+    UV_RUN(carve({{&x[0], mc}, {&x[1], mc}, {&h, mc}, {&att, mc}, {&qkv, (size_t)M * 3 * C * 2}, {&ff, (size_t)M * 4 * C * 2},
+                  {&gn_ws, (size_t)uv_groupnorm_workspace_floats(B * F, cfg.norm_groups) * sizeof(float)}, {&splitk, splitk_bytes}}));
     rB = B;
     rF = F;
     rN = N;
@@ -426,7 +341,7 @@ int Motion::run(const half_t* X, half_t* Y, int B, int F, int N, const MotionBuf
     const int C = cfg.channels;
     const int ncu = uv_num_cus();
     auto linear = [&](const half_t* Xi, int K, const half_t* Wt, const half_t* bias, int Nn, half_t* Yo, const half_t* R, int geglu) {
-        const GemmParams g = lin_params(Xi, M, K, Wt, bias, Nn, Yo, R, geglu, b.splitk, b.splitk_bytes);
+        const GemmParams g = lin_params(Xi, M, K, Wt, Nn, Yo, bias, R, geglu, b.splitk, b.splitk_bytes);
         // the workspace holds what its owner planned: a launch that wanted more (an operand of another alignment) would allocate behind the caller's back
         const GemmPlan pl = uv_gemm_plan(g, 0, ncu);
         if (pl.rc == UV_OK && pl.ws_bytes > b.splitk_bytes) {

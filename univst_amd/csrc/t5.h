@@ -13,10 +13,8 @@ struct T5Layer {      // the weights of one encoder block, looked up once by fin
     const half_t *ln1_g, *qkv_w, *o_w, *ln2_g, *wi_w, *wo_w;
 };
 
-struct T5 : WeightStore {
+struct T5 : Model {
     univst_t5_cfg cfg;
-    Arena arena;
-    bool finalized = false;
     std::vector<T5Layer> layers;
     const half_t *embed = nullptr, *fln_g = nullptr;
     const float* bias_table = nullptr;      // [heads][UV_T5_BIAS_W] fp32, derived from block 0's relative_attention_bias
@@ -27,12 +25,11 @@ struct T5 : WeightStore {
     float* splitk = nullptr;
     size_t splitk_bytes = 0;
 
-    ~T5();
+    T5() : Model("t5") {}
     int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
     int finalize(hipStream_t s);
     int reserve(int B, int S);
     int encode(const int64_t* ids, int B, int S, half_t* last_hidden, hipStream_t s);
-    double weight_bytes() const;
 };
 
 int uv_t5_check_cfg(const univst_t5_cfg& c);

@@ -204,21 +204,6 @@ __global__ __launch_bounds__(256) void t5_add_kernel(float* __restrict__ x, cons
     *reinterpret_cast<f4*>(x + i * 8 + 4) = c;
 }
 
-GemmParams lin_params(const half_t* X, long M, int K, const half_t* Wt, int N, half_t* Y, float* ws, size_t ws_bytes) {
-    GemmParams g;      // no linear of T5 has a bias
-    g.X = X;
-    g.ldx = K;
-    g.M = (int)M;
-    g.K = K;
-    g.N = N;
-    g.W = Wt;
-    g.Y = Y;
-    g.ldy = N;
-    g.partial = ws;
-    g.partial_bytes = ws_bytes;
-    return g;
-}
-
 }  // namespace
 
 int uv_t5_bucket_table(int num_buckets, int max_distance, int n, int* out) {
@@ -263,28 +248,11 @@ int uv_t5_check_cfg(const univst_t5_cfg& c) {
     return UV_OK;
 }
 
-T5::~T5() {
-    if (arena.base) (void)hipFree(arena.base);
-}
-
-double T5::weight_bytes() const {
-    double n = 0;
-    for (const auto* m : {&weights, &derived})
-        for (const auto& kv : *m) {
-            double e = 1;
-            for (long v : kv.second.shape) e *= (double)v;
-            n += e * sizeof(half_t);
-        }
-    return n;
-}
-
 int T5::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
     UV_REQUIRE(key, "t5_load_tensor: null key");
     // the embedding is tied: a checkpoint carries it as shared.weight, encoder.embed_tokens.weight or both — one copy under the first name
     if (!strcmp(key, "encoder.embed_tokens.weight")) key = "shared.weight";
-    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
-    finalized = false;
-    return UV_OK;
+    return Model::load_tensor(key, dev_ptr, dtype, shape, ndim, s);
 }
 
 int T5::finalize(hipStream_t s) {
@@ -293,40 +261,23 @@ int T5::finalize(hipStream_t s) {
     layers.clear();
     bias_table = nullptr;
     const int C = cfg.d_model, F = cfg.d_ff, Hn = cfg.num_heads, I = Hn * TA_D;
-    auto shaped = [&](const std::string& k, std::vector<long> want) -> const half_t* {
-        const WTensor* t = find(k);
-        if (!t) {
-            (void)W(k);      // records the missing key
-            return nullptr;
-        }
-        if (t->shape != want) {
-            uv_set_error("t5_finalize: %s has %zu dims / first dim %ld, which the config does not give", k.c_str(), t->shape.size(), t->shape[0]);
-            return nullptr;
-        }
-        return t->ptr;
-    };
-#define T5_W(dst, key, ...)                                                    \
-    do {                                                                       \
-        (dst) = shaped((key), {__VA_ARGS__});                                  \
-        if (!(dst)) return missing.empty() ? UV_ERR_ARG : missing_error("t5"); \
-    } while (0)
     const half_t* rel;
-    T5_W(embed, "shared.weight", cfg.vocab_size, C);
-    T5_W(fln_g, "encoder.final_layer_norm.weight", C);
-    T5_W(rel, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", cfg.num_buckets, Hn);
+    UV_SHAPED(embed, "shared.weight", cfg.vocab_size, C);
+    UV_SHAPED(fln_g, "encoder.final_layer_norm.weight", C);
+    UV_SHAPED(rel, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", cfg.num_buckets, Hn);
     for (int l = 0; l < cfg.num_layers; ++l) {
         const std::string p = "encoder.block." + std::to_string(l) + ".layer.";
         T5Layer L;
         const half_t *qw, *kw, *vw, *w0, *w1;
-        T5_W(L.ln1_g, p + "0.layer_norm.weight", C);
-        T5_W(qw, p + "0.SelfAttention.q.weight", I, C);
-        T5_W(kw, p + "0.SelfAttention.k.weight", I, C);
-        T5_W(vw, p + "0.SelfAttention.v.weight", I, C);
-        T5_W(L.o_w, p + "0.SelfAttention.o.weight", C, I);
-        T5_W(L.ln2_g, p + "1.layer_norm.weight", C);
-        T5_W(w0, p + "1.DenseReluDense.wi_0.weight", F, C);
-        T5_W(w1, p + "1.DenseReluDense.wi_1.weight", F, C);
-        T5_W(L.wo_w, p + "1.DenseReluDense.wo.weight", C, F);
+        UV_SHAPED(L.ln1_g, p + "0.layer_norm.weight", C);
+        UV_SHAPED(qw, p + "0.SelfAttention.q.weight", I, C);
+        UV_SHAPED(kw, p + "0.SelfAttention.k.weight", I, C);
+        UV_SHAPED(vw, p + "0.SelfAttention.v.weight", I, C);
+        UV_SHAPED(L.o_w, p + "0.SelfAttention.o.weight", C, I);
+        UV_SHAPED(L.ln2_g, p + "1.layer_norm.weight", C);
+        UV_SHAPED(w0, p + "1.DenseReluDense.wi_0.weight", F, C);
+        UV_SHAPED(w1, p + "1.DenseReluDense.wi_1.weight", F, C);
+        UV_SHAPED(L.wo_w, p + "1.DenseReluDense.wo.weight", C, F);
         // fused q|k|v [3 I, C] and wi_0|wi_1 [2 F, C]: one projection each (T5 has no attention scale to fold)
         half_t *fq, *fi;
         UV_RUN(derive(p + "0.SelfAttention#qkv_w", {3L * I, C}, &fq));
@@ -341,7 +292,6 @@ int T5::finalize(hipStream_t s) {
         L.wi_w = fi;
         layers.push_back(L);
     }
-#undef T5_W
     UV_HIP(hipStreamSynchronize(s));      // the uploads queued on s are in place
     // the per-head bias table [heads][delta + 511] (fp32, kept in a derived slot of twice as many halfs): block 0's relative_attention_bias
     // [num_buckets, heads] read through the bucket of every delta; built on the host, once
@@ -366,34 +316,12 @@ int T5::reserve(int B, int S) {
     rB = rS = 0;
     const long M = (long)B * S;
     const int C = cfg.d_model, F = cfg.d_ff, I = cfg.num_heads * TA_D;
-    // split-K partials of the four linears, as the GEMM launcher will plan them
-    splitk_bytes = 0;
-    const int shapes[4][2] = {{3 * I, C}, {C, I}, {2 * F, C}, {C, F}};
-    for (auto& nk : shapes) {      // (the plan looks at pointers for null and alignment only: the 256-aligned embedding table stands in for all of them)
-        half_t* any = const_cast<half_t*>(embed);
-        const GemmPlan pl = uv_gemm_plan(lin_params(any, M, nk[1], any, nk[0], any, nullptr, 0), 0, uv_num_cus());
-        if (pl.rc != UV_OK) {
-            uv_set_error("%s", pl.err);
-            return pl.rc;
-        }
-        if (pl.ws_bytes > splitk_bytes) splitk_bytes = pl.ws_bytes;
-    }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t bx = (size_t)M * C * 4, bh = (size_t)M * C * 2, bq = (size_t)M * 3 * I * 2, ba = (size_t)M * I * 2, b2 = (size_t)M * 2 * F * 2, bf = (size_t)M * F * 2;
-    UV_RUN(arena.ensure(al(bx) + 2 * al(bh) + al(bq) + al(ba) + al(b2) + al(bf) + al(splitk_bytes) + 4096));
-    auto take = [&](size_t bytes) { return bytes ? arena.alloc(bytes) : nullptr; };
-    x = (float*)take(bx);
-    h = (half_t*)take(bh);
-    y = (half_t*)take(bh);
-    qkv = (half_t*)take(bq);
-    att = (half_t*)take(ba);
-    ff2 = (half_t*)take(b2);
-    ff = (half_t*)take(bf);
-    splitk = (float*)take(splitk_bytes);
-    if (!x || !h || !y || !qkv || !att || !ff2 || !ff || (splitk_bytes && !splitk)) {
-        uv_set_error("t5: activation arena exhausted (%zu bytes)", arena.size);
-        return UV_ERR_STATE;
-    }
+    // split-K partials of the four linears (q|k|v, o, wi_0|wi_1, wo: none has a bias or a residual), as the GEMM launcher will plan them; the 256-aligned
+    // embedding table stands in for the operands
+    UV_RUN(uv_plan_splitk_bytes(M, embed, {{3 * I, C, 0, 0, 0}, {C, I, 0, 0, 0}, {2 * F, C, 0, 0, 0}, {C, F, 0, 0, 0}}, &splitk_bytes));
+    const size_t bh = (size_t)M * C * 2;
+    UV_RUN(carve({{&x, (size_t)M * C * 4}, {&h, bh}, {&y, bh}, {&qkv, (size_t)M * 3 * I * 2}, {&att, (size_t)M * I * 2}, {&ff2, (size_t)M * 2 * F * 2},
+                  {&ff, (size_t)M * F * 2}, {&splitk, splitk_bytes}}));
     rB = B;
     rS = S;
     return UV_OK;
@@ -406,7 +334,7 @@ int T5::encode(const int64_t* ids, int B, int S, half_t* last_hidden, hipStream_
     UV_RUN(reserve(B, S));
     const long M = (long)B * S;
     const int C = cfg.d_model, F = cfg.d_ff, I = cfg.num_heads * TA_D;
-    auto linear = [&](const half_t* X, int K, const half_t* Wt, int N, half_t* Y) { return uv_launch_gemm(lin_params(X, M, K, Wt, N, Y, splitk, splitk_bytes), 0, s); };
+    auto linear = [&](const half_t* X, int K, const half_t* Wt, int N, half_t* Y) { return uv_launch_gemm(lin_params(X, M, K, Wt, N, Y, nullptr, nullptr, 0, splitk, splitk_bytes), 0, s); };
     auto rms = [&](const half_t* g, half_t* dst) { hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3((unsigned)M), dim3(256), 0, s, x, g, dst, C, cfg.layer_norm_eps); };
     auto add = [&]() { hipLaunchKernelGGL(t5_add_kernel, dim3(nb(M * C / 8)), dim3(256), 0, s, x, y, M * C / 8); };
     hipLaunchKernelGGL(t5_embed_kernel, dim3(nb(M * (C / 8))), dim3(256), 0, s, ids, embed, x, M, C, cfg.vocab_size);

@@ -8,13 +8,11 @@
 #include "model.h"
 #include "motion.h"
 
-struct UNet : WeightStore {
+struct UNet : Model {
     univst_unet_cfg cfg;
     std::unordered_map<long, int*> idx_tables;
     std::unordered_map<std::string, long> temb_off;    // resnet prefix -> column offset in the fused time_emb_proj (finalize)
     long temb_total = 0;
-    Arena arena;
-    bool finalized = false;
     int gn_producer = 1;      // GroupNorm statistics from the producing conv / linear's epilogue where the tile geometry allows (UNIVST_GN_PRODUCER=0: always the stand-alone pass)
     int chain_bands = 1;      // post-attention chain of a transformer block in row bands: 1 off (default: measured +0.4 ms per step in the graph), 0 auto (bands of >= 65536 rows), n > 1 forced (UNIVST_CHAIN_BANDS)
     int gn_fold = 1;          // the transformer blocks' per-frame GroupNorm folded into proj_in where the weight copies are cheap (round 5; 0: the apply pass)
@@ -54,6 +52,7 @@ struct UNet : WeightStore {
     unsigned emu_epoch = 0;
     int comm_streams();                          // creates the forked stream + events on first use
 
+    UNet() : Model("unet") {}
     ~UNet();
     int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
     int finalize(hipStream_t s);

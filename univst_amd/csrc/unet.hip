@@ -177,7 +177,6 @@ __global__ __launch_bounds__(256) void temporal_attn_kernel(const half_t* __rest
 // ------------------------------------------------------------------------------------------ handle
 UNet::~UNet() {
     for (auto& kv : idx_tables) (void)hipFree(kv.second);
-    if (arena.base) (void)hipFree(arena.base);
     if (d_counter) (void)hipFree(d_counter);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
@@ -207,9 +206,7 @@ int UNet::load_tensor(const char* key, const void* dev_ptr, int dtype, const int
             return it->second->load_tensor(key + dot + 1, dev_ptr, dtype, shape, ndim, s);
         }
     }
-    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
-    finalized = false;
-    return UV_OK;
+    return Model::load_tensor(key, dev_ptr, dtype, shape, ndim, s);
 }
 
 int UNet::finalize(hipStream_t s) {

@@ -8,14 +8,11 @@
 
 long uv_vae_attn_chunk_rows(long score_bytes, long N);      // query rows per attention chunk under a score budget (vae.hip)
 
-struct Vae : WeightStore {
+struct Vae : Model {
     univst_vae_cfg cfg;
     std::unordered_map<std::string, float> mix;       // ST-resblock prefix -> time_mixer.mix_factor
-    Arena arena;
-    bool finalized = false;
 
-    ~Vae();
-    int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
+    Vae() : Model("vae") {}
     int finalize(hipStream_t s);
     int reserve(long imgs, int H, int W);
     int decode(const half_t* z, long imgs, int num_frames, int h, int w, half_t* out, hipStream_t s);

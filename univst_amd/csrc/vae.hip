@@ -106,16 +106,6 @@ long uv_vae_attn_chunk_rows(long score_bytes, long N) {
     return Qc > N ? N : Qc;
 }
 
-Vae::~Vae() {
-    if (arena.base) (void)hipFree(arena.base);
-}
-
-int Vae::load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s) {
-    UV_RUN(load(key, dev_ptr, dtype, shape, ndim, s));
-    finalized = false;
-    return UV_OK;
-}
-
 int Vae::finalize(hipStream_t s) {
     clear_derived();
     mix.clear();

@@ -3,8 +3,6 @@
 ``NativeRAFT`` stands where the reference builds torchvision's ``raft_large`` (src/cal_optica_flow.py:53-55): it takes that model's state
 dict unchanged and runs one C-ABI call per image pair (univst_raft_*, csrc/raft.hip): 12 flow updates, final flow only, eval mode.  The
 network is third-party: restated from its published definition, parity unpinned by the reference (tests/raft_ref.py is the yardstick)."""
-import ctypes as C
-
 import torch
 
 from . import _native
@@ -19,23 +17,13 @@ def _check_size(h, w):
                          "should be at least 8 * 16 = 128")
 
 
-class NativeRAFT:
+class NativeRAFT(_native.NativeHandle):
+    _kind, _noun = "raft", "flow estimator"
+
     def __init__(self, state_dict, device="cuda"):
-        lib = _native.load()
-        h = C.c_void_p()
-        _native.check(lib.univst_raft_create(C.byref(h)), "raft_create")
-        self._h = h
         self.device = torch.device(device)
-        st = _native.stream_ptr()
-        for k, v in state_dict.items():
-            if k.endswith("num_batches_tracked") or not torch.is_tensor(v):
-                continue
-            t = v.detach().to(device=device)
-            t = t.to(torch.float32 if t.dtype != torch.float16 else t.dtype).contiguous()
-            shape = (C.c_int64 * max(1, t.dim()))(*t.shape)
-            _native.check(lib.univst_raft_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
-                          f"raft_load_tensor({k})")
-        torch.cuda.current_stream().synchronize()
+        items = [(k, v) for k, v in state_dict.items() if torch.is_tensor(v) and not k.endswith("num_batches_tracked")]
+        self._h = _native.load_handle("raft", (), items, other_dtype=torch.float32, device=device)
 
     from_state_dict = classmethod(lambda cls, sd, device="cuda": cls(sd, device=device))
 
@@ -51,20 +39,8 @@ class NativeRAFT:
                 sd = sd["state_dict"]
         return cls(sd, device=device)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _native.load().univst_raft_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
     def _img(self, t, what):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"NativeRAFT: the native flow estimator runs on the GPU only (no CPU / eager fallback); {what} is "
-                               f"{'a ' + str(t.device) + ' tensor' if torch.is_tensor(t) else type(t).__name__}")
-        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        if self._gpu_only(t, what).dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
             raise ValueError(f"NativeRAFT: {what} must be uint8 [H, W, 3], got {t.dtype} {tuple(t.shape)}")
         return t.contiguous()
 

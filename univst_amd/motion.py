@@ -31,14 +31,12 @@ def check_supported(cfg):
                                   "(the native module attends at the full width: 1)")
 
 
-class NativeMotionModule:
+class NativeMotionModule(_native.NativeModuleFacade):
+    _kind, _noun = "motion", "motion module"
+
     def __init__(self, state_dict, config=None, prefix="", device="cuda"):
         sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix) and torch.is_tensor(v) and v.is_floating_point()}
-        cfg = dict(DEFAULT_CONFIG)
-        if config is not None:
-            get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
-            has = (lambda k: k in config) if isinstance(config, dict) else (lambda k: hasattr(config, k))
-            cfg.update({k: get(k) for k in DEFAULT_CONFIG if has(k) and get(k) is not None})
+        cfg = self.merge_config(DEFAULT_CONFIG, config)
         if "temporal_transformer.norm.weight" not in sd:
             raise KeyError(f"NativeMotionModule: {prefix}temporal_transformer.norm.weight is not in the state dict (is the prefix right?)")
         cfg["channels"] = int(sd["temporal_transformer.norm.weight"].shape[0])
@@ -51,22 +49,10 @@ class NativeMotionModule:
         self.device = torch.device(device)
         # without position encoding there is no table: the length only has to be one the handle accepts
         max_len = cfg["temporal_position_encoding_max_len"] if cfg["temporal_position_encoding"] else min(cfg["temporal_position_encoding_max_len"], MAX_FRAMES)
-        lib = _native.load()
         c = _native.MotionCfg(cfg["channels"], cfg["num_attention_heads"], cfg["num_transformer_block"], len(cfg["attention_block_types"]),
                               cfg["norm_num_groups"], max_len, int(bool(cfg["temporal_position_encoding"])),
                               cfg["norm_eps"], cfg["layer_norm_eps"])
-        h = C.c_void_p()
-        _native.check(lib.univst_motion_create(C.byref(c), C.byref(h)), "motion_create")
-        self._h = h
-        st = _native.stream_ptr()
-        for k, v in sd.items():
-            t = v.detach().to(device=device)
-            t = t.to(torch.float16 if t.dtype not in (torch.float16, torch.float32) else t.dtype).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _native.check(lib.univst_motion_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
-                          f"motion_load_tensor({k})")
-        _native.check(lib.univst_motion_finalize(h, st), "motion_finalize")
-        torch.cuda.current_stream().synchronize()
+        self._h = _native.load_handle("motion", (C.byref(c),), sd.items(), other_dtype=torch.float16, device=device)
 
     @classmethod
     def from_module(cls, m, device="cuda"):
@@ -84,43 +70,8 @@ class NativeMotionModule:
                    temporal_attention_dim_div=m.temporal_transformer.norm.num_channels // attn.to_q.weight.shape[0])
         return cls(m.state_dict(), config=cfg, device=device)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _native.load().univst_motion_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    # ---- what the call sites touch of an nn.Module
-    @property
-    def dtype(self):
-        return torch.float16
-
-    def to(self, *a, **k):
-        return self
-
-    def cuda(self, *a, **k):
-        return self
-
-    def requires_grad_(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def query(self, name):
-        """read-outs of the handle (include/univst.h ``univst_motion_query``): ``arena_high_water``, ``weight_bytes``"""
-        out = C.c_double()
-        _native.check(_native.load().univst_motion_query(self._h, name.encode(), C.byref(out)), f"motion_query({name})")
-        return int(out.value)
-
     def _check(self, t, what):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"NativeMotionModule.{what}: the native motion module runs on the GPU only (no CPU / eager fallback); got "
-                               f"{'a ' + str(t.device) + ' tensor' if torch.is_tensor(t) else type(t).__name__}")
-        if t.dtype != torch.float16:
+        if self._gpu_only(t, what).dtype != torch.float16:
             raise TypeError(f"NativeMotionModule.{what}: fp16 activations only, got {t.dtype}")
         return t
 

@@ -39,13 +39,11 @@ class CLIPTextOutput:
         return len(self._fields)
 
 
-class NativeCLIPText:
+class NativeCLIPText(_native.NativeModuleFacade):
+    _kind, _noun = "clip", "text encoder"
+
     def __init__(self, state_dict, config=None, with_projection=None, device="cuda"):
-        cfg = dict(DEFAULT_CONFIG)
-        if config is not None:
-            get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
-            has = (lambda k: k in config) if isinstance(config, dict) else (lambda k: hasattr(config, k))
-            cfg.update({k: get(k) for k in DEFAULT_CONFIG if has(k) and get(k) is not None})
+        cfg = self.merge_config(DEFAULT_CONFIG, config)
         if with_projection is None:
             with_projection = "text_projection.weight" in state_dict
         if cfg["hidden_act"] not in _ACTS:
@@ -53,26 +51,12 @@ class NativeCLIPText:
         self.with_projection = bool(with_projection)
         self.config = types.SimpleNamespace(use_attention_mask=False, **cfg)
         self.device = torch.device(device)
-        lib = _native.load()
         c = _native.ClipCfg(cfg["vocab_size"], cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
                             cfg["max_position_embeddings"], _ACTS[cfg["hidden_act"]], cfg["layer_norm_eps"],
                             cfg["projection_dim"] if self.with_projection else 0, cfg["eos_token_id"])
-        h = C.c_void_p()
-        _native.check(lib.univst_clip_create(C.byref(c), C.byref(h)), "clip_create")
-        self._h = h
-        st = _native.stream_ptr()
-        for k, v in state_dict.items():
-            if not torch.is_tensor(v) or not v.is_floating_point():       # (old checkpoints carry embeddings.position_ids, an int64 buffer)
-                continue
-            if k == "text_projection.weight" and not self.with_projection:
-                continue
-            t = v.detach().to(device=device)
-            t = t.to(torch.float16 if t.dtype not in (torch.float16, torch.float32) else t.dtype).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _native.check(lib.univst_clip_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
-                          f"clip_load_tensor({k})")
-        _native.check(lib.univst_clip_finalize(h, st), "clip_finalize")
-        torch.cuda.current_stream().synchronize()
+        # (old checkpoints carry embeddings.position_ids, an int64 buffer)
+        items = [(k, v) for k, v in state_dict.items() if torch.is_tensor(v) and v.is_floating_point() and (self.with_projection or k != "text_projection.weight")]
+        self._h = _native.load_handle("clip", (C.byref(c),), items, other_dtype=torch.float16, device=device)
 
     @classmethod
     def from_module(cls, m, device="cuda"):
@@ -111,50 +95,12 @@ class NativeCLIPText:
                 return cls(sd, config=raw, with_projection="CLIPTextModelWithProjection" in names, device=device)
         raise FileNotFoundError(f"no model.safetensors / model.fp16.safetensors / pytorch_model.bin under {d}")
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _native.load().univst_clip_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    # ---- what the call sites touch of an nn.Module
-    @property
-    def dtype(self):
-        return torch.float16
-
-    def to(self, *a, **k):
-        return self
-
-    def cuda(self, *a, **k):
-        return self
-
-    def requires_grad_(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def query(self, name):
-        """read-outs of the handle (include/univst.h ``univst_clip_query``): ``arena_high_water``, ``splitk_bytes``"""
-        out = C.c_double()
-        _native.check(_native.load().univst_clip_query(self._h, name.encode(), C.byref(out)), f"clip_query({name})")
-        return int(out.value)
-
     def arena_high_water(self):
         return self.query("arena_high_water")
 
-    def _check(self, t, what):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise RuntimeError(f"NativeCLIPText.{what}: the native text encoder runs on the GPU only (no CPU / eager fallback); got "
-                               f"{'a ' + str(t.device) + ' tensor' if torch.is_tensor(t) else type(t).__name__}")
-        return t
-
     @torch.no_grad()
     def __call__(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=True, **_):
-        ids = self._check(input_ids, "__call__")
+        ids = self._gpu_only(input_ids, "__call__")
         if ids.dim() != 2 or ids.dtype not in (torch.int64, torch.int32):
             raise ValueError(f"NativeCLIPText: input_ids must be an integer tensor [B, S], got {ids.dtype} {tuple(ids.shape)}")
         if attention_mask is not None and not bool((attention_mask != 0).all()):
@@ -262,36 +208,22 @@ def t5_config_from_dir(path, subfolder="text_encoder_3"):
     return d, raw
 
 
-class NativeT5Encoder:
+class NativeT5Encoder(_native.NativeModuleFacade):
     """transformers' ``T5EncoderModel`` (SD3 / SD3.5 ``text_encoder_3``, T5 v1.1-XXL) on the native library: ``enc(ids)[0]`` =
     ``enc(ids).last_hidden_state`` fp16 [B, S, d_model], one C-ABI call per encode (univst_t5_*, csrc/t5.hip), with an fp32 residual stream.  It takes
     that class's state dict unchanged.  tests/t5_ref.py is the yardstick, held to transformers by tests/test_t5_ref.py."""
 
+    _kind, _noun = "t5", "text encoder"
+
     def __init__(self, state_dict, config=None, device="cuda"):
-        cfg = dict(T5_DEFAULT_CONFIG)
-        if config is not None:
-            get = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
-            has = (lambda k: k in config) if isinstance(config, dict) else (lambda k: hasattr(config, k))
-            cfg.update({k: get(k) for k in T5_DEFAULT_CONFIG if has(k) and get(k) is not None})
+        cfg = self.merge_config(T5_DEFAULT_CONFIG, config)
         if cfg["feed_forward_proj"] != "gated-gelu":
             raise ValueError(f"NativeT5Encoder: feed_forward_proj {cfg['feed_forward_proj']!r} (the native encoder has gated-gelu only)")
         self.config = types.SimpleNamespace(**cfg)
         self.device = torch.device(device)
-        lib = _native.load()
         c = _native.T5Cfg(cfg["vocab_size"], cfg["d_model"], cfg["d_ff"], cfg["num_layers"], cfg["num_heads"], cfg["d_kv"],
                           cfg["relative_attention_num_buckets"], cfg["relative_attention_max_distance"], cfg["layer_norm_epsilon"])
-        h = C.c_void_p()
-        _native.check(lib.univst_t5_create(C.byref(c), C.byref(h)), "t5_create")
-        self._h = h
-        st = _native.stream_ptr()
-        for k, v in t5_tensors(state_dict).items():
-            t = v.detach().to(device=device)
-            t = t.to(torch.float16 if t.dtype not in (torch.float16, torch.float32) else t.dtype).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _native.check(lib.univst_t5_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
-                          f"t5_load_tensor({k})")
-        _native.check(lib.univst_t5_finalize(h, st), "t5_finalize")
-        torch.cuda.current_stream().synchronize()
+        self._h = _native.load_handle("t5", (C.byref(c),), t5_tensors(state_dict).items(), other_dtype=torch.float16, device=device)
 
     @classmethod
     def from_module(cls, m, device="cuda"):
@@ -307,47 +239,12 @@ class NativeT5Encoder:
         d, raw = t5_config_from_dir(path, subfolder)
         return cls(read_weight_files(d), config=raw, device=device)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _native.load().univst_t5_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    # ---- what the call sites touch of an nn.Module
-    @property
-    def dtype(self):
-        return torch.float16
-
-    def to(self, *a, **k):
-        return self
-
-    def cuda(self, *a, **k):
-        return self
-
-    def requires_grad_(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def query(self, name):
-        """read-outs of the handle (include/univst.h ``univst_t5_query``): ``arena_high_water``, ``splitk_bytes``, ``weight_bytes``"""
-        out = C.c_double()
-        _native.check(_native.load().univst_t5_query(self._h, name.encode(), C.byref(out)), f"t5_query({name})")
-        return int(out.value)
-
     def arena_high_water(self):
         return self.query("arena_high_water")
 
     @torch.no_grad()
     def __call__(self, input_ids, attention_mask=None, output_hidden_states=False, return_dict=True, **_):
-        if not torch.is_tensor(input_ids) or not input_ids.is_cuda:
-            raise RuntimeError("NativeT5Encoder.__call__: the native text encoder runs on the GPU only (no CPU / eager fallback); got "
-                               f"{'a ' + str(input_ids.device) + ' tensor' if torch.is_tensor(input_ids) else type(input_ids).__name__}")
-        ids = input_ids
+        ids = self._gpu_only(input_ids, "__call__")
         if ids.dim() != 2 or ids.dtype not in (torch.int64, torch.int32):
             raise ValueError(f"NativeT5Encoder: input_ids must be an integer tensor [B, S], got {ids.dtype} {tuple(ids.shape)}")
         if output_hidden_states:

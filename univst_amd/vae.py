@@ -35,30 +35,17 @@ class _LatentDist:
         return self.mean
 
 
-class NativeTemporalVAE(torch.nn.Module):
+class NativeTemporalVAE(_native.NativeHandle, torch.nn.Module):
+    _kind, _noun = "vae", "VAE"
+
     def __init__(self, state_dict, config=None, device="cuda"):
         super().__init__()
-        cfg = dict(DEFAULT_CONFIG)
-        if config is not None:
-            cfg.update({k: (config[k] if isinstance(config, dict) else getattr(config, k)) for k in DEFAULT_CONFIG
-                        if (k in config if isinstance(config, dict) else hasattr(config, k))})
+        cfg = self.merge_config(DEFAULT_CONFIG, config, keep_none=True)
         self.config = types.SimpleNamespace(**cfg)
         self._dummy = torch.nn.Parameter(torch.zeros(1, device=device, dtype=torch.float16), requires_grad=False)   # .parameters() / .dtype / .device for the call sites
-        lib = _native.load()
         c = _native.VaeCfg(cfg["in_channels"], cfg["out_channels"], cfg["latent_channels"], (C.c_int * 4)(*cfg["block_out_channels"]),
                            cfg["layers_per_block"], cfg["norm_num_groups"])
-        h = C.c_void_p()
-        _native.check(lib.univst_vae_create(C.byref(c), C.byref(h)), "vae_create")
-        self._h = h
-        st = _native.stream_ptr()
-        for k, v in state_dict.items():
-            t = v.detach().to(device=device)
-            t = t.to(torch.float16 if t.dtype not in (torch.float16, torch.float32) else t.dtype).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _native.check(lib.univst_vae_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
-                          f"vae_load_tensor({k})")
-        _native.check(lib.univst_vae_finalize(h, st), "vae_finalize")
-        torch.cuda.current_stream().synchronize()
+        self._h = _native.load_handle("vae", (C.byref(c),), state_dict.items(), other_dtype=torch.float16, device=device)
 
     @classmethod
     def from_module(cls, vae, device="cuda"):
@@ -93,15 +80,6 @@ class NativeTemporalVAE(torch.nn.Module):
                 return cls(sd, config=cfg, device=device)
         raise FileNotFoundError(f"no diffusion_pytorch_model.safetensors / .bin under {d}")
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _native.load().univst_vae_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
     @property
     def dtype(self):
         return torch.float16
@@ -111,9 +89,7 @@ class NativeTemporalVAE(torch.nn.Module):
         return self._dummy.device
 
     def _check(self, t, what):
-        if not t.is_cuda:
-            raise RuntimeError(f"NativeTemporalVAE.{what}: the native VAE runs on the GPU only (no CPU / eager fallback); got a {t.device} tensor")
-        return t.to(torch.float16).contiguous()
+        return self._gpu_only(t, what).to(torch.float16).contiguous()
 
     @torch.no_grad()
     def decode(self, z, num_frames=1, return_dict=True, **_):
@@ -194,7 +170,7 @@ def kl_config_from_dir(path, subfolder="vae"):
     return d, {k: v for k, v in raw.items() if not k.startswith("_")}
 
 
-class NativeAutoencoderKL(torch.nn.Module):
+class NativeAutoencoderKL(_native.NativeHandle, torch.nn.Module):
     """Stands where the SD3 pipeline keeps diffusers' ``AutoencoderKL`` (src/sd3/run_*_sd3.py; used at custom_pipeline.py ``_decode`` and
     inversion_tools/flow_inversion.py ``_img_latents``): ``.decode(z, return_dict=False)[0]`` / ``.decode(z).sample``, ``.encode(x).latent_dist.sample()``,
     ``.config.scaling_factor`` / ``.shift_factor``, ``.parameters()``.  It takes that class's state dict (old attention names included, ``kl_tensors``) and
@@ -204,33 +180,20 @@ class NativeAutoencoderKL(torch.nn.Module):
     ``attn_score_bytes`` / ``pass_bytes`` (0: 128 MiB / 8 GiB) bound the attention's score matrix and the activation arena (include/univst.h).
     The network is third-party: restated from its published definition, parity unpinned (tests/klvae_ref.py is a second restatement)."""
 
+    _kind, _noun = "klvae", "VAE"
+
     def __init__(self, state_dict, config=None, device="cuda", attn_score_bytes=0, pass_bytes=0):
         super().__init__()
-        cfg = dict(KL_DEFAULT_CONFIG)
-        if config is not None:
-            cfg.update({k: (config[k] if isinstance(config, dict) else getattr(config, k)) for k in KL_DEFAULT_CONFIG
-                        if (k in config if isinstance(config, dict) else hasattr(config, k))})
+        cfg = self.merge_config(KL_DEFAULT_CONFIG, config, keep_none=True)
         if cfg["shift_factor"] is None:      # SD-v1.5's config
             cfg["shift_factor"] = 0.0
         cfg["block_out_channels"] = tuple(cfg["block_out_channels"])
         self.config = types.SimpleNamespace(**cfg)
         self._dummy = torch.nn.Parameter(torch.zeros(1, device=device, dtype=torch.float16), requires_grad=False)   # .parameters() / .dtype / .device for the call sites
-        lib = _native.load()
         c = _native.KlVaeCfg(cfg["in_channels"], cfg["out_channels"], cfg["latent_channels"], (C.c_int * 4)(*cfg["block_out_channels"]),
                              cfg["layers_per_block"], cfg["norm_num_groups"], int(bool(cfg["use_quant_conv"])), int(bool(cfg["use_post_quant_conv"])),
                              int(attn_score_bytes), int(pass_bytes))
-        h = C.c_void_p()
-        _native.check(lib.univst_klvae_create(C.byref(c), C.byref(h)), "klvae_create")
-        self._h = h
-        st = _native.stream_ptr()
-        for k, v in kl_tensors(state_dict).items():
-            t = v.detach().to(device=device)
-            t = t.to(torch.float16 if t.dtype not in (torch.float16, torch.float32) else t.dtype).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _native.check(lib.univst_klvae_load_tensor(h, k.encode(), _native.ptr(t), 0 if t.dtype == torch.float16 else 1, shape, t.dim(), st),
-                          f"klvae_load_tensor({k})")
-        _native.check(lib.univst_klvae_finalize(h, st), "klvae_finalize")
-        torch.cuda.current_stream().synchronize()
+        self._h = _native.load_handle("klvae", (C.byref(c),), kl_tensors(state_dict).items(), other_dtype=torch.float16, device=device)
 
     @classmethod
     def from_module(cls, vae, device="cuda", **kw):
@@ -255,15 +218,6 @@ class NativeAutoencoderKL(torch.nn.Module):
                 return cls(sd, config=cfg, device=device, attn_score_bytes=attn_score_bytes, pass_bytes=pass_bytes)
         raise FileNotFoundError(f"no diffusion_pytorch_model.safetensors / .bin under {d}")
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                _native.load().univst_klvae_destroy(h)
-                self._h = None
-            except Exception:      # interpreter shutdown: torch's own module attributes may already be gone
-                pass
-
     @property
     def dtype(self):
         return torch.float16
@@ -273,15 +227,7 @@ class NativeAutoencoderKL(torch.nn.Module):
         return self._dummy.device
 
     def _check(self, t, what):
-        if not t.is_cuda:
-            raise RuntimeError(f"NativeAutoencoderKL.{what}: the native VAE runs on the GPU only (no CPU / eager fallback); got a {t.device} tensor")
-        return t.to(torch.float16).contiguous()
-
-    def query(self, name):
-        """a read-out of the handle: "arena_high_water", "arena_bytes", "attn_chunks", "passes" (include/univst.h)"""
-        v = C.c_double()
-        _native.check(_native.load().univst_klvae_query(self._h, name.encode(), C.byref(v)), f"klvae_query({name})")
-        return v.value
+        return self._gpu_only(t, what).to(torch.float16).contiguous()
 
     @torch.no_grad()
     def decode(self, z, return_dict=True, **_):

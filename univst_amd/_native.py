@@ -672,11 +672,21 @@ def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False,
     return (out_i, out_t) if enc is not None else out_i
 
 
+def _qkv_ld(qkv, F, N):
+    """row stride of a fused [3*F*N, >= 3C] q | k | v buffer: a column-sliced view of a wider buffer is fine, a column stride is not."""
+    if not (qkv.is_cuda and qkv.dtype == torch.float16):
+        raise ValueError(f"adain shift: expected an fp16 CUDA/HIP tensor, got {qkv.dtype} {qkv.device}")
+    if qkv.dim() != 2 or qkv.shape[0] != 3 * F * N or qkv.stride(1) != 1:
+        raise ValueError(f"adain shift: expected a [3*F*N = {3 * F * N}, >= 3C] buffer with unit column stride, got {tuple(qkv.shape)} "
+                         f"strides {tuple(qkv.stride())}")
+    return qkv.stride(0)
+
+
 def sd3_adain_shift_(qkv, F, N, C_, heads, alpha, beta, gamma):
-    """in place on the fused [3*F*N, 3C] buffer (SD3 plugin's AdaIN shift)."""
-    _f16(qkv)
+    """in place on the fused [3*F*N, 3C] buffer (SD3 plugin's AdaIN shift); qkv may be a column-sliced view (row stride >= 3C)."""
+    ld = _qkv_ld(qkv, F, N)
     ws = torch.empty(4 * F * 2 * C_ + 2 * F * 2 * heads, device=qkv.device, dtype=torch.float32)
-    check(load().univst_sd3_adain_shift(ptr(qkv), qkv.shape[-1], F, N, C_, heads, alpha, beta, gamma, ptr(ws), stream_ptr()), "sd3_adain_shift")
+    check(load().univst_sd3_adain_shift(ptr(qkv), ld, F, N, C_, heads, alpha, beta, gamma, ptr(ws), stream_ptr()), "sd3_adain_shift")
     return qkv
 
 
@@ -772,11 +782,11 @@ def axpbypcz(x, y, z, a, b, c, out=None):
 
 
 def attention_adain_shift_(qkv, F, N, C_, alpha, beta, gamma, return_stats=False):
-    """in place on the fused [3*F*N, 3C] buffer.  return_stats: also the style branch's per-(frame, channel) statistics the kernel
-    used, (mean, unbiased std) each [F, 2C] (K columns then V columns)."""
-    _f16(qkv)
+    """in place on the fused [3*F*N, 3C] buffer; qkv may be a column-sliced view (row stride >= 3C).  return_stats: also the style
+    branch's per-(frame, channel) statistics the kernel used, (mean, unbiased std) each [F, 2C] (K columns then V columns)."""
+    ld = _qkv_ld(qkv, F, N)
     ws = torch.empty(4 * F * 2 * C_, device=qkv.device, dtype=torch.float32)
-    check(load().univst_attention_adain_shift(ptr(qkv), qkv.shape[-1], F, N, C_, alpha, beta, gamma, ptr(ws), stream_ptr()),
+    check(load().univst_attention_adain_shift(ptr(qkv), ld, F, N, C_, alpha, beta, gamma, ptr(ws), stream_ptr()),
           "attention_adain_shift")
     if return_stats:
         return qkv, ws[:F * 2 * C_].view(F, 2 * C_), ws[F * 2 * C_:2 * F * 2 * C_].view(F, 2 * C_)
@@ -788,6 +798,30 @@ def latent_adain(cnt, sty, out=None):
     _, Cl, F, H, W = cnt.shape
     out = torch.empty_like(cnt) if out is None else out
     check(load().univst_latent_adain(ptr(cnt), ptr(sty), ptr(out), Cl, F, H * W, stream_ptr()), "latent_adain")
+    return out
+
+
+def latent_adain_stats(cnt):
+    """frame-shard half 1 of latent_adain: per-channel (sum, sum of squares) of the local content frames [1, C, Fl, h, w] -> [C, 2] fp32,
+    to be summed over the ranks."""
+    _f16(cnt)
+    _, Cl, Fl, H, W = cnt.shape
+    st = torch.empty(Cl, 2, device=cnt.device, dtype=torch.float32)
+    check(load().univst_latent_adain_stats(ptr(cnt), ptr(st), Cl, Fl, H * W, stream_ptr()), "latent_adain_stats")
+    return st
+
+
+def latent_adain_apply(cnt, sty, stats, n_total, out=None):
+    """frame-shard half 2: latent_adain of the local frames with the content statistics of the whole clip (stats [C, 2] fp32 summed
+    over the ranks, n_total = F * h * w of the clip)."""
+    _f16(cnt), _f16(sty)
+    if sty.shape != cnt.shape:
+        raise ValueError(f"latent_adain_apply: cnt {tuple(cnt.shape)} and sty {tuple(sty.shape)} differ in shape")
+    _, Cl, Fl, H, W = cnt.shape
+    if not (stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 2 * Cl):
+        raise ValueError(f"latent_adain_apply: stats must be {Cl} x 2 contiguous fp32 on the GPU")
+    out = torch.empty_like(cnt) if out is None else out
+    check(load().univst_latent_adain_apply(ptr(cnt), ptr(sty), ptr(stats), int(n_total), ptr(out), Cl, Fl, H * W, stream_ptr()), "latent_adain_apply")
     return out
 
 

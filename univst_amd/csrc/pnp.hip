@@ -263,9 +263,12 @@ __global__ __launch_bounds__(1024) void latent_adain_apply_kernel(const half_t* 
     const float cmu = (float)mu, crstd = (float)(1.0 / sqrt(var + 1e-5));
     for (int f = 0; f < F; ++f) {
         const half_t* sp = sty + base + (long)f * HW;
+        // one pass, about a pivot (the frame's first element): raw fp32 sum(x), sum(x^2) give a constant style frame (0.7 over 5x7) a std
+        // of 2e-4 instead of 0 and lose the variance when |mean| >> std (same reason as the colstats pivot above)
+        const float pv = (float)sp[0];
         float a = 0.f, b = 0.f;
         for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            float v = (float)sp[i];
+            float v = (float)sp[i] - pv;
             a += v;
             b += v * v;
         }
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(1024) void latent_adain_apply_kernel(const half_t* 
                 y += red[1][i];
             }
             double m = x / HW, v = (y - x * m) / (HW > 1 ? HW - 1 : 1);
-            bc[0] = (float)m;
+            bc[0] = (float)((double)pv + m);
             bc[1] = (float)sqrt(v > 0 ? v : 0);
         }
         __syncthreads();
@@ -319,7 +322,9 @@ int uv_launch_colstats(const half_t* x, long ld, int F, int N, int ncols, float*
 
 int uv_launch_adain_shift(half_t* qkv, long ld, int F, int N, int C, float* mean, float* stdv, float alpha, float beta,
                           float gamma, hipStream_t stream) {
-    UV_REQUIRE(C % 8 == 0 && C <= 2048 && ld % 8 == 0, "adain_shift: C=%d ld=%ld unsupported", C, ld);
+    UV_REQUIRE(F >= 1 && N >= 1, "adain_shift: F=%d N=%d must be positive", F, N);
+    UV_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && ld % 8 == 0, "adain_shift: C=%d ld=%ld unsupported", C, ld);
+    UV_REQUIRE(ld >= 3L * C, "adain_shift: ld=%ld is less than the 3C=%ld columns of q | k | v", ld, 3L * C);
     // style statistics: K1|V1 columns [C,3C) of the style branch rows [F*N, 2*F*N)
     uv_prof_begin(UV_CLS_ADAIN, 0.0, 2.0 * (double)F * N * C * 11.0, stream);   // 6 reads + 3 writes + 2 stat reads of [F,N,C] fp16
     int rc = uv_launch_colstats(qkv + (long)F * N * ld + C, ld, F, N, 2 * C, mean, stdv, stream);

@@ -435,7 +435,11 @@ int univst_axpbypcz(const void* x, const void* y, const void* z, void* out, floa
 // in place on the fused [3*F*N, 3C] q | k | v buffer (row stride ld; branch 0 content, 1 style, 2 stylised); ws: 4*F*2C + 2*F*2*heads floats
 int univst_sd3_adain_shift(void* qkv, int64_t ld, int F, int N, int C, int heads, float alpha, float beta, float gamma, void* ws, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    UV_REQUIRE(qkv && ws && F >= 1 && N >= 2 && heads >= 1 && C % heads == 0 && C % 8 == 0, "sd3_adain_shift: bad argument");
+    UV_REQUIRE(qkv && ws, "sd3_adain_shift: null argument");
+    UV_REQUIRE(F >= 1 && N >= 2, "sd3_adain_shift: F=%d must be positive and N=%d at least 2 (the style std is unbiased)", F, N);
+    UV_REQUIRE(heads >= 1 && C >= 8 && C % heads == 0 && C % 8 == 0, "sd3_adain_shift: C=%d heads=%d unsupported", C, heads);
+    UV_REQUIRE(ld % 8 == 0 && ld >= 3L * C, "sd3_adain_shift: ld=%ld must be a multiple of 8 and at least the 3C=%ld columns of q | k | v",
+               (long)ld, 3L * C);
     half_t* q = (half_t*)qkv;
     float *smean = (float*)ws, *sstd = smean + (long)F * 2 * C, *cmean = sstd + (long)F * 2 * C, *cstd = cmean + (long)F * 2 * C;
     float *mu = cstd + (long)F * 2 * C, *rstd = mu + (long)F * 2 * heads;

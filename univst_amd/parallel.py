@@ -314,15 +314,10 @@ class FrameShard:
     def latent_adain(self, cnt: torch.Tensor, sty: torch.Tensor) -> torch.Tensor:
         if self.world == 1:
             return _native.latent_adain(cnt, sty)
-        lib = _native.load()
-        _, Cl, Fl, H, W = cnt.shape
-        st = torch.empty(Cl * 2, device=cnt.device, dtype=torch.float32)
-        _native.check(lib.univst_latent_adain_stats(cnt.data_ptr(), st.data_ptr(), Cl, Fl, H * W, _native.stream_ptr()), "adain_stats")
+        _, _, _, H, W = cnt.shape
+        st = _native.latent_adain_stats(cnt)
         self.comm.all_reduce_sum(st)
-        out = torch.empty_like(cnt)
-        _native.check(lib.univst_latent_adain_apply(cnt.data_ptr(), sty.data_ptr(), st.data_ptr(), self.frames * H * W, out.data_ptr(),
-                                                    Cl, Fl, H * W, _native.stream_ptr()), "adain_apply")
-        return out
+        return _native.latent_adain_apply(cnt, sty, st, self.frames * H * W)
 
     # ------------------------------------------------------------------ one step of the transfer loop on the local frames
     def make_step_fn(self, pipe, content, style, text3, mask_m=None, n=50):

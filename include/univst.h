@@ -77,6 +77,10 @@ int univst_unet_reserve(univst_unet* h, int B, int F, int H, int W);
 int univst_unet_forward(univst_unet* h, const void* sample, float timestep, const void* text, int B, int F, int H,
                         int W, int text_len, const univst_pnp* pnp, void* eps_out, void* feat_out, int ft_index,
                         void* stream);
+/* univst_unet_forward plus the feature tap on every kind of handle: feat_out receives the output of up_blocks[ft_index] (after its upsampler)
+ * for batch element 0 as [F,H',W',C] fp16 (animatediff/models/unet.py:453-459).  feat_out NULL or ft_index outside 0..3: UNIVST_ERR_ARG before any launch. */
+int univst_unet_forward_tap(univst_unet* h, const void* sample, float timestep, const void* text, int B, int F, int H, int W, int text_len,
+                            const univst_pnp* pnp, void* eps_out, void* feat_out, int ft_index, void* stream);
 /* frame-sharded multi-GPU: this rank holds frames [rank*F, (rank+1)*F) of a clip of world*F frames
  * for ALL branches.  comm_ws is a caller-owned device workspace (>= 64 KiB + 4 x the largest frame pack); the callbacks are invoked on the
  * host while forward() enqueues work and must enqueue the collective on the SAME stream forward() was given (RCCL through
@@ -376,7 +380,7 @@ int univst_temporal_attention(const void* qkv, int64_t ldx, const void* pe_qkv, 
  *   finalize finds on the device the modules whose proj_out (weight and bias) is still all zeros (zero_initialize: no motion checkpoint loaded):
  *            they are skipped EXACTLY, so a UNet with 2-D weights only equals the per-frame 2-D UNet.  A module none of whose tensors was loaded
  *            counts as such a module.
- *   forward  refuses F > 32, F > motion.max_len with position encoding on, and a non-NULL feat_out (this UNet has no feature tap).
+ *   forward  refuses F > 32, F > motion.max_len with position encoding on, and a non-NULL feat_out (the feature tap of this UNet is on univst_unet_forward_tap).
  *            PnP: the same 8 decoder attn1 layers and the same univst_pnp; the window is pnp_utils.py:45 of this backbone,
  *            eta1 * 50 <= idx < eta2 * 50 (exclusive at the top, eta1 scaled); outside it the registered forward equals the stock one bit for bit;
  *            alpha / gamma come from the caller (the reference has 0.8 and 2.0).

@@ -83,6 +83,7 @@ SIGNATURES = {
     "univst_unet_finalize": (_I, [_P, _P]),
     "univst_unet_reserve": (_I, [_P, _I, _I, _I, _I]),
     "univst_unet_forward": (_I, [_P, _P, _F, _P, _I, _I, _I, _I, _I, C.POINTER(PnP), _P, _P, _I, _P]),
+    "univst_unet_forward_tap": (_I, [_P, _P, _F, _P, _I, _I, _I, _I, _I, C.POINTER(PnP), _P, _P, _I, _P]),
     "univst_unet_set_comm": (_I, [_P, _I, _I, _P, _L, ALLREDUCE_FN, KVEXCHANGE_FN, _P]),
     "univst_unet_set_option": (_I, [_P, C.c_char_p, _I]),
     "univst_unet_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),

@@ -9,8 +9,9 @@ Kept, so that the class drops into the reference's scripts: the module tree and 
 
 Different: the modules carry parameters only.  The forward is ONE call of the native graph (csrc/unet.hip behind ``univst_unet_create_animatediff``:
 the SD-v1.5 2-D UNet per frame, a motion module behind every resnet / transformer pair); there is no PyTorch fallback and no CPU path.  Not built:
-``unet_use_cross_frame_attention`` / ``unet_use_temporal_attention`` (animatediff-v2.yaml leaves both off), ``motion_module_decoder_only``, the feature
-dump (``ft_indices``), SparseControlNet inputs."""
+``unet_use_cross_frame_attention`` / ``unet_use_temporal_attention`` (animatediff-v2.yaml leaves both off), ``motion_module_decoder_only``,
+SparseControlNet inputs.  The feature dump (``ft_indices`` / ``ft_timesteps`` / ``ft_path``, unet.py:453-459) is one ``univst_unet_forward_tap`` call and
+writes the reference's file, as the SD mirror does: one block per call, ``last_feature_map`` keeps the tensor."""
 import ctypes as C
 import json
 import os
@@ -388,8 +389,6 @@ class UNet3DConditionModel(nn.Module):
                 ft_timesteps=None, ft_path=None):
         if attention_mask is not None or class_labels is not None:
             raise NotImplementedError("attention_mask / class_labels are not used on the UniVST path")
-        if ft_indices is not None and ft_timesteps is not None and ft_path is not None:
-            raise NotImplementedError("the native AnimateDiff UNet has no feature tap (ft_indices / ft_timesteps / ft_path)")
         if sample.dim() != 5:
             raise ValueError(f"sample must be [B,C,F,H,W], got {tuple(sample.shape)}")
         self._sync_native()
@@ -407,10 +406,27 @@ class UNet3DConditionModel(nn.Module):
         else:
             t = float(timestep)
         eps = torch.empty(B, self.config.out_channels, F_, H, W, device=x.device, dtype=torch.float16)
+        feat, ft_index = None, -1
+        if ft_indices is not None and ft_timesteps is not None and ft_path is not None:          # unet.py:453-459; as the SD mirror: one block per call
+            hits = [i for i in ft_indices if i is not None and 0 <= i < 4]
+            tt = int(t) if float(int(t)) == t else t
+            if hits and any(tt == v for v in ft_timesteps):
+                if len(hits) > 1:
+                    raise NotImplementedError("one feature-dump block per call")
+                ft_index = hits[0]
+                lvl = min(ft_index + 1, 3)
+                feat = torch.empty(F_, (H >> 3) << lvl, (W >> 3) << lvl, list(reversed(self.config.block_out_channels))[ft_index], device=x.device,
+                                   dtype=torch.float16)
         pnp = self._pnp_state()
-        rc = lib.univst_unet_forward(self._native_handle, x.data_ptr(), t, txt.data_ptr(), B, F_, H, W, txt.shape[1],
-                                     C.byref(pnp) if pnp is not None else None, eps.data_ptr(), None, -1, _native.stream_ptr())
-        _native.check(rc, "unet_forward")
+        args = (self._native_handle, x.data_ptr(), t, txt.data_ptr(), B, F_, H, W, txt.shape[1], C.byref(pnp) if pnp is not None else None, eps.data_ptr())
+        if feat is not None:
+            _native.check(lib.univst_unet_forward_tap(*args, feat.data_ptr(), ft_index, _native.stream_ptr()), "unet_forward_tap")
+            save_path = os.path.join(ft_path, f"inversion_feature_map_{ft_index}_block_{tt}_step.pt")
+            torch.save(feat, save_path)
+            print(f"save feature map at: {save_path}")
+            self.last_feature_map = feat
+        else:
+            _native.check(lib.univst_unet_forward(*args, None, -1, _native.stream_ptr()), "unet_forward")
         return UNet3DConditionOutput(sample=eps.to(sample.dtype) if sample.dtype != torch.float16 else eps)
 
     # ------------------------------------------------------------------ loading (unet.py:468-506)

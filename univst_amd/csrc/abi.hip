@@ -227,6 +227,13 @@ int univst_unet_forward(univst_unet* h, const void* sample, float t, const void*
     UV_REQUIRE(h && sample && text && eps, "unet_forward: null argument");
     return h->impl.forward(H(sample), t, H(text), B, F, Hh, W, text_len, pnp, HM(eps), HM(feat), ft_index, S(s));
 }
+int univst_unet_forward_tap(univst_unet* h, const void* sample, float t, const void* text, int B, int F, int Hh, int W, int text_len,
+                            const univst_pnp* pnp, void* eps, void* feat, int ft_index, void* s) {
+    UV_REQUIRE(h && sample && text && eps, "unet_forward_tap: null argument");
+    UV_REQUIRE(feat, "unet_forward_tap: feat_out must not be NULL (univst_unet_forward is the entry without a tap)");
+    UV_REQUIRE(ft_index >= 0 && ft_index <= 3, "unet_forward_tap: ft_index %d outside 0..3", ft_index);
+    return h->impl.forward(H(sample), t, H(text), B, F, Hh, W, text_len, pnp, HM(eps), HM(feat), ft_index, S(s), true);
+}
 int univst_unet_set_comm(univst_unet* h, int rank, int world, void* comm_ws, int64_t comm_ws_bytes, univst_allreduce_fn ar,
                          univst_kv_exchange_fn kv, void* user) {
     UV_REQUIRE(h && world >= 1 && rank >= 0 && rank < world, "set_comm: bad rank/world");

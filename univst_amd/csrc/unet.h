@@ -58,5 +58,5 @@ struct UNet : Model {
     int finalize(hipStream_t s);
     int reserve(int B, int F, int H, int W);
     int forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int W, int text_len,
-                const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s);
+                const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s, bool tap_entry = false);
 };

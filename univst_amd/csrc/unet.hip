@@ -1243,7 +1243,7 @@ struct Fwd {
 };
 
 int UNet::forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int Wd, int text_len,
-                  const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s) {
+                  const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s, bool tap_entry) {
     UV_REQUIRE(finalized, "forward: call univst_unet_finalize after loading weights");
     UV_REQUIRE(world == 1 || (temporal_conv_active.empty() && temporal_attn_active.empty()),
                "forward: trained temporal layers couple all frames of a pixel; frame sharding (world=%d) is not supported with them", world);
@@ -1257,7 +1257,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         UV_REQUIRE(F <= UV_MOTION_MAX_F, "forward: F=%d frames (the AnimateDiff UNet takes at most %d: what the frame-axis attention holds)", F, UV_MOTION_MAX_F);
         UV_REQUIRE(!ad.motion.position_encoding || motions.empty() || F <= ad.motion.max_len,
                    "forward: F=%d frames exceed motion.max_len %d (the position table has max_len rows)", F, ad.motion.max_len);
-        UV_REQUIRE(!feat_out, "forward: feat_out must be NULL: the AnimateDiff UNet has no feature tap");
+        UV_REQUIRE(tap_entry || !feat_out, "forward: feat_out must be NULL: the AnimateDiff UNet has its feature tap on univst_unet_forward_tap");
         UV_REQUIRE(world == 1, "forward: the AnimateDiff UNet cannot be frame-sharded (world=%d)", world);
     }
     UV_RUN(reserve(B, F, H, Wd));

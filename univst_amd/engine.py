@@ -68,8 +68,10 @@ def _dev16(t, device):
 def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv: Sequence[torch.Tensor],
                   style_inv: Sequence[torch.Tensor], mask_u8: Optional[torch.Tensor], num_inference_steps: int = 50,
                   smoother: Optional[Callable] = None, callback: Optional[Callable] = None,
-                  skip_dead_branches: bool = False, shard=None) -> torch.Tensor:
-    """stable_diffusion.py:680-766 of the reference, device-resident.
+                  skip_dead_branches: bool = False, shard=None, *, adain_from_inclusive: bool = False,
+                  register_time_fn: Optional[Callable] = None, pnp_window_closed: Optional[Callable] = None) -> torch.Tensor:
+    """stable_diffusion.py:680-766 of the reference, device-resident; with the three keyword-only parameters also
+    animatediff/pipelines/pipeline_animation.py:503-591.
 
     pipe            object with ``.unet`` (native UNetPseudo3DConditionModel) and ``.scheduler``
     latents         [1,4,F,h,w] fp16 cuda (already latent_adain'ed, run_video_style_transfer_sd.py:57)
@@ -80,6 +82,12 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
     skip_dead_branches  run only the stylised branch once the PnP window is closed (idx > eta2*50): branches
                     0/1 no longer influence branch 2 and their eps is discarded (:712) — identical output,
                     2/3 less work on those steps.  Off by default (reference-equivalent work).
+    adain_from_inclusive  the latent-AdaIN window is 0.8 n <= i <= 0.9 n (pipeline_animation.py:515) instead of the SD loop's
+                    0.8 n < i <= 0.9 n (stable_diffusion.py:704): at n = 50 the two differ at step 40
+    register_time_fn  the backbone's own ``register_time(pipe, i)``; default: the SD backbone's
+    pnp_window_closed  ``(i, eta2) -> bool``, the test ``skip_dead_branches`` uses for "the PnP window is closed at step i";
+                    default ``i > eta2 * 50`` (the SD closure's window is inclusive at the top), the AnimateDiff closure's
+                    exclusive window takes ``i >= eta2 * 50``
     shard           optional ``parallel.FrameShard`` already attached to ``pipe.unet`` (one process per GPU):
                     every argument is the FULL clip on every rank; this rank runs its frames of all three branches and the
                     full stylised latents come back on every rank (all-gather at the end).  The smoother is sequential over
@@ -90,6 +98,8 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
     dev = latents.device
     n = num_inference_steps
     sched.set_timesteps(n)
+    reg_time = register_time if register_time_fn is None else register_time_fn
+    closed = (lambda i, e2: i > e2 * 50) if pnp_window_closed is None else pnp_window_closed
     sharded = shard is not None and shard.world > 1
     if sharded and latents.shape[2] != shard.frames:
         raise ValueError(f"transfer_loop: the shard was built for {shard.frames} frames, the clip has {latents.shape[2]}")
@@ -107,7 +117,7 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
             m = m.reshape(-1, latents.shape[-2], latents.shape[-1])[shard.f0:shard.f0 + shard.local].contiguous()
     eta2 = 0.5
     if skip_dead_branches:
-        register_time(pipe, 0)
+        reg_time(pipe, 0)
         st = unet._pnp_state()       # validates that all eight PnP layers agree (raises otherwise) and returns their window
         eta2 = float(st.eta2) if st is not None else -1.0     # no PnP registered: the branches never interact
     timesteps = [int(t) for t in sched.timesteps.tolist()]          # one D2H copy at most, before the loop
@@ -115,10 +125,10 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
         c_t, s_t = cinv[n - i], sinv[n - i]
         if m is not None and i <= 0.9 * n:
             latents = _native.mask_blend(latents, c_t, m)
-        if i > 0.8 * n and i <= 0.9 * n:
+        if (i >= 0.8 * n if adain_from_inclusive else i > 0.8 * n) and i <= 0.9 * n:
             latents = _native.mask_blend(adain(latents, s_t), c_t, m)
-        register_time(pipe, i)
-        if skip_dead_branches and i > eta2 * 50:
+        reg_time(pipe, i)
+        if skip_dead_branches and closed(i, eta2):
             eps = _unet_single_branch(unet, latents, t, text3[2:3])
         else:
             x = torch.cat([c_t, s_t, latents])

@@ -1,5 +1,7 @@
 """DDIMScheduler with the diffusers 0.35.1 semantics the UniVST SD path relies on (SD-v1.5
 scheduler_config.json: scaled_linear betas, steps_offset=1, leading spacing, set_alpha_to_one=False, eta=0).
+The AnimateDiff pipeline's scheduler (animatediff-v2.yaml noise_scheduler_kwargs) has ``beta_schedule="linear"`` and relies on
+diffusers' default ``set_alpha_to_one=True``; the default HERE stays False (the SD file's value), so that caller passes True.
 Used when ``diffusers`` is not installed; the pipeline is duck-typed and accepts the real diffusers object too
 (it only reads ``timesteps``, ``alphas_cumprod``, ``final_alpha_cumprod``, ``num_inference_steps`` and
 ``config.num_train_timesteps``).  The arithmetic of ``step`` itself runs in the axpby HIP kernel
@@ -22,12 +24,15 @@ class DDIMScheduler:
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  steps_offset=1, set_alpha_to_one=False, clip_sample=False, prediction_type="epsilon",
                  timestep_spacing="leading", **unused):
-        if beta_schedule != "scaled_linear" or prediction_type != "epsilon" or timestep_spacing != "leading" or clip_sample:
-            raise NotImplementedError("only the SD-v1.5 DDIM configuration is implemented")
+        if beta_schedule not in ("scaled_linear", "linear") or prediction_type != "epsilon" or timestep_spacing != "leading" or clip_sample:
+            raise NotImplementedError("only the SD-v1.5 DDIM configuration (scaled_linear betas) and the AnimateDiff one (animatediff-v2.yaml: linear betas) are implemented")
         self.config = _Cfg(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                            beta_schedule=beta_schedule, steps_offset=steps_offset, set_alpha_to_one=set_alpha_to_one,
                            clip_sample=clip_sample, prediction_type=prediction_type, timestep_spacing=timestep_spacing)
-        self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        if beta_schedule == "linear":
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        else:
+            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]

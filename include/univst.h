@@ -559,6 +559,33 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
  * first frame (from rank 0) and of the frame before this rank's first one (from rank - 1) arrive through the communicator's peer
  * writes (one exchange + one one-float all-reduce as a barrier per call; workspace >= 64 KiB + 6 x branches*N*Cin fp16: since round 6 a pack is the layer's HIDDEN rows of a boundary frame, posted on the communicator's forked
  * stream at the start of the op; the receiving rank projects them to K | V, applies the k RMSNorm and the shift, and attends in two phases). */
+/* ---- MX-fp8 q | k | v projections (BASELINE config 5, "MFMA fp8 QKV"); an option, fp16 stays the default ----
+ * Format: OCP MX with e4m3fn elements (OCP, not fnuz): blocks of 32 consecutive K elements, one E8M0 scale byte per block.
+ *   block scale  e = floor(log2(amax)) - 8, and e += 1 when amax * 2^-e > 448, amax = max|x| of the block's fp16 values; amax == 0 -> e = 0;
+ *                scale byte = e + 127.  With this rule no element saturates.
+ *   elements     x * 2^-e (exact) rounded to e4m3 to nearest even.  NaN / Inf inputs are not defined.
+ * univst_mxfp8_quantize: X fp16 rows (row stride ldx elements, a multiple of 8; 16-byte aligned) -> Q e4m3 bytes [rows][K], S E8M0 bytes
+ * [rows][K/32].  K % 32 == 0. */
+int univst_mxfp8_quantize(const void* X, int64_t ldx, int64_t rows, int K, void* Q, void* S, void* stream);
+/* Y[M,N] = deq(X) deq(W)^T + bias: Xq [M][K] / Wq [N][K] e4m3 bytes with Xs [M][K/32] / Ws [N][K/32] scale bytes, bias fp16 [N] or NULL,
+ * Y fp16 (row stride ldy, a multiple of 4).  Products accumulate in fp32 inside the block-scaled MFMA, the bias is added in fp32, one rounding to
+ * fp16 on store.  K % 128 == 0, N % 16 == 0, any M >= 1; anything else is UNIVST_ERR_ARG before any launch. */
+int univst_linear_mxfp8(const void* Xq, const void* Xs, const void* Wq, const void* Ws, const void* bias, void* Y, int64_t ldy, int64_t M, int N,
+                        int K, void* stream);
+/* the quantised FUSED q | k | v weights of one attention module: [3C][Cin] e4m3 bytes and [3C][Cin/32] scale bytes of the consecutive
+ * to_q | to_k | to_v (and add_q | add_k | add_v; NULL when the call has no text stream) */
+typedef struct {
+    const void *qkv, *qkv_scale, *add_qkv, *add_qkv_scale;
+} univst_sd3_mx_weights;
+/* univst_sd3_joint_attention with the two q | k | v projections in MX-fp8: the op quantises its input rows into its own stream-ordered scratch
+ * (rows * Cin * (1 + 1/32) bytes more) and runs univst_linear_mxfp8 against `mx`; biases still come from `w`, and everything behind the
+ * projections is the code of univst_sd3_joint_attention.  mx == NULL is univst_sd3_joint_attention itself, launch for launch.
+ * With mx: Cin % 128 != 0, or q | k | v weights / biases of `w` that are not consecutive (the fused layout), is UNIVST_ERR_ARG; a communicator
+ * of world > 1 is UNIVST_ERR_UNSUPPORTED (the receiver-side projection of the halo rows is not built in MX-fp8). */
+int univst_sd3_joint_attention_mx(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin,
+                                  int heads, int head_dim, int clip_length, int shift, float beta, float rms_eps,
+                                  void* out_img, void* out_txt, const univst_sd3_gated_residual* gated_residual /* may be NULL */,
+                                  univst_comm* comm /* may be NULL */, void* stream, const univst_sd3_mx_weights* mx /* may be NULL */);
 /* the shift alone, in place on a fused [3*F*N, 3C] q | k | v buffer (branch 0 content, 1 style, 2 stylised; row stride ld):
  * q2 <- gamma*(alpha*q0 + (1-alpha)*q2);  k2 <- beta*AdaIN(k2; k1) + (1-beta)*k1 (same for v) with the SD3 plugin's AdaIN
  * (pnp_utils.py:289-302: F.instance_norm over (N, head_dim) jointly per (frame, head), style mean / unbiased std per channel over N).
@@ -645,10 +672,10 @@ int univst_window_store(const float* acc, float weight, uint8_t* dst, int64_t n,
 /* ------------------------------------------------------------------ per-kernel-class HIP-event timing (bench.py roofline leg)
  * classes (one per kernel symbol): 0 gemm_big<0>, 1 gemm_big<1> (conv), 2 gemm_kernel<*,0> (linear), 3 gemm_kernel<*,1>
  * (conv), 4 attention d=40, 5 attention d=80, 6 other attention, 7 groupnorm, 8 layernorm, 9 adain shift, 10 text attention,
- * 11 conv_patch_kernel (LDS-patch 3x3 convs), 12 attn2_fused_kernel.
+ * 11 conv_patch_kernel (LDS-patch 3x3 convs), 12 attn2_fused_kernel, 13 linear_mxfp8_kernel (the MX-fp8 linear; its quantise pass is not bracketed).
  * While enabled every launch of these classes is bracketed by hipEvents on its stream; collect() waits for
  * them and returns per class: summed ms, launch count, algorithmic flops and algorithmic bytes. */
-#define UNIVST_PROFILE_CLASSES 13
+#define UNIVST_PROFILE_CLASSES 14
 int univst_profile_enable(int on);
 int univst_profile_collect(double* ms, int64_t* count, double* flops, double* bytes, int nclasses);
 /* per class, for the records the LAST univst_profile_collect returned: the EXPANDED operand bytes of the GEMM classes — for a 3x3 conv `bytes` above

@@ -62,6 +62,10 @@ class Sd3AttnWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _NAMES]
 
 
+class Sd3MxWeights(C.Structure):
+    _fields_ = [("qkv", C.c_void_p), ("qkv_scale", C.c_void_p), ("add_qkv", C.c_void_p), ("add_qkv_scale", C.c_void_p)]
+
+
 class Sd3GatedResidual(C.Structure):
     _fields_ = [("res_img", C.c_void_p), ("gate_img", C.c_void_p), ("res_txt", C.c_void_p), ("gate_txt", C.c_void_p), ("ld_gate_img", C.c_int64),
                 ("ld_gate_txt", C.c_int64)]
@@ -99,6 +103,8 @@ SIGNATURES = {
     "univst_comm_status": (_I, [_P]),
     "univst_unet_set_comm_native": (_I, [_P, _P]),
     "univst_linear": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
+    "univst_mxfp8_quantize": (_I, [_P, _L, _L, _I, _P, _P, _P]),
+    "univst_linear_mxfp8": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P]),
     "univst_linear_ln": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P]),
     "univst_geglu_xres_permute": (_I, [_P, _P, _I, _I, _P]),
     "univst_frag_pack": (_I, [_P, _P, _I, _I, _P]),
@@ -165,6 +171,8 @@ SIGNATURES = {
     "univst_attention_phase": (_I, [_P, _L, _P, _P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "univst_sd3_joint_attention": (_I, [C.POINTER(Sd3AttnWeights), _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P,
                                         C.POINTER(Sd3GatedResidual), _P, _P]),
+    "univst_sd3_joint_attention_mx": (_I, [C.POINTER(Sd3AttnWeights), _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P,
+                                           C.POINTER(Sd3GatedResidual), _P, _P, C.POINTER(Sd3MxWeights)]),
     "univst_sd3_adain_shift": (_I, [_P, _L, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
     "univst_rmsnorm_heads": (_I, [_P, _L, _L, _I, _I, _P, _F, _P]),
     "univst_linear_gated": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _I, _P]),
@@ -375,6 +383,40 @@ def linear(x, w, bias=None, residual=None, geglu=False, out=None):
         out = torch.empty(M, No, device=x.device, dtype=torch.float16)
     check(load().univst_linear(ptr(x), K, ptr(w), ptr(bias), ptr(residual), No, ptr(out), No, M, N, K, int(geglu),
                                stream_ptr()), "linear")
+    return out
+
+
+def mxfp8_quantize(x):
+    """OCP MX quantisation of fp16 rows (include/univst.h univst_mxfp8_quantize): x fp16 [rows, K] with unit column stride (a column slice of a wider
+    buffer is fine) -> (e4m3fn bytes uint8 [rows, K], E8M0 scale bytes uint8 [rows, K/32])."""
+    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1):
+        raise ValueError(f"mxfp8_quantize: expected fp16 CUDA/HIP rows with contiguous columns, got {x.dtype} {x.device} strides {tuple(x.stride())}")
+    rows, K = x.shape
+    if K % 32:
+        raise ValueError(f"mxfp8_quantize: K = {K} is not a multiple of the 32-element MX block")
+    q = torch.empty(rows, K, device=x.device, dtype=torch.uint8)
+    s = torch.empty(rows, K // 32, device=x.device, dtype=torch.uint8)
+    check(load().univst_mxfp8_quantize(ptr(x), x.stride(0), rows, K, ptr(q), ptr(s), stream_ptr()), "mxfp8_quantize")
+    return q, s
+
+
+def linear_mxfp8(xq, xs, wq, ws, bias=None, out=None):
+    """y[M,N] = deq(xq, xs) deq(wq, ws)^T (+bias) on the block-scaled MFMA (univst_linear_mxfp8): xq [M, K] / wq [N, K] e4m3fn bytes, xs [M, K/32] /
+    ws [N, K/32] scale bytes (what mxfp8_quantize returns), bias fp16 [N] -> fp16 [M, N], or the rows of a given ``out`` (stride out.stride(0))."""
+    for name, t in (("xq", xq), ("xs", xs), ("wq", wq), ("ws", ws)):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.is_contiguous()):
+            raise ValueError(f"linear_mxfp8: {name} must be a contiguous uint8 CUDA/HIP matrix, got {t.dtype} {t.device} {tuple(t.shape)}")
+    M, K = xq.shape
+    N = wq.shape[0]
+    if wq.shape[1] != K or tuple(xs.shape) != (M, K // 32) or tuple(ws.shape) != (N, K // 32):
+        raise ValueError(f"linear_mxfp8: xq {tuple(xq.shape)} xs {tuple(xs.shape)} wq {tuple(wq.shape)} ws {tuple(ws.shape)} do not fit together")
+    if bias is not None:
+        _f16(bias, "bias")
+    if out is None:
+        out = torch.empty(M, N, device=xq.device, dtype=torch.float16)
+    elif not (out.is_cuda and out.dtype == torch.float16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N):
+        raise ValueError(f"linear_mxfp8: out must be fp16 CUDA/HIP rows [>= {M}, >= {N}] with contiguous columns")
+    check(load().univst_linear_mxfp8(ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(bias), ptr(out), out.stride(0), M, N, K, stream_ptr()), "linear_mxfp8")
     return out
 
 
@@ -638,15 +680,49 @@ class Sd3AttnParams(dict):
                     for i, n in enumerate(names):
                         t[n] = fused[i * rows:(i + 1) * rows]
         self.update(t)
+        self._mx = None
+
+    def _fused_rows(self, first):
+        """the [3C, Cin] tensor the three views first | k | v are slices of, or None when they are not consecutive"""
+        q = self.get(first)
+        if q is None:
+            return None
+        k, v = self.get(first.replace("q", "k")), self.get(first.replace("q", "v"))
+        step = q.numel() * q.element_size()
+        if k is None or v is None or k.data_ptr() - q.data_ptr() != step or v.data_ptr() - k.data_ptr() != step:
+            return None
+        return torch.as_strided(q, (3 * q.shape[0], q.shape[1]), (q.shape[1], 1))
+
+    def mx(self):
+        """the MX-fp8 copies of the fused q | k | v weights (``univst_sd3_mx_weights``), quantised on first use and kept with this object: a rebuild of
+        the fp16 tensors is a new Sd3AttnParams, and so a new quantisation.  -> dict(qkv, qkv_scale[, add_qkv, add_qkv_scale]) of uint8 tensors."""
+        if self._mx is None:
+            w = self._fused_rows("to_q")
+            if w is None:
+                raise RuntimeError("Sd3AttnParams.mx: MX-fp8 q | k | v needs to_q / to_k / to_v of one shape (the fused [3C, Cin] layout)")
+            if w.shape[1] % 128:
+                raise RuntimeError(f"Sd3AttnParams.mx: MX-fp8 q | k | v needs an input width that is a multiple of 128, got {w.shape[1]}")
+            mx = {}
+            mx["qkv"], mx["qkv_scale"] = mxfp8_quantize(w)
+            a = self._fused_rows("add_q")
+            if a is not None:
+                mx["add_qkv"], mx["add_qkv_scale"] = mxfp8_quantize(a)
+            self._mx = mx
+        return self._mx
 
 
-def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False, idx=-1, eta1=0.0, eta2=0.6, rms_eps=1e-6, fuse=None, comm=None):
+def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False, idx=-1, eta1=0.0, eta2=0.6, rms_eps=1e-6, fuse=None, comm=None,
+                        qkv_dtype="fp16"):
     """CrossFrameProcessor / AttentionShiftProcessor of the reference's SD3 plugin on the native kernels.  params: the state dict
     of diffusers' Attention module (to_q.weight, ..., to_add_out.bias; missing entries = absent).  hidden [B, N, Cin],
     enc [B, Nt, Cin] or None -> (img [B, N, Cin], txt [B, Nt, Cin]) or img alone.  clip_length 0: no cross-frame keys.
     fuse (optional): dict(res_img, gate_img[, res_txt, gate_txt]) — the block's gated residuals computed in the out-projections'
     epilogue: the returned tensors are then res + gate[:, None] * attention output.
-    comm (optional): pointer of a connected univst_comm — the batch is this rank's clip_length frames of every branch (frame shard)."""
+    comm (optional): pointer of a connected univst_comm — the batch is this rank's clip_length frames of every branch (frame shard).
+    qkv_dtype: "fp16", or "mxfp8" for the two q | k | v projections on the block-scaled fp8 MFMA (univst_sd3_joint_attention_mx; params' quantised
+    weights are made on first use; input width a multiple of 128, no frame shard)."""
+    if qkv_dtype not in ("fp16", "mxfp8"):
+        raise ValueError(f"sd3_joint_attention: qkv_dtype must be 'fp16' or 'mxfp8', got {qkv_dtype!r}")
     _f16(hidden)
     B, N, Cin = hidden.shape
     keep = params if isinstance(params, Sd3AttnParams) else Sd3AttnParams(params, hidden.device)
@@ -667,9 +743,14 @@ def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False,
     # pnp_utils.py:183-186 in Python double, like the reference: in fp32 eta1 = 0.3 gives 0.3f * 50 = 15.000001 and idx 15 drops out
     active = bool(shift) and idx >= eta1 * 50 and idx <= eta2 * 50
     beta = ((0.9 - 0.1) / (eta1 * 50 - eta2 * 50) * (idx - eta2 * 50) + 0.1) if active else 0.0
-    check(load().univst_sd3_joint_attention(C.byref(w), ptr(hidden), ptr(enc), B, N, Nt, Cin, heads, inner // heads, clip_length, int(active),
-                                            float(beta), rms_eps, ptr(out_i), ptr(out_t), C.byref(gr) if gr is not None else None,
-                                            comm, stream_ptr()), "sd3_joint_attention")
+    args = (C.byref(w), ptr(hidden), ptr(enc), B, N, Nt, Cin, heads, inner // heads, clip_length, int(active), float(beta), rms_eps, ptr(out_i),
+            ptr(out_t), C.byref(gr) if gr is not None else None, comm, stream_ptr())
+    if qkv_dtype == "mxfp8":
+        m = keep.mx()
+        mx = Sd3MxWeights(ptr(m["qkv"]), ptr(m["qkv_scale"]), ptr(m.get("add_qkv")), ptr(m.get("add_qkv_scale")))
+        check(load().univst_sd3_joint_attention_mx(*args, C.byref(mx)), "sd3_joint_attention_mx")
+    else:
+        check(load().univst_sd3_joint_attention(*args), "sd3_joint_attention")
     return (out_i, out_t) if enc is not None else out_i
 
 
@@ -869,7 +950,7 @@ def delay_us(us: float):
 
 PROFILE_CLASSES = ("gemm_big_kernel<0>", "gemm_big_kernel<1>", "gemm_kernel<*,0>", "gemm_kernel<*,1>", "attn_pp40_kernel<true>",
                    "attn_kernel_occ3<96,5,2>", "attn_kernel<other>", "groupnorm", "layernorm", "adain_shift", "attn_kernel<text>",
-                   "conv_patch_kernel", "attn2_fused_kernel")
+                   "conv_patch_kernel", "attn2_fused_kernel", "linear_mxfp8_kernel")
 
 
 def profile_enable(on: bool):

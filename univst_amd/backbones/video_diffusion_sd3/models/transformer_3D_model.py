@@ -67,6 +67,7 @@ class Attention(nn.Module):
             if qk_norm == "rms_norm":
                 self.norm_added_q, self.norm_added_k = RMSNorm(dim_head, 1e-6), RMSNorm(dim_head, 1e-6)
         self.processor = processor
+        self.qkv_dtype = "fp16"          # "mxfp8": the q | k | v projections on the block-scaled fp8 MFMA (CustomSD3Transformer2DModel.set_qkv_dtype)
 
     def set_processor(self, processor):
         self.processor = processor
@@ -267,6 +268,34 @@ class CustomSD3Transformer2DModel(nn.Module):
                                   use_dual_attention=(i in self.config.dual_attention_layers)) for i in range(num_layers)])
         self.norm_out = _AdaNorm(dim, 2)
         self.proj_out = nn.Linear(dim, patch_size * patch_size * out_channels)
+        self.qkv_dtype = "fp16"
+        if os.environ.get("UNIVST_SD3_QKV"):                         # e.g. UNIVST_SD3_QKV=mxfp8 python bench.py --workload sd3_transfer
+            self.set_qkv_dtype(os.environ["UNIVST_SD3_QKV"])
+
+    # ------------------------------------------------------------------ BASELINE config 5: "MFMA fp8 QKV"
+    def _attentions(self):
+        return [a for blk in self.transformer_blocks for a in (blk.attn, blk.attn2) if a is not None]
+
+    def set_qkv_dtype(self, qkv_dtype):
+        """"fp16" (the default) or "mxfp8": the q | k | v projections of every joint attention (image and text stream, attn and attn2) in OCP MX-fp8 —
+        e4m3 elements, one power-of-two scale per 32 inputs, weights quantised once, activations per call (include/univst.h
+        univst_sd3_joint_attention_mx).  Everything else of the model stays fp16.  There is no silent fallback: a width the block-scaled MFMA does
+        not take, or a frame shard, raises here."""
+        if qkv_dtype not in ("fp16", "mxfp8"):
+            raise ValueError(f"set_qkv_dtype: expected 'fp16' or 'mxfp8', got {qkv_dtype!r}")
+        if qkv_dtype == "mxfp8":
+            if self.inner_dim % 128:
+                raise ValueError(f"set_qkv_dtype('mxfp8'): the inner dim {self.inner_dim} is not a multiple of 128 (one scaled MFMA spans four 32-element "
+                                 "MX blocks)")
+            for a in self._attentions():
+                shard = getattr(a, "_uv_frame_shard", None)
+                if shard is not None and shard.world > 1:
+                    raise RuntimeError(f"set_qkv_dtype('mxfp8'): this MM-DiT is frame-sharded (world {shard.world}); MX-fp8 q | k | v under a frame shard "
+                                       "is not built (the receiver-side projection of the halo rows is fp16 only)")
+        for a in self._attentions():
+            a.qkv_dtype = qkv_dtype
+        self.qkv_dtype = qkv_dtype
+        return self
 
     @property
     def dtype(self):

@@ -40,8 +40,12 @@ def _run(attn, hidden_states, encoder_hidden_states, shift, idx, eta1, eta2, cli
         if clip_length == 0:
             raise RuntimeError("a frame-sharded MM-DiT needs the cross-frame processors (CrossFrameProcessor / AttentionShiftProcessor)")
         clip_length, comm = shard.local, shard.comm.ptr
+    qkv_dtype = getattr(attn, "qkv_dtype", "fp16")            # CustomSD3Transformer2DModel.set_qkv_dtype
+    if qkv_dtype == "mxfp8" and comm is not None:
+        raise RuntimeError(f"qkv_dtype 'mxfp8' under a frame shard (world {shard.world}) is not built: the receiver-side projection of the halo rows "
+                           "is fp16 only; use set_qkv_dtype('fp16') on a sharded MM-DiT")
     out = _native.sd3_joint_attention(_params(attn), hid, enc, attn.heads, clip_length=clip_length, shift=shift, idx=idx, eta1=eta1, eta2=eta2,
-                                      rms_eps=float(eps), fuse=fuse, comm=comm)
+                                      rms_eps=float(eps), fuse=fuse, comm=comm, qkv_dtype=qkv_dtype)
     if enc is None:
         return out.to(dt)
     return out[0].to(dt), out[1].to(dt)

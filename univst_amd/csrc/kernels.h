@@ -290,6 +290,10 @@ int uv_launch_latent_window_smooth(half_t* x0, const float* lflow, int C, int F,
 int uv_launch_delay_us(double us, hipStream_t s);
 int uv_launch_accumulate_u8(const uint8_t* f, float* acc, long n, hipStream_t s);
 int uv_launch_window_store(const float* acc, float weight, uint8_t* dst, long n, hipStream_t s);
+// ---- MX-fp8 (mxfp8.hip): e4m3fn bytes [rows][K] + E8M0 scale bytes [rows][K/32]; Y = deq(X) deq(W)^T + bias, fp16 out
+int uv_launch_mxfp8_quantize(const half_t* X, long ldx, long rows, int K, uint8_t* Q, uint8_t* S, hipStream_t s);
+int uv_launch_linear_mxfp8(const uint8_t* Xq, const uint8_t* Xs, const uint8_t* Wq, const uint8_t* Ws, const half_t* bias, half_t* Y, long ldy, long M,
+                           int N, int K, hipStream_t s);
 
 // ---- optional per-class HIP-event profiling (prof.hip)
 // one class per kernel SYMBOL that matters, so bench.py's average launch duration is comparable with the
@@ -308,7 +312,8 @@ enum {
     UV_CLS_ATTN_TEXT = 10,  // the 77-key text cross-attention launches (any head_dim): reported apart from the self-attention
     UV_CLS_CONV_PATCH = 11, // conv_patch_kernel<*>: 3x3 / stride-1 convs from an input patch kept in LDS
     UV_CLS_ATTN2_FUSED = 12, // attn2_fused_kernel: q projection + 77-key text attention + out projection + residual in one launch
-    UV_NCLS = 13
+    UV_CLS_MXFP8 = 13,      // linear_mxfp8_kernel<*> (mxfp8.hip); the quantise pass in front of it is not bracketed
+    UV_NCLS = 14
 };
 void uv_prof_enable(int on);
 bool uv_prof_on();

@@ -453,9 +453,10 @@ int univst_sd3_adain_shift(void* qkv, int64_t ld, int F, int N, int C, int heads
     return UV_OK;
 }
 
-int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin, int heads,
-                               int head_dim, int clip_length, int shift, float beta, float rms_eps, void* out_img,
-                               void* out_txt, const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream) {
+// the body of both entries: mx == NULL is univst_sd3_joint_attention, launch for launch; with mx the two q | k | v projections run in MX-fp8
+static int sd3_joint_attention_body(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin, int heads,
+                                    int head_dim, int clip_length, int shift, float beta, float rms_eps, void* out_img, void* out_txt,
+                                    const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream, const univst_sd3_mx_weights* mx) {
     hipStream_t s = (hipStream_t)stream;
     UV_REQUIRE(w && hidden && out_img && B >= 1 && N >= 1 && heads >= 1, "sd3_joint_attention: null / empty argument");
     UV_REQUIRE(w->to_q && w->to_k && w->to_v && w->to_out, "sd3_joint_attention: to_q / to_k / to_v / to_out weights are required");
@@ -469,6 +470,26 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
     UV_REQUIRE(Cin % 8 == 0 && C % 8 == 0, "sd3_joint_attention: widths must be multiples of 8");
     const int world = comm ? uv_comm_world(comm) : 1, rank = comm ? uv_comm_rank(comm) : 0;
     const bool sharded = world > 1;
+    auto fused3 = [&](const void* q, const void* k, const void* v, const void* qb, const void* kb, const void* vb) {
+        const half_t *q_ = (const half_t*)q, *k_ = (const half_t*)k, *v_ = (const half_t*)v;
+        const bool wf = k_ == q_ + (long)C * Cin && v_ == k_ + (long)C * Cin;
+        const bool bf = (!qb && !kb && !vb) || (qb && (const half_t*)kb == (const half_t*)qb + C && (const half_t*)vb == (const half_t*)kb + C);
+        return wf && bf;
+    };
+    if (mx) {
+        UV_REQUIRE(mx->qkv && mx->qkv_scale && (!enc || (mx->add_qkv && mx->add_qkv_scale)),
+                   "sd3_joint_attention_mx: the quantised q | k | v weights and their scales are required for every projected stream");
+        UV_REQUIRE(Cin % 128 == 0, "sd3_joint_attention_mx: Cin=%d must be a multiple of 128 (one scaled MFMA spans four 32-element MX blocks)", Cin);
+        UV_REQUIRE(fused3(w->to_q, w->to_k, w->to_v, w->to_q_bias, w->to_k_bias, w->to_v_bias) &&
+                       (!enc || fused3(w->add_q, w->add_k, w->add_v, w->add_q_bias, w->add_k_bias, w->add_v_bias)),
+                   "sd3_joint_attention_mx: the q | k | v weights (and biases) must be consecutive in memory, the fused [3C, Cin] layout the quantised "
+                   "weights were made from");
+        if (sharded) {
+            uv_set_error("sd3_joint_attention_mx: MX-fp8 q | k | v under a frame shard (world = %d) is not built: the receiver-side projection of "
+                         "the halo rows is out of scope", world);
+            return UV_ERR_UNSUPPORTED;
+        }
+    }
     UV_REQUIRE(!sharded || clip_length >= 1, "sd3_joint_attention: a frame shard needs the cross-frame processors (clip_length = frames per rank)");
     const int nbr = clip_length ? B / clip_length : 0;                 // branches (clips) in the batch
     const long rows_i = (long)B * N, rows_t = enc ? (long)B * Nt : 0;
@@ -481,7 +502,11 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
     char* ws = nullptr;
     const bool two_phase = sharded && rank > 0;              // round 6: the keys this rank holds first, the halo frames continue from the softmax state
     const size_t n_state = two_phase ? (size_t)(rows_i + rows_t) * heads * 2 : 0;
-    const size_t bytes = n_half * sizeof(half_t) + (n_stat + n_state) * sizeof(float) + (size_t)B * 8 * sizeof(int) + 1024;      // src_idx[3B] x_idx[B] cnt[B] logw[3B]
+    // mx: e4m3 bytes [rows][Cin] + scale bytes [rows][Cin/32] of the image rows, then of the text rows, behind the index tables
+    auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };       // every part starts 256-byte aligned (rows * Cin / 32 alone is only a multiple of 4)
+    const size_t n_mx = mx ? up256((size_t)rows_i * Cin) + up256((size_t)rows_i * (Cin / 32)) + up256((size_t)rows_t * Cin) +
+                                 up256((size_t)rows_t * (Cin / 32)) + 256 : 0;
+    const size_t bytes = n_half * sizeof(half_t) + (n_stat + n_state) * sizeof(float) + (size_t)B * 8 * sizeof(int) + 1024 + n_mx;      // src_idx[3B] x_idx[B] cnt[B] logw[3B]
     UV_HIP(hipMallocAsync((void**)&ws, bytes, s));
     half_t* qkv_i = (half_t*)ws;
     half_t* qkv_t = qkv_i + (rows_i + rows_x) * 3 * C;
@@ -491,6 +516,10 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
     float* state_i = st + n_stat;
     float* state_t = state_i + (two_phase ? (size_t)rows_i * heads * 2 : 0);
     int* tab = (int*)(st + n_stat + n_state);
+    uint8_t* mq_i = (uint8_t*)(((uintptr_t)(tab + (size_t)B * 8) + 255) & ~(uintptr_t)255);
+    uint8_t* ms_i = mq_i + up256((size_t)rows_i * Cin);
+    uint8_t* mq_t = ms_i + up256((size_t)rows_i * (Cin / 32));
+    uint8_t* ms_t = mq_t + up256((size_t)rows_t * Cin);
     auto H = [](const void* p) { return (const half_t*)p; };
     int rc = UV_OK;
     auto body = [&]() -> int {
@@ -498,12 +527,6 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
         // ONE q | k | v projection per stream when the three weight matrices (and biases) are consecutive in memory — the host mirror
         // keeps them so (univst_amd/_native.py: a [3C, Cin] copy per attention module): the activation rows are read once instead of three
         // times and the 256 x 320 tile runs 14.4 column tiles instead of 3 x 4.8 (round 4)
-        auto fused3 = [&](const void* q, const void* k, const void* v, const void* qb, const void* kb, const void* vb) {
-            const half_t *q_ = H(q), *k_ = H(k), *v_ = H(v);
-            const bool wf = k_ == q_ + (long)C * Cin && v_ == k_ + (long)C * Cin;
-            const bool bf = (!qb && !kb && !vb) || (qb && H(kb) == H(qb) + C && H(vb) == H(kb) + C);
-            return wf && bf;
-        };
         // ---- frame shard (round 6): the exchange in two packs of different kinds, both on the communicator's forked stream.
         //   previous frame (this rank's last frame of every branch -> rank + 1): its HIDDEN rows — this op's input, the adaLN-modulated tokens every
         //     projection reads — [branch][N][Cin], half a K | V pack, posted before anything else of the layer; the RECEIVER projects them to K | V,
@@ -538,7 +561,11 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
             if (rank < world - 1 || emu) UV_RUN(uv_comm_fork(comm, s, &xs));
             UV_RUN(uv_comm_kv_post_halo(comm, o_send, o_prev, bytes_h, xs));
         }
-        if (fused3(w->to_q, w->to_k, w->to_v, w->to_q_bias, w->to_k_bias, w->to_v_bias)) {
+        if (mx) {                 // quantise this op's input rows, then the block-scaled MFMA linear against the quantised fused weight
+            UV_RUN(uv_launch_mxfp8_quantize(x, Cin, rows_i, Cin, mq_i, ms_i, s));
+            UV_RUN(uv_launch_linear_mxfp8(mq_i, ms_i, (const uint8_t*)mx->qkv, (const uint8_t*)mx->qkv_scale, H(w->to_q_bias), qkv_i, 3 * C, rows_i, 3 * C,
+                                          Cin, s));
+        } else if (fused3(w->to_q, w->to_k, w->to_v, w->to_q_bias, w->to_k_bias, w->to_v_bias)) {
             UV_RUN(linear(x, Cin, rows_i, Cin, H(w->to_q), H(w->to_q_bias), 3 * C, qkv_i, 3 * C, s));
         } else {
             UV_RUN(linear(x, Cin, rows_i, Cin, H(w->to_q), H(w->to_q_bias), C, qkv_i, 3 * C, s));
@@ -569,7 +596,11 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
         }
         if (enc) {
             const half_t* e = H(enc);
-            if (fused3(w->add_q, w->add_k, w->add_v, w->add_q_bias, w->add_k_bias, w->add_v_bias)) {
+            if (mx) {
+                UV_RUN(uv_launch_mxfp8_quantize(e, Cin, rows_t, Cin, mq_t, ms_t, s));
+                UV_RUN(uv_launch_linear_mxfp8(mq_t, ms_t, (const uint8_t*)mx->add_qkv, (const uint8_t*)mx->add_qkv_scale, H(w->add_q_bias), qkv_t, 3 * C,
+                                              rows_t, 3 * C, Cin, s));
+            } else if (fused3(w->add_q, w->add_k, w->add_v, w->add_q_bias, w->add_k_bias, w->add_v_bias)) {
                 UV_RUN(linear(e, Cin, rows_t, Cin, H(w->add_q), H(w->add_q_bias), 3 * C, qkv_t, 3 * C, s));
             } else {
                 UV_RUN(linear(e, Cin, rows_t, Cin, H(w->add_q), H(w->add_q_bias), C, qkv_t, 3 * C, s));
@@ -660,6 +691,20 @@ int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hid
     rc = body();
     (void)hipFreeAsync(ws, s);
     return rc;
+}
+
+int univst_sd3_joint_attention(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin, int heads,
+                               int head_dim, int clip_length, int shift, float beta, float rms_eps, void* out_img,
+                               void* out_txt, const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream) {
+    return sd3_joint_attention_body(w, hidden, enc, B, N, Nt, Cin, heads, head_dim, clip_length, shift, beta, rms_eps, out_img, out_txt, gr, comm, stream,
+                                    nullptr);
+}
+
+int univst_sd3_joint_attention_mx(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin, int heads,
+                                  int head_dim, int clip_length, int shift, float beta, float rms_eps, void* out_img, void* out_txt,
+                                  const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream, const univst_sd3_mx_weights* mx) {
+    return sd3_joint_attention_body(w, hidden, enc, B, N, Nt, Cin, heads, head_dim, clip_length, shift, beta, rms_eps, out_img, out_txt, gr, comm, stream,
+                                    mx);
 }
 
 }  // extern "C"

@@ -81,7 +81,7 @@ def _flow_match_scheduler():
     return FlowMatchEulerDiscreteScheduler
 
 
-def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
+def build_pipeline(pretrained_model_path, weight_dtype=torch.float16, qkv_dtype="fp16"):
     from transformers import CLIPTokenizer, T5TokenizerFast
     from ..sd._common import load_text_encoder
     from ...backbones.video_diffusion_sd3.pipelines.custom_pipeline import CustomStableDiffusion3Pipeline
@@ -90,6 +90,8 @@ def build_pipeline(pretrained_model_path, weight_dtype=torch.float16):
     sub = lambda cls, name: cls.from_pretrained(pretrained_model_path, subfolder=name)          # noqa: E731
     transformer = load_transformer(pretrained_model_path, weight_dtype)
     transformer.set_attn_processor({n: CrossFrameProcessor() for n in transformer.attn_processors})      # run_*_sd3.py:58-69
+    if getattr(transformer, "qkv_dtype", "fp16") != qkv_dtype:     # --qkv_dtype (an addition) decides here: it outranks UNIVST_SD3_QKV
+        transformer.set_qkv_dtype(qkv_dtype)
     clip = lambda name: load_text_encoder(pretrained_model_path, name, weight_dtype, projected=True).to(weight_dtype).cuda()      # noqa: E731
     return CustomStableDiffusion3Pipeline(
         tokenizer=sub(CLIPTokenizer, "tokenizer"), tokenizer_2=sub(CLIPTokenizer, "tokenizer_2"), tokenizer_3=sub(T5TokenizerFast, "tokenizer_3"),
@@ -103,4 +105,7 @@ def add_common_args(parser, weight_dtype=torch.float16):
     parser.add_argument("--weight_dtype", type=torch.dtype, default=weight_dtype)
     parser.add_argument("--time_steps", type=int, default=50)
     parser.add_argument("--seed", type=int, default=33)
+    # an addition to the reference's flags: the q | k | v projections of the MM-DiT in OCP MX-fp8 (CustomSD3Transformer2DModel.set_qkv_dtype)
+    # (in these scripts the flag, given or not, outranks the UNIVST_SD3_QKV environment switch)
+    parser.add_argument("--qkv_dtype", type=str, default="fp16", choices=("fp16", "mxfp8"))
     return parser

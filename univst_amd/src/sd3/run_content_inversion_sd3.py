@@ -12,7 +12,7 @@ from ..util import seed_everything
 def main(a):
     if a.seed is not None:
         seed_everything(a.seed)
-    pipe = build_pipeline(a.pretrained_model_path, a.weight_dtype)
+    pipe = build_pipeline(a.pretrained_model_path, a.weight_dtype, qkv_dtype=a.qkv_dtype)
     out = os.path.join(a.output_path, "sd3", a.content_path.split("/")[-1])
     paths = {k: os.path.join(out, k) for k in ("inversion", "reconstruction", "features")}
     for p in paths.values():

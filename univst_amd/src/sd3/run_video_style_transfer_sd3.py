@@ -16,7 +16,7 @@ def main(a):
     init_distributed()            # torchrun --nproc-per-node N: the pipeline shards the frames over the N GPUs; rank 0 writes the PNGs
     if a.seed is not None:
         seed_everything(a.seed)
-    pipe = build_pipeline(a.pretrained_model_path, a.weight_dtype)
+    pipe = build_pipeline(a.pretrained_model_path, a.weight_dtype, qkv_dtype=a.qkv_dtype)
     content_inv_noises = load_ddim_latents_at_t(a.time_steps, ddim_latents_path=a.content_inv_path).to(a.weight_dtype).cuda()
     content_inv_latents = load_ddim_latents_at_t(0, ddim_latents_path=a.content_inv_path).to(a.weight_dtype).cuda()
     style_inv_noises = load_ddim_latents_at_t(a.time_steps, ddim_latents_path=a.style_inv_path).to(a.weight_dtype).cuda()

@@ -500,6 +500,7 @@ int64_t univst_groupnorm_workspace_bytes(int64_t rows, int rows_per_stat, int gr
 int univst_groupnorm_nhwc(const void* X1, const void* X2, int C1, int C2, int64_t rows, int rows_per_stat, int groups,
                           float eps, const void* gamma, const void* beta, int silu, void* Y, void* workspace,
                           void* stream);
+/* LayerNorm with affine over the last dim of X [rows, C] (rows in 1 .. INT_MAX; C a multiple of 8 in 8 .. 2048) */
 int univst_layernorm(const void* X, void* Y, const void* gamma, const void* beta, int64_t rows, int C, float eps,
                      void* stream);
 /* multi-source flash attention.  q rows (bf*Nq+i) at ldq, k/v rows (src*Nkv+j) at ldkv, src_idx int32 [BF][nsrc].
@@ -592,12 +593,18 @@ int univst_sd3_joint_attention_mx(const univst_sd3_attn_weights* w, const void* 
  * ws: 4*F*2C + 2*F*2*heads floats. */
 int univst_sd3_adain_shift(void* qkv, int64_t ld, int F, int N, int C, int heads, float alpha, float beta, float gamma, void* ws,
                            void* stream);
-/* diffusers RMSNorm over the head dim, in place: x[r, h*d + e] *= rsqrt(mean_e x^2 + eps) * weight[e]  (row stride ld) */
+/* diffusers RMSNorm over the head dim, in place: x[r, h*d + e] *= rsqrt(mean_e x^2 + eps) * weight[e]  (row stride ld >= heads*d) */
 int univst_rmsnorm_heads(void* x, int64_t ld, int64_t rows, int heads, int head_dim, const void* weight, float eps, void* stream);
+/* the same on two column blocks of one row-strided buffer, as the joint attention runs it on a fused q | k | v row: the heads * head_dim
+ * columns at c0 with w0, times scale0 (the softmax scale folded into q), and those at c1 with w1.  The blocks are disjoint and inside ld;
+ * every other column is left as it is. */
+int univst_rmsnorm_heads_pair(void* x, int64_t ld, int64_t rows, int heads, int head_dim, int64_t c0, const void* w0, int64_t c1,
+                              const void* w1, float eps, float scale0, void* stream);
 /* y = LayerNorm(x; no affine, eps) * (1 + scale[b]) + shift[b]: AdaLayerNormZero / ZeroX / Continuous of the MM-DiT blocks (diffusers
  * normalization.py, third-party).  x, y [rows, C] (C % 8 == 0, <= 4096); scale / shift are rows of a [rows / rows_per_batch, ...]
  * matrix ld_mod halfs apart (chunks of the adaLN linear's output).  y2 / scale2 / shift2 (all NULL or all set): a second modulation
- * of the same normalised rows (AdaLayerNormZeroX, the dual-attention blocks of SD3.5-medium). */
+ * of the same normalised rows (AdaLayerNormZeroX, the dual-attention blocks of SD3.5-medium).  Every pointer of this entry, of
+ * univst_gate_residual and of univst_activation is 16-byte aligned (chunk views at multiples of C of a torch allocation are). */
 int univst_adaln_modulate(const void* x, void* y, const void* scale, const void* shift, int64_t ld_mod, int64_t rows, int64_t rows_per_batch,
                           int C, float eps, void* y2, const void* scale2, const void* shift2, void* stream);
 /* out = x + gate[b] * y: the gated residuals of diffusers' JointTransformerBlock (gate rows ld_gate halfs apart; out may alias x) */

@@ -175,6 +175,7 @@ SIGNATURES = {
                                            C.POINTER(Sd3GatedResidual), _P, _P, C.POINTER(Sd3MxWeights)]),
     "univst_sd3_adain_shift": (_I, [_P, _L, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
     "univst_rmsnorm_heads": (_I, [_P, _L, _L, _I, _I, _P, _F, _P]),
+    "univst_rmsnorm_heads_pair": (_I, [_P, _L, _L, _I, _I, _L, _P, _L, _P, _F, _F, _P]),
     "univst_linear_gated": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _I, _P]),
     "univst_adaln_modulate": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _F, _P, _P, _P, _P]),
     "univst_gate_residual": (_I, [_P, _P, _L, _P, _P, _L, _L, _I, _P]),
@@ -777,6 +778,16 @@ def rmsnorm_heads_(x, heads, weight, eps=1e-6):
     _f16(x)
     rows, Cc = x.shape
     check(load().univst_rmsnorm_heads(ptr(x), x.stride(0), rows, heads, Cc // heads, ptr(weight), eps, stream_ptr()), "rmsnorm_heads")
+    return x
+
+
+def rmsnorm_heads_pair_(x, heads, head_dim, c0, w0, c1, w1, eps=1e-6, scale0=1.0):
+    """in place on the column blocks [c0, c0 + heads*d) (weight w0, times scale0) and [c1, c1 + heads*d) (weight w1) of x [rows, ld] fp16:
+    the q | k normalisation of a fused q | k | v buffer."""
+    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1):
+        raise ValueError("rmsnorm_heads_pair_: x must be an fp16 CUDA/HIP [rows, ld] tensor or row view with a unit column stride")
+    check(load().univst_rmsnorm_heads_pair(ptr(x), x.stride(0), x.shape[0], heads, head_dim, c0, ptr(w0), c1, ptr(w1), eps, scale0, stream_ptr()),
+          "rmsnorm_heads_pair")
     return x
 
 

@@ -1,4 +1,5 @@
 // extern "C" surface of libunivst_hip.so (include/univst.h).  Thin argument checking + dispatch.
+#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -666,6 +667,7 @@ int univst_groupnorm_nhwc(const void* X1, const void* X2, int C1, int C2, int64_
 }
 int univst_layernorm(const void* X, void* Y, const void* gamma, const void* beta, int64_t rows, int C, float eps, void* s) {
     UV_REQUIRE(X && Y && gamma && beta, "layernorm: null argument");
+    UV_REQUIRE(rows >= 1 && rows <= INT_MAX && C >= 8, "layernorm: rows=%ld must be in 1 .. INT_MAX and C=%d at least 8", (long)rows, C);
     return uv_launch_layernorm(H(X), C, HM(Y), C, H(gamma), H(beta), rows, C, eps, S(s));
 }
 int univst_attention(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* out, int64_t ldo,

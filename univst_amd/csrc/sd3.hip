@@ -354,13 +354,31 @@ int linear(const half_t* X, long ldx, long M, int K, const half_t* W, const half
     return uv_launch_gemm(g, 0, s);
 }
 
+// the 16-byte loads / stores of the vector kernels (a null pointer passes: optional operands)
+template <class... P>
+bool aligned16(const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int univst_rmsnorm_heads(void* x, int64_t ld, int64_t rows, int heads, int d, const void* weight, float eps, void* stream) {
     UV_REQUIRE(x && weight && rows >= 1 && heads >= 1 && d >= 1 && d <= 256, "rmsnorm_heads: bad argument (head_dim <= 256)");
+    UV_REQUIRE(ld >= (int64_t)heads * d, "rmsnorm_heads: ld=%ld is below heads * head_dim = %ld", (long)ld, (long)heads * d);
     return launch_rms_pair((half_t*)x, ld, rows, heads, d, 0, (const half_t*)weight, 0, nullptr, eps, (hipStream_t)stream);
+}
+
+// the q | k pass of the joint attention as an operator: block c0 with w0 and scale0, block c1 with w1, one launch where the head width allows
+int univst_rmsnorm_heads_pair(void* x, int64_t ld, int64_t rows, int heads, int d, int64_t c0, const void* w0, int64_t c1, const void* w1,
+                              float eps, float scale0, void* stream) {
+    UV_REQUIRE(x && w0 && w1 && rows >= 1 && heads >= 1 && d >= 1 && d <= 256, "rmsnorm_heads_pair: bad argument (head_dim <= 256)");
+    const int64_t C = (int64_t)heads * d;
+    UV_REQUIRE(c0 >= 0 && c1 >= 0 && (c0 + C <= c1 || c1 + C <= c0) && c0 + C <= ld && c1 + C <= ld,
+               "rmsnorm_heads_pair: column blocks c0=%ld, c1=%ld of heads * head_dim = %ld must be disjoint and inside ld=%ld", (long)c0, (long)c1,
+               (long)C, (long)ld);
+    return launch_rms_pair((half_t*)x, ld, rows, heads, d, c0, (const half_t*)w0, c1, (const half_t*)w1, eps, (hipStream_t)stream, scale0);
 }
 
 int univst_adaln_modulate(const void* x, void* y, const void* scale, const void* shift, int64_t ld_mod, int64_t rows, int64_t rows_per_batch,
@@ -368,6 +386,7 @@ int univst_adaln_modulate(const void* x, void* y, const void* scale, const void*
     UV_REQUIRE(x && y && scale && shift && rows >= 1 && rows_per_batch >= 1 && C >= 8 && C % 8 == 0 && C <= 4096 && ld_mod % 8 == 0 && ld_mod >= C,
                "adaln_modulate: bad argument (C=%d must be a multiple of 8, <= 4096; ld_mod=%ld)", C, (long)ld_mod);
     UV_REQUIRE(!y2 || (scale2 && shift2), "adaln_modulate: y2 needs scale2 and shift2");
+    UV_REQUIRE(aligned16(x, y, scale, shift, y2, scale2, shift2), "adaln_modulate: every pointer must be 16-byte aligned");
     hipLaunchKernelGGL(adaln_modulate_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const half_t*)x, (half_t*)y,
                        (const half_t*)scale, (const half_t*)shift, (long)ld_mod, (long)rows, (long)rows_per_batch, C, eps, (half_t*)y2,
                        (const half_t*)scale2, (const half_t*)shift2);
@@ -378,6 +397,7 @@ int univst_adaln_modulate(const void* x, void* y, const void* scale, const void*
 int univst_gate_residual(const void* x, const void* gate, int64_t ld_gate, const void* y, void* out, int64_t rows, int64_t rows_per_batch, int C,
                          void* stream) {
     UV_REQUIRE(x && gate && y && out && rows >= 1 && rows_per_batch >= 1 && C >= 8 && C % 8 == 0 && ld_gate % 8 == 0, "gate_residual: bad argument");
+    UV_REQUIRE(aligned16(x, gate, y, out), "gate_residual: every pointer must be 16-byte aligned");
     const long n = rows * (C / 8);
     hipLaunchKernelGGL(gate_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const half_t*)x,
                        (const half_t*)gate, (long)ld_gate, (const half_t*)y, (half_t*)out, (long)rows, (long)rows_per_batch, C);
@@ -387,6 +407,7 @@ int univst_gate_residual(const void* x, const void* gate, int64_t ld_gate, const
 
 int univst_activation(const void* x, void* out, int64_t n, int act, void* stream) {
     UV_REQUIRE(x && out && n >= 8 && n % 8 == 0 && (act == UNIVST_ACT_SILU || act == UNIVST_ACT_GELU_TANH), "activation: bad argument");
+    UV_REQUIRE(aligned16(x, out), "activation: x and out must be 16-byte aligned");
     const long n8 = n / 8;
     if (act == UNIVST_ACT_SILU)
         hipLaunchKernelGGL(act_kernel<0>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const half_t*)x, (half_t*)out, n8);

@@ -127,7 +127,10 @@ int univst_comm_allreduce_f32(univst_comm* c, void* buf, int n, void* stream);
 int univst_comm_status(univst_comm* c);
 int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm);
 
-/* tuning switches of a handle (not part of the reference's surface; tests use them for A/B runs).
+/* tuning switches of a handle (not part of the reference's surface; tests use them for A/B runs).  The library keeps ONE table of them (abi.hip: name,
+ * environment seed, accepted range): univst_unet_create seeds a new handle from the environment — a seed is clamped into the range, never refused;
+ * UNIVST_CHAIN_BANDS alone has no upper clamp — univst_unet_set_option refuses a value outside the range with UV_ERR_ARG and leaves the option as it
+ * was (the 0 / 1 switches gn_producer, gn_fold and kv_overlap take any int as != 0), and univst_unet_query("<option name>") reads the current value back.
  *   "ln_fold" (default 2 since round 4, env UNIVST_LN_FOLD): fold the transformer blocks' LayerNorms (attention.py:311,321,329) into the
  *             linears around them instead of launching them separately: 0 none, 1 norm1 + norm2, 2 also norm3 (-> GEGLU).
  *   "gn_producer" (default 1, env UNIVST_GN_PRODUCER): GroupNorm statistics (resnet.py:338,369, attention.py:121) are taken from the epilogue
@@ -159,8 +162,9 @@ int univst_unet_set_comm_native(univst_unet* h, univst_comm* comm);
 int univst_unet_set_option(univst_unet* h, const char* name, int value);
 /* read-outs of a handle.  Every *_query below answers "arena_high_water" (bytes), "arena_bytes" (the size of the activation slab: it changes only when
  * a reserve / forward had to replace it by a larger one) and "weight_bytes" (loaded tensors plus the copies finalize derives; a UNet's own store, without
- * its motion modules').  This one adds "emu_wire_us" (modelled wire time issued since the last query; reading resets it) and "motion_active" (handles of
- * univst_unet_create_animatediff: the number of motion modules finalize found with a non-zero proj_out). */
+ * its motion modules').  This one adds "emu_wire_us" (modelled wire time issued since the last query; reading resets it), "motion_active" (handles of
+ * univst_unet_create_animatediff: the number of motion modules finalize found with a non-zero proj_out) and the name of every option above (its
+ * current value; "motion_fold" on the handles that have it). */
 int univst_unet_query(univst_unet* h, const char* name, double* out);
 
 /* ------------------------------------------------------------------ temporal VAE handle

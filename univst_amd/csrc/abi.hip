@@ -59,6 +59,35 @@ static bool model_query(const Model& m, const char* name, double* out) {
     return true;
 }
 
+// The tuning switches of a UNet handle (include/univst.h), ONE row per option: univst_unet_create seeds the handle from `env`, univst_unet_set_option
+// accepts [lo, hi] (lo > hi: a boolean, any int, stored as != 0) and refuses the rest with "<name> is <what>", univst_unet_query reads the value back.
+// A seed is never refused: a boolean one is != 0, the others are clamped to [lo, seed_hi] — or (SEED_PRE) pick 2 / 1 as a boolean.  The defaults are unet.h's.
+enum { SEED_PRE = -1 };
+struct UNetOption {
+    const char *name, *env;      // env: null = no seed
+    int UNet::*member;
+    int lo, hi;
+    const char* what;
+    int seed_hi;
+};
+static const UNetOption kUNetOptions[] = {
+    {"ln_fold", "UNIVST_LN_FOLD", &UNet::ln_fold, 0, 2, "0, 1 or 2", 2},
+    {"gn_fold", "UNIVST_GN_FOLD", &UNet::gn_fold, 1, 0, nullptr, 0},
+    {"kcat_fold", "UNIVST_KCAT_FOLD", &UNet::kcat_fold, 0, 3, "0, 1 (proj_out), 2 (conv_shortcut) or 3 (both)", 3},
+    {"attn2_fused", "UNIVST_ATTN2_PRE", &UNet::attn2_fused, 0, 2, "0, 1 or 2", SEED_PRE},
+    {"gn_producer", "UNIVST_GN_PRODUCER", &UNet::gn_producer, 1, 0, nullptr, 0},
+    {"chain_bands", "UNIVST_CHAIN_BANDS", &UNet::chain_bands, 0, 64, "0 (auto), 1 (off) or a band count <= 64", INT_MAX},      // (the seed has no upper clamp)
+    {"kv_overlap", "UNIVST_KV_OVERLAP", &UNet::kv_overlap, 1, 0, nullptr, 0},
+    {"emu_wire_gbps", nullptr, &UNet::emu_wire_gbps, 0, 10000, "a per-link rate in GB/s (0: off)", 0},
+    {"emu_wire_lat_us", nullptr, &UNet::emu_wire_lat_us, 0, 100000, "a latency in microseconds", 0},
+    {"motion_fold", nullptr, &UNet::motion_fold, 0, 1, "0 or 1", 0},      // (handles of univst_unet_create_animatediff only; 1 is not built)
+};
+static const UNetOption* unet_option(const char* name) {
+    for (const UNetOption& o : kUNetOptions)
+        if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
 extern "C" {
 
 const char* univst_last_error(void) { return g_err; }
@@ -85,13 +114,11 @@ int univst_unet_create(const univst_unet_cfg* cfg, univst_unet** out) {
     univst_unet* h = new (std::nothrow) univst_unet();
     UV_REQUIRE(h, "unet_create: out of host memory");
     h->impl.cfg = *cfg;
-    if (const char* e = getenv("UNIVST_LN_FOLD")) h->impl.ln_fold = atoi(e) < 0 ? 0 : (atoi(e) > 2 ? 2 : atoi(e));
-    if (const char* e = getenv("UNIVST_KCAT_FOLD")) h->impl.kcat_fold = atoi(e) < 0 ? 0 : (atoi(e) > 3 ? 3 : atoi(e));
-    if (const char* e = getenv("UNIVST_GN_PRODUCER")) h->impl.gn_producer = atoi(e) != 0;
-    if (const char* e = getenv("UNIVST_GN_FOLD")) h->impl.gn_fold = atoi(e) != 0;
-    if (const char* e = getenv("UNIVST_ATTN2_PRE")) h->impl.attn2_fused = atoi(e) ? 2 : 1;
-    if (const char* e = getenv("UNIVST_CHAIN_BANDS")) h->impl.chain_bands = atoi(e) < 0 ? 0 : atoi(e);
-    if (const char* e = getenv("UNIVST_KV_OVERLAP")) h->impl.kv_overlap = atoi(e) != 0;
+    for (const UNetOption& o : kUNetOptions)
+        if (const char* e = o.env ? getenv(o.env) : nullptr) {
+            const int v = atoi(e);
+            h->impl.*o.member = o.lo > o.hi ? v != 0 : o.seed_hi == SEED_PRE ? (v ? 2 : 1) : v < o.lo ? o.lo : v > o.seed_hi ? o.seed_hi : v;
+        }
     *out = h;
     return UV_OK;
 }
@@ -148,60 +175,20 @@ int univst_unet_create_animatediff(const univst_unet_cfg* cfg, const univst_anim
 }
 int univst_unet_set_option(univst_unet* h, const char* name, int value) {
     UV_REQUIRE(h && name, "unet_set_option: null argument");
-    if (!strcmp(name, "motion_fold")) {
-        UV_REQUIRE(h->impl.animatediff, "unet_set_option: motion_fold belongs to a handle of univst_unet_create_animatediff");
-        UV_REQUIRE(value == 0 || value == 1, "unet_set_option: motion_fold is 0 or 1");
-        if (value == 1) {
-            uv_set_error("unet_set_option: motion_fold = 1 (the motion modules' norms folded into their GEMMs) is not built; the chain runs unfolded (0)");
-            return UV_ERR_UNSUPPORTED;
-        }
-        h->impl.motion_fold = 0;
-        return UV_OK;
+    const UNetOption* o = unet_option(name);
+    if (!o) {
+        uv_set_error("unet_set_option: unknown option '%s'", name);
+        return UV_ERR_ARG;
     }
-    if (!strcmp(name, "ln_fold")) {
-        UV_REQUIRE(value >= 0 && value <= 2, "unet_set_option: ln_fold is 0, 1 or 2");
-        h->impl.ln_fold = value;
-        return UV_OK;
+    const bool mf = o->member == &UNet::motion_fold;
+    UV_REQUIRE(!mf || h->impl.animatediff, "unet_set_option: motion_fold belongs to a handle of univst_unet_create_animatediff");
+    UV_REQUIRE(o->lo > o->hi || (value >= o->lo && value <= o->hi), "unet_set_option: %s is %s", name, o->what);
+    if (mf && value == 1) {
+        uv_set_error("unet_set_option: motion_fold = 1 (the motion modules' norms folded into their GEMMs) is not built; the chain runs unfolded (0)");
+        return UV_ERR_UNSUPPORTED;
     }
-    if (!strcmp(name, "gn_fold")) {
-        h->impl.gn_fold = value != 0;
-        return UV_OK;
-    }
-    if (!strcmp(name, "kcat_fold")) {
-        UV_REQUIRE(value >= 0 && value <= 3, "unet_set_option: kcat_fold is 0, 1 (proj_out), 2 (conv_shortcut) or 3 (both)");
-        h->impl.kcat_fold = value;
-        return UV_OK;
-    }
-    if (!strcmp(name, "attn2_fused")) {
-        UV_REQUIRE(value >= 0 && value <= 2, "unet_set_option: attn2_fused is 0, 1 or 2");
-        h->impl.attn2_fused = value;
-        return UV_OK;
-    }
-    if (!strcmp(name, "gn_producer")) {
-        h->impl.gn_producer = value != 0;
-        return UV_OK;
-    }
-    if (!strcmp(name, "chain_bands")) {
-        UV_REQUIRE(value >= 0 && value <= 64, "unet_set_option: chain_bands is 0 (auto), 1 (off) or a band count <= 64");
-        h->impl.chain_bands = value;
-        return UV_OK;
-    }
-    if (!strcmp(name, "kv_overlap")) {
-        h->impl.kv_overlap = value != 0;
-        return UV_OK;
-    }
-    if (!strcmp(name, "emu_wire_gbps")) {
-        UV_REQUIRE(value >= 0 && value <= 10000, "unet_set_option: emu_wire_gbps is a per-link rate in GB/s (0: off)");
-        h->impl.emu_wire_gbps = value;
-        return UV_OK;
-    }
-    if (!strcmp(name, "emu_wire_lat_us")) {
-        UV_REQUIRE(value >= 0 && value <= 100000, "unet_set_option: emu_wire_lat_us is a latency in microseconds");
-        h->impl.emu_wire_lat_us = value;
-        return UV_OK;
-    }
-    uv_set_error("unet_set_option: unknown option '%s'", name);
-    return UV_ERR_ARG;
+    h->impl.*o->member = o->lo > o->hi ? value != 0 : value;
+    return UV_OK;
 }
 int univst_unet_query(univst_unet* h, const char* name, double* out) {
     UV_REQUIRE(h && name && out, "unet_query: null argument");
@@ -215,6 +202,11 @@ int univst_unet_query(univst_unet* h, const char* name, double* out) {
         *out = (double)h->impl.motion_active.size();
         return UV_OK;
     }
+    if (const UNetOption* o = unet_option(name))      // an option's current value (motion_fold: on the handles that have it)
+        if (o->member != &UNet::motion_fold || h->impl.animatediff) {
+            *out = (double)(h->impl.*o->member);
+            return UV_OK;
+        }
     uv_set_error("unet_query: unknown quantity '%s'", name);
     return UV_ERR_ARG;
 }

@@ -284,17 +284,8 @@ int Clip::finalize(hipStream_t s) {
         UV_SHAPED(vb, p + "self_attn.v_proj.bias", C);
         // fused q|k|v projection [3C, C] + [3C]; the attention scale d^-0.5 = 1/8 rides on the q rows (a power of two: exact in fp16 short of
         // underflow), which leaves the kernel the factor log2(e) only
-        half_t *fw, *fb;
-        UV_RUN(derive(p + "self_attn#qkv_w", {3L * C, C}, &fw));
-        UV_RUN(derive(p + "self_attn#qkv_b", {3L * C}, &fb));
-        UV_RUN(uv_launch_scale_f16(qw, fw, (long)C * C, 0.125f, s));
-        UV_RUN(uv_launch_scale_f16(qb, fb, C, 0.125f, s));
-        UV_HIP(hipMemcpyAsync(fw + (long)C * C, kw, (size_t)C * C * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fw + 2L * C * C, vw, (size_t)C * C * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fb + C, kb, (size_t)C * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fb + 2 * C, vb, (size_t)C * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-        L.qkv_w = fw;
-        L.qkv_b = fb;
+        UV_RUN(derive_concat(p + "self_attn#qkv_w", {qw, kw, vw}, C, C, s, 0.125f, &L.qkv_w));
+        UV_RUN(derive_concat(p + "self_attn#qkv_b", {qb, kb, vb}, C, 0, s, 0.125f, &L.qkv_b));
         layers.push_back(L);
     }
     UV_HIP(hipStreamSynchronize(s));

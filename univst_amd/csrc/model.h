@@ -53,6 +53,10 @@ struct WeightStore {
     void clear_missing() { missing.clear(); }
     int missing_error(const char* who) const;
     int derive(const std::string& k, std::vector<long> shape, half_t** out);      // replaces a derived tensor of that key
+    // derives `k` as the row-wise concatenation of equally shaped blocks [rows, cols] (cols = 0: vectors of `rows` elements: biases), the FIRST one
+    // multiplied by `scale0` unless that is 1 (an attention scale riding on the q rows): the fused q|k|v, k|v and wi_0|wi_1 operands of the handles
+    int derive_concat(const std::string& k, std::initializer_list<const half_t*> blocks, long rows, long cols, hipStream_t s, float scale0 = 1.f,
+                      const half_t** out = nullptr);
     void clear_derived();
 };
 
@@ -91,6 +95,9 @@ struct Model : WeightStore {
 int uv_derive_conv_layouts(WeightStore& st, const std::string& key, hipStream_t s);
 // out[i] = fp16(in[i] * f)
 int uv_launch_scale_f16(const half_t* in, half_t* out, long n, float f, hipStream_t s);
+// GEGLU row interleave of the `geglu = 1` epilogue (16 value rows, then their 16 gate rows): out row (32q + j) = in row (16q + j), out row
+// (32q + 16 + j) = in row (rows / 2 + 16q + j); rows a multiple of 32
+int uv_launch_geglu_interleave(const half_t* in, half_t* out, int rows, int cols, hipStream_t s);
 // [Wp W2 | Wp] and Wp (b2 + tb) + bp: two chained linears with a residual in between as ONE linear over K2 + C columns (include/univst.h univst_linear_compose)
 int uv_launch_linear_compose(const half_t* Wp, const half_t* W2, const half_t* b2, const half_t* tb, const half_t* bp, int C, int K2, half_t* W_out,
                              half_t* bias_out, hipStream_t s);

@@ -28,6 +28,14 @@ __global__ void scale_f16_kernel(const half_t* __restrict__ in, half_t* __restri
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (half_t)((float)in[i] * f);
 }
+__global__ void geglu_interleave_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int rows, int cols) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)rows * cols) return;
+    int c = (int)(i % cols), r = (int)(i / cols);
+    int q = r / 32, j = r % 32;
+    int src = j < 16 ? 16 * q + j : rows / 2 + 16 * q + (j - 16);
+    out[i] = in[(long)src * cols + c];
+}
 
 // Two chained linears composed into one (uv_launch_linear_compose): out[n][k] = sum_j Wp[n][j] W2[j][k] for k < K2, Wp[n][k - K2] for the C columns behind
 // them, and (column K2 + C of the grid) the bias Wp (b2 + tb) + bp.  fp32 accumulation in j order, one fp16 rounding.  Runs once per handle: plain FMAs,
@@ -174,6 +182,21 @@ int WeightStore::derive(const std::string& k, std::vector<long> shape, half_t** 
     return UV_OK;
 }
 
+int WeightStore::derive_concat(const std::string& k, std::initializer_list<const half_t*> blocks, long rows, long cols, hipStream_t s, float scale0,
+                               const half_t** out) {
+    const long nblk = (long)blocks.size(), n = rows * (cols ? cols : 1);
+    half_t* d;
+    UV_RUN(cols ? derive(k, {nblk * rows, cols}, &d) : derive(k, {nblk * rows}, &d));
+    long i = 0;
+    for (const half_t* src : blocks) {
+        if (i == 0 && scale0 != 1.f) UV_RUN(uv_launch_scale_f16(src, d, n, scale0, s));
+        else UV_HIP(hipMemcpyAsync(d + i * n, src, (size_t)n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+        ++i;
+    }
+    if (out) *out = d;
+    return UV_OK;
+}
+
 void WeightStore::clear_derived() {
     for (auto& kv : derived) (void)hipFree(kv.second.ptr);
     derived.clear();
@@ -250,6 +273,12 @@ int uv_derive_conv_layouts(WeightStore& st, const std::string& key, hipStream_t 
 
 int uv_launch_scale_f16(const half_t* in, half_t* out, long n, float f, hipStream_t s) {
     hipLaunchKernelGGL(scale_f16_kernel, dim3(nb(n)), dim3(256), 0, s, in, out, n, f);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+
+int uv_launch_geglu_interleave(const half_t* in, half_t* out, int rows, int cols, hipStream_t s) {
+    hipLaunchKernelGGL(geglu_interleave_kernel, dim3(nb((long)rows * cols)), dim3(256), 0, s, in, out, rows, cols);
     UV_LAUNCH_CHECK();
     return UV_OK;
 }

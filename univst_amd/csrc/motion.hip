@@ -150,15 +150,6 @@ __global__ __launch_bounds__(ta_waves(D, KT) * 64) void temporal_attn_kernel(con
     }
 }
 
-// GEGLU row interleave of the `geglu = 1` epilogue: out row (32q + j) = in row (16q + j), out row (32q + 16 + j) = in row (rows / 2 + 16q + j)
-__global__ __launch_bounds__(256) void motion_geglu_rows_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int rows, int cols) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)rows * cols) return;
-    const int c = (int)(i % cols), r = (int)(i / cols), q = r / 32, j = r % 32;
-    const int src = j < 16 ? 16 * q + j : rows / 2 + 16 * q + (j - 16);
-    out[i] = in[(long)src * cols + c];
-}
-
 template <int D, int KT>
 void ta_launch(const half_t* qkv, long ldx, const half_t* pe, int B, int F, int N, int heads, half_t* out, long ldo, hipStream_t s) {
     constexpr int WAVES = ta_waves(D, KT);
@@ -251,12 +242,7 @@ int Motion::finalize(hipStream_t s) {
             UV_SHAPED(kw, a + "to_k.weight", C, C);
             UV_SHAPED(vw, a + "to_v.weight", C, C);
             // fused q|k|v projection [3C, C]; the score scale d^-0.5 rides on the q rows, which leaves the kernel the factor log2(e) only
-            half_t* fw;
-            UV_RUN(derive(a + "#qkv_w", {3 * C, C}, &fw));
-            UV_RUN(uv_launch_scale_f16(qw, fw, C * C, 1.f / sqrtf((float)d), s));
-            UV_HIP(hipMemcpyAsync(fw + C * C, kw, (size_t)(C * C) * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-            UV_HIP(hipMemcpyAsync(fw + 2 * C * C, vw, (size_t)(C * C) * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-            A.qkv_w = fw;
+            UV_RUN(derive_concat(a + "#qkv_w", {qw, kw, vw}, C, C, s, 1.f / sqrtf((float)d), &A.qkv_w));
             A.pe_qkv = nullptr;
             if (cfg.position_encoding) {
                 // the table: a checkpoint's pos_encoder.pe [1, max_len, C] when it was loaded, else the formula; then pe_qkv[f] = Wqkv pe[f]
@@ -270,7 +256,7 @@ int Motion::finalize(hipStream_t s) {
                 }
                 half_t* pq;
                 UV_RUN(derive(a + "#pe_qkv", {L, 3 * C}, &pq));
-                UV_RUN(uv_launch_gemm(lin_params(pe, L, (int)C, fw, (int)(3 * C), pq), 0, s));
+                UV_RUN(uv_launch_gemm(lin_params(pe, L, (int)C, A.qkv_w, (int)(3 * C), pq), 0, s));
                 A.pe_qkv = pq;
             }
             Bk.attn.push_back(A);
@@ -286,9 +272,8 @@ int Motion::finalize(hipStream_t s) {
         half_t *gw, *gb;
         UV_RUN(derive(p + "ff.net.0.proj.weight#geglu", {8 * C, C}, &gw));
         UV_RUN(derive(p + "ff.net.0.proj.bias#geglu", {8 * C}, &gb));
-        hipLaunchKernelGGL(motion_geglu_rows_kernel, dim3(nb(8 * C * C)), dim3(256), 0, s, w1, gw, (int)(8 * C), (int)C);
-        hipLaunchKernelGGL(motion_geglu_rows_kernel, dim3(nb(8 * C)), dim3(256), 0, s, b1, gb, (int)(8 * C), 1);
-        UV_LAUNCH_CHECK();
+        UV_RUN(uv_launch_geglu_interleave(w1, gw, (int)(8 * C), (int)C, s));
+        UV_RUN(uv_launch_geglu_interleave(b1, gb, (int)(8 * C), 1, s));
         Bk.ff1_w = gw;
         Bk.ff1_b = gb;
         blocks.push_back(Bk);

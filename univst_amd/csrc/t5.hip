@@ -279,17 +279,8 @@ int T5::finalize(hipStream_t s) {
         UV_SHAPED(w1, p + "1.DenseReluDense.wi_1.weight", F, C);
         UV_SHAPED(L.wo_w, p + "1.DenseReluDense.wo.weight", C, F);
         // fused q|k|v [3 I, C] and wi_0|wi_1 [2 F, C]: one projection each (T5 has no attention scale to fold)
-        half_t *fq, *fi;
-        UV_RUN(derive(p + "0.SelfAttention#qkv_w", {3L * I, C}, &fq));
-        UV_RUN(derive(p + "1.DenseReluDense#wi_w", {2L * F, C}, &fi));
-        const size_t qb = (size_t)I * C * sizeof(half_t), fb = (size_t)F * C * sizeof(half_t);
-        UV_HIP(hipMemcpyAsync(fq, qw, qb, hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fq + (long)I * C, kw, qb, hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fq + 2L * I * C, vw, qb, hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fi, w0, fb, hipMemcpyDeviceToDevice, s));
-        UV_HIP(hipMemcpyAsync(fi + (long)F * C, w1, fb, hipMemcpyDeviceToDevice, s));
-        L.qkv_w = fq;
-        L.wi_w = fi;
+        UV_RUN(derive_concat(p + "0.SelfAttention#qkv_w", {qw, kw, vw}, I, C, s, 1.f, &L.qkv_w));
+        UV_RUN(derive_concat(p + "1.DenseReluDense#wi_w", {w0, w1}, F, C, s, 1.f, &L.wi_w));
         layers.push_back(L);
     }
     UV_HIP(hipStreamSynchronize(s));      // the uploads queued on s are in place

@@ -13,12 +13,13 @@ struct UNet : Model {
     std::unordered_map<long, int*> idx_tables;
     std::unordered_map<std::string, long> temb_off;    // resnet prefix -> column offset in the fused time_emb_proj (finalize)
     long temb_total = 0;
-    int gn_producer = 1;      // GroupNorm statistics from the producing conv / linear's epilogue where the tile geometry allows (UNIVST_GN_PRODUCER=0: always the stand-alone pass)
-    int chain_bands = 1;      // post-attention chain of a transformer block in row bands: 1 off (default: measured +0.4 ms per step in the graph), 0 auto (bands of >= 65536 rows), n > 1 forced (UNIVST_CHAIN_BANDS)
+    // The tuning switches: the DEFAULTS live here, names / environment seeds / accepted ranges in the option table of abi.hip (kUNetOptions)
+    int gn_producer = 1;      // GroupNorm statistics from the producing conv / linear's epilogue where the tile geometry allows (0: always the stand-alone pass)
+    int chain_bands = 1;      // post-attention chain of a transformer block in row bands: 1 off (default: measured +0.4 ms per step in the graph), 0 auto (bands of >= 65536 rows), n > 1 forced
     int gn_fold = 1;          // the transformer blocks' per-frame GroupNorm folded into proj_in where the weight copies are cheap (round 5; 0: the apply pass)
     int attn2_fused = 2;      // the text cross-attention of a block as one launch where fused.hip serves the shape (round 5): 2 = with the self-attention's out projection in front, 1 = attn2 alone, 0 = q projection + attention + out projection
-    int ln_fold = 2;          // transformer-block LayerNorms folded into the neighbouring linears: 0 none, 1 norm1 + norm2, 2 also norm3 (default since round 4; UNIVST_LN_FOLD)
-    int kcat_fold = 3;        // bit 0: proj_out as extra K columns of ff.net.2 — one K = 5C GEMM over the channel concat [mid | h3] with the composed weight "proj_out#kcat" (finalize) instead of two launches; bit 1: reserved for conv_shortcut as a tail of conv2, NOT BUILT (the graph launches the shortcut separately whatever the bit says) (UNIVST_KCAT_FOLD)
+    int ln_fold = 2;          // transformer-block LayerNorms folded into the neighbouring linears: 0 none, 1 norm1 + norm2, 2 also norm3 (default since round 4)
+    int kcat_fold = 3;        // bit 0: proj_out as extra K columns of ff.net.2 — one K = 5C GEMM over the channel concat [mid | h3] with the composed weight "proj_out#kcat" (finalize) instead of two launches; bit 1: reserved for conv_shortcut as a tail of conv2, NOT BUILT (the graph launches the shortcut separately whatever the bit says)
     // AnimateDiff UNet3D (univst_unet_create_animatediff): the per-frame 2-D graph with a motion module behind every resnet / transformer pair.
     // The modules keep their own weight stores (keys below "<block>.motion_modules.<j>."); their chains run on THIS handle's arena and split-K workspace.
     bool animatediff = false;

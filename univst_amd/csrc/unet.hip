@@ -38,15 +38,6 @@ __global__ void permute_conv_weight_t32_kernel(const half_t* __restrict__ in, ha
     int o = (int)(i / ((long)Ci * 9));
     out[i] = in[((long)o * Ci + q * 32 + j) * 9 + t];
 }
-// GEGLU row interleave: out row (32q + j) = in row (16q + j), out row (32q+16+j) = in row (half + 16q + j)
-__global__ void geglu_interleave_kernel(const half_t* __restrict__ in, half_t* __restrict__ out, int rows, int cols) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)rows * cols) return;
-    int c = (int)(i % cols), r = (int)(i / cols);
-    int q = r / 32, j = r % 32;
-    int src = j < 16 ? 16 * q + j : rows / 2 + 16 * q + (j - 16);
-    out[i] = in[(long)src * cols + c];
-}
 
 // LayerNorm folded into the following linear (GemmParams::ln_stats): W'[n][k] = fp16(gamma[k] * W[n][k]), wsum[n] = sum_k W'[n][k]
 // (of the ROUNDED values: it has to cancel mean * sum_k W' exactly), lnb[n] = bias[n] + sum_k beta[k] * W[n][k].  One wave per row.
@@ -278,19 +269,12 @@ int UNet::finalize(hipStream_t s) {
             const WTensor *tk = find(p + "to_k.weight"), *tv = find(p + "to_v.weight");
             UV_REQUIRE(tk && tv, "%s: to_k / to_v missing", p.c_str());
             long C = t.shape[0], K = t.shape[1];
-            half_t* d;
-            UV_RUN(derive(p + "qkv#fused", {3 * C, K}, &d));
-            UV_HIP(hipMemcpyAsync(d, t.ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-            UV_HIP(hipMemcpyAsync(d + C * K, tk->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-            UV_HIP(hipMemcpyAsync(d + 2 * C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
+            UV_RUN(derive_concat(p + "qkv#fused", {t.ptr, tk->ptr, tv->ptr}, C, K, s));
             const int hd = (int)C / cfg.attention_heads[level_of(k)];
-            if (hd == 40 || hd == 64 || hd == 80 || hd == 160) {         // second copy whose Q rows carry log2(e)/sqrt(d) (AttnParams::q_prescaled): the software-
-                half_t* d2;                     // pipelined kernels (head_dim 40: SD-v1.5; 64: the SD-v2.1 layout) take the scale from the weights
-                UV_RUN(derive(p + "qkv#fused#qs", {3 * C, K}, &d2));
-                UV_RUN(uv_launch_scale_f16(t.ptr, d2, C * K, 1.4426950408889634f / sqrtf((float)hd), s));
-                UV_HIP(hipMemcpyAsync(d2 + C * K, tk->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-                UV_HIP(hipMemcpyAsync(d2 + 2 * C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-            }
+            // second copy whose Q rows carry log2(e)/sqrt(d) (AttnParams::q_prescaled): the software-pipelined kernels (head_dim 40: SD-v1.5; 64: the
+            // SD-v2.1 layout) take the scale from the weights
+            if (hd == 40 || hd == 64 || hd == 80 || hd == 160)
+                UV_RUN(derive_concat(p + "qkv#fused#qs", {t.ptr, tk->ptr, tv->ptr}, C, K, s, 1.4426950408889634f / sqrtf((float)hd)));
         } else if (ends(k, ".attn2.to_q.weight")) {
             const long C = t.shape[0], K = t.shape[1];
             const int hd = (int)C / cfg.attention_heads[level_of(k)];
@@ -303,17 +287,13 @@ int UNet::finalize(hipStream_t s) {
             std::string p = k.substr(0, k.size() - strlen("to_k.weight"));
             const WTensor* tv = find(p + "to_v.weight");
             UV_REQUIRE(tv, "%s: to_v missing", p.c_str());
-            long C = t.shape[0], K = t.shape[1];
-            half_t* d;
-            UV_RUN(derive(p + "kv#fused", {2 * C, K}, &d));
-            UV_HIP(hipMemcpyAsync(d, t.ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-            UV_HIP(hipMemcpyAsync(d + C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
+            UV_RUN(derive_concat(p + "kv#fused", {t.ptr, tv->ptr}, t.shape[0], t.shape[1], s));
         } else if (ends(k, ".ff.net.0.proj.weight") || ends(k, ".ff.net.0.proj.bias")) {
             int rows = (int)t.shape[0], cols = t.shape.size() > 1 ? (int)t.shape[1] : 1;
             UV_REQUIRE(rows % 32 == 0, "%s: GEGLU width %d must be a multiple of 32", k.c_str(), rows);
             half_t* d;
             UV_RUN(derive(k + "#geglu", {rows, cols}, &d));
-            hipLaunchKernelGGL(geglu_interleave_kernel, dim3(nb((long)rows * cols)), dim3(256), 0, s, t.ptr, d, rows, cols);
+            UV_RUN(uv_launch_geglu_interleave(t.ptr, d, rows, cols, s));
             // K = 320 (the 64x64 level): a second copy in the row order of the X-resident kernel (gemm.hip geglu_xres_kernel)
             int kdim = cols;
             if (!ends(k, ".weight")) {      // the bias: the reduction length is its weight's (a checkpoint that carries the bias without the weight is refused)
@@ -417,12 +397,7 @@ int UNet::finalize(hipStream_t s) {
                           *tv = find(pre + ".attn_temporal.to_v.weight");
             UV_REQUIRE(tq && tk && tv && find(pre + ".norm_temporal.weight") && find(pre + ".norm_temporal.bias") &&
                        find(pre + ".attn_temporal.to_out.0.bias"), "%s: attn_temporal / norm_temporal parameters incomplete", pre.c_str());
-            const long C = tq->shape[0], K = tq->shape[1];
-            half_t* d;
-            UV_RUN(derive(pre + ".attn_temporal.qkv#fused", {3 * C, K}, &d));
-            UV_HIP(hipMemcpyAsync(d, tq->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-            UV_HIP(hipMemcpyAsync(d + C * K, tk->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
-            UV_HIP(hipMemcpyAsync(d + 2 * C * K, tv->ptr, C * K * 2, hipMemcpyDeviceToDevice, s));
+            UV_RUN(derive_concat(pre + ".attn_temporal.qkv#fused", {tq->ptr, tk->ptr, tv->ptr}, tq->shape[0], tq->shape[1], s));
             temporal_attn_active[pre] = 1;
         }
     }
@@ -571,6 +546,49 @@ int UNet::reserve(int B, int F, int H, int Wd) {
 }
 
 // ------------------------------------------------------------------------------------------ forward
+// the optional arguments of Fwd::conv / Fwd::linear, set by name
+struct ConvOpt {
+    int stride = 1, up = 0;
+    const half_t* rowbias = nullptr;      // the time-embedding row bias, ldrb halfs apart (0: Cout)
+    long ldrb = 0;
+    const half_t* R = nullptr;            // residual [rows, Cout]
+    bool want_gst = false;                // let the epilogue leave the GroupNorm statistics of the output (Act::gst) for a following GroupNorm
+};
+struct LinOpt {
+    const half_t* R = nullptr;            // residual rows, ldr halfs apart
+    long ldr = 0;
+    const half_t* bias2 = nullptr;        // GemmParams::bias2
+    int geglu = 0;
+    float* stats_out = nullptr;           // emit the per-row (sum, sumsq) of Y for a following folded LayerNorm
+    const float* ln_in = nullptr;         // fold LayerNorm(X) (statistics in ln_in, K / 160 slots per row) into this linear: `wkey` names the "#ln" weight, whose bias comes with it
+    const float** gst_out = nullptr;      // where to leave the GroupNorm statistics of Y when the epilogue wrote them (else null)
+    // the weight in place of W(wkey) — with rows_per_set: per-frame weight sets + fp32 bias (a GroupNorm folded into this linear: uv_launch_groupnorm's fold)
+    const half_t* wsets = nullptr;
+    const float* bias32 = nullptr;
+    int rows_per_set = 0;
+};
+// One spatial transformer block (attention.py:104-153 + :280-346, + pnp_utils.py:20-100 when pnp_layer) runs as a sequence of stages over this
+// context: the names, the shapes, the decisions `decide` takes once from shapes and options, and the buffers that live across stages.  The arena is
+// first-fit, so WHERE a stage takes and releases a buffer is part of the graph (the high-water mark depends on it): no scope-bound guards.
+struct Block {
+    std::string p, b;                  // "<block>.attentions.<j>" and its ".transformer_blocks.0"
+    const Act* x = nullptr;            // the block's input: proj_in reads it, proj_out adds it
+    int C = 0, d = 0, N = 0, heads = 0, nbands = 1;
+    long rows = 0;
+    float scale_log2e = 0.f, beta = 0.f;
+    bool gnf = false, fold = false, fold3 = false, qs = false, qs2 = false, registered = false, shift = false, kcat = false, a2pre = false,
+         a2fused = false, t_attn = false;
+    std::string wpi, wqkv, wq2, pkc;   // proj_in / attn1 q|k|v / attn2 to_q weights as the decisions picked them; the composed K = 5C operand
+    half_t *t0 = nullptr, *h = nullptr, *h2 = nullptr, *h3 = nullptr, *h4 = nullptr, *kv = nullptr, *q2 = nullptr, *mid = nullptr;
+    float* lnst = nullptr;             // [rows][C/160][2] fp32: row statistics for the folded LayerNorms
+    half_t *gm2 = nullptr, *bt2 = nullptr, *gm3 = nullptr, *bt3 = nullptr, *tb = nullptr;      // norm2 / norm3, the bias-only temporal attention
+};
+struct Band {      // one band of whole frames of the row-local chain (the whole tensor when nbands == 1)
+    int bd, imgs;
+    long rows, o;  // rows of the band; offset of its first row in a C-wide tensor (halfs)
+    float* lb;     // its rows of Block::lnst
+};
+
 struct Fwd {
     UNet& u;
     hipStream_t s;
@@ -612,6 +630,55 @@ struct Fwd {
     void free(void* p) { u.arena.release(p); }
     half_t* W(const std::string& k) { return u.W(k); }
 
+    // the K/V source tables of this (B, F) (layout: UNet::reserve) and the workspaces every forward holds from its start to its end
+    int workspaces(const int* tab, int H, int Wd) {
+        const long BF_ = (long)B * F;
+        idx_stock = tab; idx_pnp = tab + BF_ * 3; idx_text = tab + BF_ * 5;
+        cnt_stock = tab + BF_ * 6; cnt_pnp = tab + BF_ * 7;
+        lw_stock = (const float*)(tab + BF_ * 8); lw_pnp = (const float*)(tab + BF_ * 11);
+        if (u.world > 1 && u.rank > 0) {
+            idx2_stock = tab + BF_ * 13; idx2_pnp = tab + BF_ * 16;
+            cnt2_stock = tab + BF_ * 18; cnt2_pnp = tab + BF_ * 19;
+        }
+        gn_ws = (float*)u.arena.alloc((size_t)uv_groupnorm_workspace_floats(B * F, u.cfg.norm_num_groups) * sizeof(float));
+        ad_ws = (float*)u.arena.alloc((size_t)F * 2 * u.cfg.block_out_channels[3] * 2 * sizeof(float) + 1024);
+        sk_ws = (float*)u.arena.alloc(UV_SPLITK_WS_BYTES);
+        UV_REQUIRE(gn_ws && ad_ws && sk_ws, "forward: arena too small");
+        if (u.animatediff) {
+            idx_self = tab + BF_ * 13;
+            if (!u.motions.empty()) {       // (without modules the motion config is not validated and not used)
+                mgn_ws = (float*)u.arena.alloc((size_t)uv_groupnorm_workspace_floats(B * F, u.ad.motion.norm_groups) * sizeof(float) + 256);
+                UV_REQUIRE(mgn_ws, "forward: arena too small");
+            }
+        }
+        if (u.gn_producer) {           // statistics of up to 64 level-0-sized tensors: [rows/16][G][2] fp32 each (3 MB per tensor at 3 x 16 x 64 x 64: 201 MB, counted in
+                                       // reserve()); taken AFTER the mandatory workspaces, so it is the part that degrades first (consumers fall back to their own pass)
+            gst_left = (size_t)(((long)B * F * H * Wd + 15) / 16) * u.cfg.norm_num_groups * 2 * 64;
+            gst_pool = (float*)u.arena.alloc(gst_left * sizeof(float));
+            if (!gst_pool) gst_left = 0;
+        }
+        return UV_OK;
+    }
+    // time embedding (unet_3d_condition.py:359-365): emb, and every resnet's time_emb_proj of it in one launch (resnet.py:349-351)
+    int time_embedding(float timestep) {
+        const int C0 = u.cfg.block_out_channels[0], TED = 4 * C0;
+        half_t* tsin = alloc((long)B * C0);
+        half_t* e1 = alloc((long)B * TED);
+        emb = alloc((long)B * TED);
+        if (!tsin || !e1 || !emb) return UV_ERR_STATE;
+        UV_RUN(uv_launch_timestep_embed(timestep, tsin, B, C0, u.cfg.flip_sin_to_cos, u.cfg.freq_shift, s));
+        half_t *w1 = W("time_embedding.linear_1.weight"), *b1 = W("time_embedding.linear_1.bias");
+        half_t *w2 = W("time_embedding.linear_2.weight"), *b2 = W("time_embedding.linear_2.bias");
+        if (!w1 || !b1 || !w2 || !b2) return u.missing_error("unet");
+        UV_RUN(uv_launch_linear_small(tsin, w1, b1, e1, B, TED, C0, 0, s));
+        UV_RUN(uv_launch_linear_small(e1, w2, b2, emb, B, TED, TED, 1, s));
+        if (u.temb_total == 0) return UV_OK;
+        half_t *wa = W("time_emb_proj#all.weight"), *ba = W("time_emb_proj#all.bias");
+        temb_all = alloc((long)B * u.temb_total);
+        if (!wa || !ba || !temb_all) return u.missing_error("unet");
+        return uv_launch_linear_small(emb, wa, ba, temb_all, B, (int)u.temb_total, TED, 1, s);
+    }
+
     int groupnorm(const Act& a, const Act* b, int rows_per_stat, float eps, const std::string& p, int silu, half_t* out,
                   bool cross_frame = false, const UvGnFold* fold = nullptr) {
         UvGnComm gc;
@@ -629,156 +696,84 @@ struct Fwd {
                                    eps, gm, bt, silu, out, gn_ws, s, sharded ? &gc : nullptr,
                                    rows_per_stat % 16 == 0 ? a.gst : nullptr, b ? b->gst : nullptr, fold);
     }
-    // want_gst: let the epilogue leave the GroupNorm statistics of the output (Act::gst) for a following GroupNorm
-    int conv(const Act& a, const Act* b, const std::string& p, int Cout, int taps, int stride, int up, const half_t* rowbias,
-             const half_t* R, Act* out, long ldrb = 0, bool want_gst = false) {
+    // launches g on the split-K workspace of the graph.  gst: let the epilogue leave the GroupNorm statistics of Y there ([N/10][M/16][2], from the pool) —
+    // null when the pool is exhausted or the launch took a kernel that does not write them (the consumer then runs its own pass)
+    int gemm(GemmParams& g, int mode, const float** gst = nullptr) {
+        int emitted = 0;
+        if (gst) *gst = nullptr;
+        if (gst && (g.gn_out = gst_take(g.M, g.N))) {
+            g.gn_G = g.N / 10;           // sub-groups of 10 channels: every group width of the UNet (10 .. 80) is a multiple
+            g.gn_gw = 10;
+            g.gn_emitted = &emitted;
+        }
+        g.partial = sk_ws; g.partial_bytes = UV_SPLITK_WS_BYTES;
+        UV_RUN(uv_launch_gemm(g, mode, s));
+        if (g.gn_out && emitted) *gst = g.gn_out;
+        else if (g.gn_out) gst_give_back(g.M, g.N);
+        return UV_OK;
+    }
+    int conv(const Act& a, const Act* b, const std::string& p, int Cout, int taps, Act* out, const ConvOpt& o = ConvOpt()) {
         GemmParams g;
-        g.X = a.p;
-        g.X2 = b ? b->p : nullptr;
-        g.C1 = a.C;
-        g.C2 = b ? b->C : 0;
-        g.Hs = a.H;
-        g.Ws = a.W;
-        g.up = up;
-        g.stride = stride;
-        g.taps = taps;
-        const int He = a.H << up, We = a.W << up;
-        g.Ho = (taps == 9) ? (He + 2 - 3) / stride + 1 : He;
-        g.Wo = (taps == 9) ? (We + 2 - 3) / stride + 1 : We;
-        g.M = a.imgs * g.Ho * g.Wo;
-        g.N = Cout;
-        g.K = taps * (g.C1 + g.C2);
+        g.X = a.p; g.C1 = a.C; g.Hs = a.H; g.Ws = a.W;
+        g.X2 = b ? b->p : nullptr; g.C2 = b ? b->C : 0;
+        g.up = o.up; g.stride = o.stride; g.taps = taps;
+        const int He = a.H << o.up, We = a.W << o.up;
+        g.Ho = (taps == 9) ? (He + 2 - 3) / o.stride + 1 : He;
+        g.Wo = (taps == 9) ? (We + 2 - 3) / o.stride + 1 : We;
+        g.M = a.imgs * g.Ho * g.Wo; g.N = Cout; g.K = taps * (g.C1 + g.C2);
         g.korder = (taps == 9 && g.C1 % 64 == 0 && g.C2 % 64 == 0 && u.find(p + ".weight#ti")) ? 1 : 0;
         g.W = W(p + (g.korder ? ".weight#ti" : ".weight#nhwc"));
-        if (taps == 9 && stride == 1 && u.find(p + ".weight#t32")) g.W32 = W(p + ".weight#t32");
-        if (taps == 9 && stride == 1 && up == 1 && !b && u.find(p + ".weight#ph4")) g.W4 = W(p + ".weight#ph4");      // the plan takes it or keeps the 9-tap form
+        if (taps == 9 && o.stride == 1 && u.find(p + ".weight#t32")) g.W32 = W(p + ".weight#t32");
+        if (taps == 9 && o.stride == 1 && o.up == 1 && !b && u.find(p + ".weight#ph4")) g.W4 = W(p + ".weight#ph4");      // the plan takes it or keeps the 9-tap form
         g.bias = W(p + ".bias");
-        g.rowbias = rowbias;
-        g.ldrb = ldrb;
-        g.rows_per_rb = F * g.Ho * g.Wo;
-        g.R = R;
-        g.ldr = Cout;
-        out->imgs = a.imgs;
-        out->H = g.Ho;
-        out->W = g.Wo;
-        out->C = Cout;
-        out->p = alloc(out->rows() * Cout);
-        if (!out->p) return UV_ERR_STATE;
-        g.Y = out->p;
-        g.ldy = Cout;
+        g.rowbias = o.rowbias; g.ldrb = o.ldrb; g.rows_per_rb = F * g.Ho * g.Wo;
+        g.R = o.R; g.ldr = Cout;
+        out->imgs = a.imgs; out->H = g.Ho; out->W = g.Wo; out->C = Cout; out->gst = nullptr;
+        if (!(out->p = alloc(out->rows() * Cout))) return UV_ERR_STATE;
+        g.Y = out->p; g.ldy = Cout;
         if (!g.W || !g.bias) return u.missing_error("unet");
-        g.partial = sk_ws;
-        g.partial_bytes = UV_SPLITK_WS_BYTES;
-        out->gst = nullptr;
-        if (taps != 9 || !u.temporal_conv_active.count(p)) {
-            int emitted = 0;
-            if (want_gst && (g.gn_out = gst_take(out->rows(), Cout))) {
-                g.gn_G = Cout / 10;           // sub-groups of 10 channels: every group width of the UNet (10 .. 80) is a multiple
-                g.gn_gw = 10;
-                g.gn_emitted = &emitted;
-            }
-            UV_RUN(uv_launch_gemm(g, 1, s));
-            if (g.gn_out) {
-                if (emitted) out->gst = g.gn_out;
-                else gst_give_back(out->rows(), Cout);
-            }
-            return UV_OK;
-        }
+        if (taps != 9 || !u.temporal_conv_active.count(p)) return gemm(g, 1, o.want_gst ? &out->gst : nullptr);
         // TRAINED temporal conv (resnet.py:70-80): spatial conv (+ its bias) -> Conv1d over the frames of every pixel -> whatever the
         // caller wanted fused behind the PseudoConv3d (time-embedding row bias, residual).  The Conv1d runs as a 3x3 conv on the
         // geometry (image rows = frames, image columns = pixels) with zero side taps (embed_temporal_weight_kernel).
         half_t* mid = alloc(out->rows() * Cout);
         if (!mid) return UV_ERR_STATE;
-        g.Y = mid;
-        g.rowbias = nullptr;
-        g.R = nullptr;
-        UV_RUN(uv_launch_gemm(g, 1, s));
+        g.Y = mid; g.rowbias = nullptr; g.R = nullptr;
+        UV_RUN(gemm(g, 1));
         half_t *tw = W(p + ".conv_temporal.weight"), *tb = W(p + ".conv_temporal.bias");
         if (!tw || !tb) return u.missing_error("unet");
         const long HWo = (long)g.Ho * g.Wo;
         if (Cout % 8 != 0) {
-            UV_REQUIRE(!rowbias && !R, "%s: temporal conv on %d channels cannot carry a fused epilogue", p.c_str(), Cout);
+            UV_REQUIRE(!o.rowbias && !o.R, "%s: temporal conv on %d channels cannot carry a fused epilogue", p.c_str(), Cout);
             hipLaunchKernelGGL(temporal_conv_small_kernel, dim3(nb(out->rows() * Cout)), dim3(256), 0, s, mid, out->p, tw, tb, B, F, HWo, Cout);
             UV_LAUNCH_CHECK();
         } else {
             GemmParams t;
-            t.X = mid;
-            t.C1 = Cout;
-            t.Hs = F;
-            t.Ws = (int)HWo;
-            t.taps = 9;
-            t.Ho = F;
-            t.Wo = (int)HWo;
-            t.M = (int)out->rows();
-            t.N = Cout;
-            t.K = 9 * Cout;
-            t.W = W(p + ".conv_temporal.weight#t3x3");
-            t.bias = tb;
-            t.rowbias = rowbias;
-            t.ldrb = ldrb;
-            t.rows_per_rb = (int)(F * HWo);
-            t.R = R;
-            t.ldr = Cout;
-            t.Y = out->p;
-            t.ldy = Cout;
+            t.X = mid; t.C1 = Cout; t.Hs = t.Ho = F; t.Ws = t.Wo = (int)HWo; t.taps = 9;
+            t.M = (int)out->rows(); t.N = Cout; t.K = 9 * Cout;
+            t.W = W(p + ".conv_temporal.weight#t3x3"); t.bias = tb;
+            t.rowbias = o.rowbias; t.ldrb = o.ldrb; t.rows_per_rb = (int)(F * HWo);
+            t.R = o.R; t.ldr = Cout;
+            t.Y = out->p; t.ldy = Cout;
             if (!t.W) return u.missing_error("unet");
-            t.partial = sk_ws;
-            t.partial_bytes = UV_SPLITK_WS_BYTES;
-            UV_RUN(uv_launch_gemm(t, 1, s));
+            UV_RUN(gemm(t, 1));
         }
         free(mid);
         return UV_OK;
     }
-    // stats_out: emit the per-row (sum, sumsq) of Y for a following folded LayerNorm.  ln_in: fold LayerNorm(X) (statistics in ln_in,
-    // ln_slots = K / 160 slots per row) into this linear: `wkey` then names the derived "#ln" weight and the bias comes with it.
-    int linear(const half_t* X, long ldx, long M, int K, const std::string& wkey, const std::string& bkey, int N, half_t* Y,
-               long ldy, const half_t* R = nullptr, long ldr = 0, const half_t* bias2 = nullptr, int geglu = 0, float* stats_out = nullptr,
-               const float* ln_in = nullptr, const float** gst_out = nullptr, const half_t* wsets = nullptr, const float* bias32 = nullptr, int rows_per_set = 0) {
-        GemmParams g;
-        if (wsets) {                  // per-frame weight sets + fp32 bias (a GroupNorm folded into this linear: uv_launch_groupnorm's fold)
-            g.w_rows_per_set = rows_per_set;
-            g.bias32 = bias32;
+    int linear(const half_t* X, long ldx, long M, int K, const std::string& wkey, const std::string& bkey, int N, half_t* Y, long ldy,
+               const LinOpt& o = LinOpt()) {
+        const bool own_bias = !bkey.empty() && !o.ln_in && !o.wsets;
+        GemmParams g = lin_params(X, M, K, o.wsets ? o.wsets : W(wkey), N, Y, own_bias ? W(bkey) : nullptr, o.R, o.geglu);
+        g.ldx = ldx; g.ldy = ldy; g.ldr = o.ldr;      // (the graph's rows are not always contiguous: bands, the q|k|v rows, the GEGLU hidden tensor)
+        g.bias2 = o.bias2; g.stats_out = o.stats_out;
+        g.w_rows_per_set = o.wsets ? o.rows_per_set : 0; g.bias32 = o.wsets ? o.bias32 : nullptr;
+        if (o.ln_in) {
+            g.ln_stats = o.ln_in; g.ln_slots = K / 160; g.ln_eps = 1e-5f;
+            g.ln_wsum = (const float*)W(wkey + ".wsum"); g.ln_bias = (const float*)W(wkey + ".bias");
         }
-        int emitted = 0;
-        if (gst_out) {
-            *gst_out = nullptr;
-            if ((g.gn_out = gst_take(M, N))) {
-                g.gn_G = N / 10;
-                g.gn_gw = 10;
-                g.gn_emitted = &emitted;
-            }
-        }
-        g.stats_out = stats_out;
-        if (ln_in) {
-            g.ln_stats = ln_in;
-            g.ln_slots = K / 160;
-            g.ln_eps = 1e-5f;
-            g.ln_wsum = (const float*)W(wkey + ".wsum");
-            g.ln_bias = (const float*)W(wkey + ".bias");
-            if (!g.ln_wsum || !g.ln_bias) return u.missing_error("unet");
-        }
-        g.X = X;
-        g.ldx = ldx;
-        g.M = (int)M;
-        g.K = K;
-        g.N = N;
-        g.W = wsets ? wsets : W(wkey);
-        g.bias = (bkey.empty() || ln_in || wsets) ? nullptr : W(bkey);
-        g.Y = Y;
-        g.ldy = ldy;
-        g.R = R;
-        g.ldr = ldr;
-        g.bias2 = bias2;
-        g.geglu = geglu;
-        if (!g.W || (!bkey.empty() && !ln_in && !wsets && !g.bias)) return u.missing_error("unet");
-        g.partial = sk_ws;
-        g.partial_bytes = UV_SPLITK_WS_BYTES;
-        UV_RUN(uv_launch_gemm(g, 0, s));
-        if (g.gn_out) {
-            if (emitted) *gst_out = g.gn_out;
-            else gst_give_back(M, N);
-        }
-        return UV_OK;
+        if (!g.W || (own_bias && !g.bias) || (o.ln_in && (!g.ln_wsum || !g.ln_bias))) return u.missing_error("unet");
+        return gemm(g, 0, o.gst_out);
     }
 
     // frame shard (SURVEY §8e coupling 2): every frame attends to {prev, (cur), first}; the previous frame of this rank's first frame lives on
@@ -859,7 +854,9 @@ struct Fwd {
         auto to = u.temb_off.find(p);
         UV_REQUIRE(to != u.temb_off.end() && temb_all, "%s: time_emb_proj missing", p.c_str());
         Act n1a{n1, x.imgs, x.H, x.W, Cin}, h;
-        UV_RUN(conv(n1a, nullptr, p + ".conv1", Cout, 9, 1, 0, temb_all + to->second, nullptr, &h, u.temb_total, true));
+        ConvOpt c1;
+        c1.rowbias = temb_all + to->second; c1.ldrb = u.temb_total; c1.want_gst = true;
+        UV_RUN(conv(n1a, nullptr, p + ".conv1", Cout, 9, &h, c1));
         free(n1);
         half_t* n2 = alloc(h.rows() * Cout);
         if (!n2) return UV_ERR_STATE;
@@ -868,145 +865,58 @@ struct Fwd {
         const half_t* res = x.p;
         Act sc{};
         if (u.find(p + ".conv_shortcut.weight")) {
-            UV_RUN(conv(x, skip, p + ".conv_shortcut", Cout, 1, 1, 0, nullptr, nullptr, &sc));
+            UV_RUN(conv(x, skip, p + ".conv_shortcut", Cout, 1, &sc));
             res = sc.p;
         } else {
             UV_REQUIRE(!skip && x.C == Cout, "%s: no conv_shortcut but channel mismatch", p.c_str());
         }
         Act n2a{n2, x.imgs, x.H, x.W, Cout};
-        UV_RUN(conv(n2a, nullptr, p + ".conv2", Cout, 9, 1, 0, nullptr, res, out, 0, true));
+        ConvOpt c2;
+        c2.R = res; c2.want_gst = true;
+        UV_RUN(conv(n2a, nullptr, p + ".conv2", Cout, 9, out, c2));
         free(n2);
         if (sc.p) free(sc.p);
         return UV_OK;
     }
 
-    // attention.py:104-153 + :280-346 (+ pnp_utils.py:20-100 when pnp_layer)
-    int transformer(const std::string& p, const Act& x, bool pnp_layer, int heads, Act* out) {
-        const int C = x.C, d = C / heads, N = x.H * x.W;
-        const long rows = x.rows();
-        const std::string b = p + ".transformer_blocks.0";
-        half_t* t0 = alloc(rows * C);
-        if (!t0) return UV_ERR_STATE;
+    // Everything that is a predicate on shapes and options: no launch, no allocation
+    int decide(Block& k, bool pnp_layer) {
+        const Act& x = *k.x;
+        const int C = k.C, N = k.N, heads = k.heads;
+        const long rows = k.rows;
+        const std::string &p = k.p, &b = k.b;
+        k.scale_log2e = 1.4426950408889634f / sqrtf((float)k.d);
         // The block's per-frame GroupNorm (attention.py:121) folded into proj_in where that pays (round 5): per frame a weight set gamma * rstd (.) W and
         // an fp32 bias carrying the mean term, proj_in then reads the RAW tensor — the apply pass (read + write of the tensor) goes for B*F weight copies
         // (9.8 MB against 252 MB at the 64x64 level; at the 32x32 level the copies are a third of the pass: not taken)
-        const std::string wpi = p + (u.find(p + ".proj_in.weight#nhwc") ? ".proj_in.weight#nhwc" : ".proj_in.weight");
+        k.wpi = p + (u.find(p + ".proj_in.weight#nhwc") ? ".proj_in.weight#nhwc" : ".proj_in.weight");
         const long set_bytes = (long)x.imgs * C * C * 2, apply_bytes = rows * C * 4;
-        const bool gnf = u.gn_fold && uv_linear_takes_big_direct(rows, C, C) && (N % 256 == 0 || N % 192 == 0) && 8 * set_bytes <= apply_bytes;
-        half_t* wsets = nullptr;
-        float* b32 = nullptr;
-        if (gnf) {
-            wsets = alloc((long)x.imgs * C * C);
-            b32 = (float*)alloc((long)x.imgs * C * 2);
-            if (!wsets || !b32) return UV_ERR_STATE;
-            UvGnFold gf;
-            gf.W = W(wpi); gf.bias = W(p + ".proj_in.bias"); gf.N = C; gf.W_out = wsets; gf.bias32 = b32;
-            if (!gf.W || !gf.bias) return u.missing_error("unet");
-            UV_RUN(groupnorm(x, nullptr, N, 1e-6f, p + ".norm", 0, nullptr, false, &gf));
-        } else {
-            UV_RUN(groupnorm(x, nullptr, N, 1e-6f, p + ".norm", 0, t0));
-        }
-        half_t* h = alloc(rows * C);
-        if (!h) return UV_ERR_STATE;
+        k.gnf = u.gn_fold && uv_linear_takes_big_direct(rows, C, C) && (N % 256 == 0 || N % 192 == 0) && 8 * set_bytes <= apply_bytes;
         // The three LayerNorms of the block are folded into the linears around them when all of those take the direct 256x320 path
         // (levels with >= 150 tiles: the 64x64 .. 16x16 levels of an unsharded clip): the producing linear's epilogue leaves the row
         // statistics, the consuming one runs on the raw rows — no LayerNorm launch, no normalised copy in HBM.
         // norm3 -> GEGLU projection is folded only on request (ln_fold = 2): its epilogue is the longest of the block and the fold
         // costs it more than the LayerNorm launch it removes (tools/bench_ln_fold.py).
         // (round 4: also on the 128-wide kernel where that runs these linears without split-K — the 64x64 / 32x32 levels of a frame shard)
-        const bool fold = u.ln_fold > 0 && C % 160 == 0 && uv_linear_fold_producer_ok(rows, C, C) && uv_linear_fold_consumer_ok(rows, 3 * C, C, false) &&
-                          uv_linear_fold_consumer_ok(rows, C, C, false);
+        k.fold = u.ln_fold > 0 && C % 160 == 0 && uv_linear_fold_producer_ok(rows, C, C) && uv_linear_fold_consumer_ok(rows, 3 * C, C, false) &&
+                 uv_linear_fold_consumer_ok(rows, C, C, false);
         // norm3 is folded also with the statistics from a 128-wide producer (A/B: emulated rank of 8, F = 16: 12.83 ms per step
         // without the 128-wide fold, 12.81 with norm1 / norm2 only, 12.70 with all three)
         const bool xres3 = u.find(b + ".ff.net.0.proj.weight#xres") != nullptr && uv_geglu_xres_ok(8 * C, C, rows);
-        const bool fold3 = fold && u.ln_fold > 1 && (xres3 || uv_linear_fold_consumer_ok(rows, 8 * C, C, true));
-        float* lnst = fold ? (float*)alloc(rows * (C / 160) * 4) : nullptr;      // [rows][C/160][2] fp32
-        if (fold && !lnst) return UV_ERR_STATE;
-        UV_RUN(linear(gnf ? x.p : t0, C, rows, C, wpi, p + ".proj_in.bias", C, h, C, nullptr, 0, nullptr, 0, lnst, nullptr, nullptr, wsets, b32, N));
-        if (gnf) {
-            free(wsets);
-            free(b32);
-        }
-        // ---- attn1
-        half_t *gm, *bt;
-        gm = W(b + ".norm1.weight"); bt = W(b + ".norm1.bias");
-        if (!gm || !bt) return u.missing_error("unet");
-        if (!fold) UV_RUN(uv_launch_layernorm(h, C, t0, C, gm, bt, rows, C, 1e-5f, s));
-        const bool shard = u.world > 1, halo = shard && u.rank > 0;
-        if (shard) UV_RUN(kv_post(h, C, N));                  // the boundary frames' hidden rows leave now, on the forked stream
-        const long extra_rows = shard ? (long)2 * B * N : 0;     // the halo frames' q|k|v rows behind the local ones: [prev: B x N | first: B x N]
-        half_t* qkv = alloc((rows + extra_rows) * 3 * C);
-        if (!qkv) return UV_ERR_STATE;
-        const bool qs = u.find(b + ".attn1.qkv#fused#qs") != nullptr;      // head_dim 40: scale folded into to_q (finalize)
-        const std::string wqkv = b + (qs ? ".attn1.qkv#fused#qs" : ".attn1.qkv#fused");
-        if (fold) UV_RUN(linear(h, C, rows, C, wqkv + "#ln", "", 3 * C, qkv, 3 * C, nullptr, 0, nullptr, 0, nullptr, lnst));
-        else UV_RUN(linear(t0, C, rows, C, wqkv, "", 3 * C, qkv, 3 * C));
-        const bool registered = pnp_layer && pnp && pnp->registered;
+        k.fold3 = k.fold && u.ln_fold > 1 && (xres3 || uv_linear_fold_consumer_ok(rows, 8 * C, C, true));
+        k.qs = u.find(b + ".attn1.qkv#fused#qs") != nullptr;      // head_dim 40: scale folded into to_q (finalize)
+        k.wqkv = b + (k.qs ? ".attn1.qkv#fused#qs" : ".attn1.qkv#fused");
+        k.qs2 = u.find(b + ".attn2.to_q.weight#qs") != nullptr;
+        k.wq2 = b + (k.qs2 ? ".attn2.to_q.weight#qs" : ".attn2.to_q.weight");
+        k.registered = pnp_layer && pnp && pnp->registered;
         // AnimateDiff's closure (pnp_utils.py:45 of that backbone): eta1 * 50 <= idx < eta2 * 50, evaluated in double as Python does
-        const bool shift = registered && (u.animatediff ? (double)pnp->idx >= (double)pnp->eta1 * 50.0 && (double)pnp->idx < (double)pnp->eta2 * 50.0
-                                                        : pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f);
-        float beta = 0.f;
-        if (shift) {
+        k.shift = k.registered && (u.animatediff ? (double)pnp->idx >= (double)pnp->eta1 * 50.0 && (double)pnp->idx < (double)pnp->eta2 * 50.0
+                                                  : pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f);
+        if (k.shift) {
             UV_REQUIRE(B == 3, "PnP attention shift needs the three-branch batch (B=3), got B=%d", B);
-            beta = (0.9f - 0.1f) / (pnp->eta1 * 50.f - pnp->eta2 * 50.f) * ((float)pnp->idx - pnp->eta2 * 50.f) + 0.1f;
-            UV_RUN(uv_launch_adain_shift(qkv, 3 * C, F, N, C, ad_ws, ad_ws + (long)F * 2 * C, pnp->alpha, beta, pnp->gamma, s));
+            k.beta = (0.9f - 0.1f) / (pnp->eta1 * 50.f - pnp->eta2 * 50.f) * ((float)pnp->idx - pnp->eta2 * 50.f) + 0.1f;
         }
-        AttnParams ap;
-        ap.q = qkv; ap.k = qkv + C; ap.v = qkv + 2 * C;
-        ap.ldq = ap.ldkv = 3 * C;
-        ap.o = t0; ap.ldo = C;
-        ap.src_idx = registered ? idx_pnp : idx_stock;
-        ap.src_cnt = registered ? cnt_pnp : cnt_stock;
-        ap.src_logw = registered ? lw_pnp : lw_stock;
-        ap.nsrc = registered ? 2 : 3;
-        if (u.animatediff) {      // plain per-frame self-attention (attention.py:344: no video_length, no key frames), registered or not
-            ap.src_idx = idx_self;
-            ap.src_cnt = nullptr;
-            ap.src_logw = nullptr;
-            ap.nsrc = 1;
-        }
-        ap.BF = x.imgs; ap.Nq = N; ap.Nkv = N; ap.heads = heads; ap.d = d;
-        ap.scale_log2e = 1.4426950408889634f / sqrtf((float)d);
-        ap.q_prescaled = qs;
-        float* state = nullptr;
-        if (halo) {               // phase 1: the key frames this rank holds; (m, l) per query stays behind for phase 2
-            state = (float*)alloc((long)x.imgs * heads * N * 4);
-            if (!state) return UV_ERR_STATE;
-            ap.state_out = state;
-        }
-        UV_RUN(uv_launch_attention(ap, s));
-        if (shard) UV_RUN(kv_join());
-        if (halo) {
-            // the two halo frames: LayerNorm (norm1) of the received hidden rows -> to_k | to_v (all of q|k|v inside the window: the shift kernel works on
-            // the fused rows) -> the AdaIN shift of each frame -> phase 2 over them.  The sender would have computed the same K | V from the same fp16 rows
-            // (with the LayerNorm folded into the GEMM when `fold`: equal up to fp16 rounding of the normalised rows).
-            const long hrows = 2L * B * N;
-            half_t* tn = alloc(hrows * C);
-            if (!tn) return UV_ERR_STATE;
-            UV_RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_prev), C, tn, C, gm, bt, (long)B * N, C, 1e-5f, s));
-            UV_RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_rfirst), C, tn + (long)B * N * C, C, gm, bt, (long)B * N, C, 1e-5f, s));
-            half_t* qh = qkv + rows * 3 * C;
-            half_t* wfull = W(wqkv);
-            if (!wfull) return u.missing_error("unet");
-            if (shift) {
-                UV_RUN(linear(tn, C, hrows, C, wqkv, "", 3 * C, qh, 3 * C));
-                for (int sl = 0; sl < 2; ++sl)            // rows [slot][3 branches][N] = the shift kernel's [3][F = 1][N]
-                    UV_RUN(uv_launch_adain_shift(qh + (long)sl * B * N * 3 * C, 3 * C, 1, N, C, ad_ws, ad_ws + 2L * C, pnp->alpha, beta, pnp->gamma, s));
-            } else {
-                UV_RUN(linear(tn, C, hrows, C, wqkv, "", 2 * C, qh + C, 3 * C, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, wfull + (long)C * C));
-            }
-            free(tn);
-            ap.src_idx = registered ? idx2_pnp : idx2_stock;
-            ap.src_cnt = registered ? cnt2_pnp : cnt2_stock;
-            ap.src_logw = nullptr;
-            ap.state_out = nullptr;
-            ap.state_in = state;
-            UV_RUN(uv_launch_attention(ap, s));
-            ap.state_in = nullptr;
-            free(state);
-        }
-        free(qkv);
-        // ---- the row-local chain behind the self-attention: to_out + residual -> (norm2) -> attn2 -> to_out + residual -> (norm3) ->
+        // The row-local chain behind the self-attention: to_out + residual -> (norm2) -> attn2 -> to_out + residual -> (norm3) ->
         // GEGLU projection -> FF2 + residual.  Round 4: it runs BAND BY BAND over whole frames when the level is large (64x64 level of
         // an unsharded clip: 196 608 rows, every C-wide tensor 126 MB, the 4C-wide hidden one 503 MB): with bands of 65 536 rows (one
         // round of 256-row tiles on the 256 CUs) the band's intermediates (42 MB each, hidden 168 MB) are re-read by the next kernel of
@@ -1014,188 +924,323 @@ struct Fwd {
         // band-sized (tools/bench_mall_bands.py: -13 % on the four FF linears; every kernel is row-local: same results up to fp32 summation order).
         // OFF by default: inside the step (same box, alternating runs) the banded graph is 0.4 ms SLOWER (linears 16.7 -> 17.0 ms: three
         // one-round launches per kernel lose more to launch tails than the cache returns).  Kept as a switch (chain_bands).
-        const long N_rows = N;
-        int nbands = 1;
+        k.nbands = 1;
         if (u.chain_bands != 1) {
             const long target = 65536;
             int want = u.chain_bands > 1 ? u.chain_bands : (int)(rows / target);
             while (want > 1 && (x.imgs % want != 0 || (u.chain_bands <= 1 && rows / want < target))) --want;
-            nbands = want < 1 ? 1 : want;
+            k.nbands = want < 1 ? 1 : want;
             // the folded LayerNorms need the direct 256x320 path for the band's row count as well: a level too small for that stays unbanded
-            if (nbands > 1 && fold && !(uv_linear_takes_big_direct(rows / nbands, C, C) && (!fold3 || uv_linear_takes_big_direct(rows / nbands, 8 * C, C)))) nbands = 1;
+            if (k.nbands > 1 && k.fold &&
+                !(uv_linear_takes_big_direct(rows / k.nbands, C, C) && (!k.fold3 || uv_linear_takes_big_direct(rows / k.nbands, 8 * C, C))))
+                k.nbands = 1;
         }
-        const int band_imgs = x.imgs / nbands;
-        const long brows = (long)band_imgs * N_rows;
-        // (buffers are taken when first needed and, with ONE band, released as soon as the chain is past them — the arena's
-        // high-water mark of the unbanded graph is unchanged; with bands the full-height tensors live until the last band, the band-sized
-        // q2 / hidden buffers are reused by every band)
-        half_t* h2 = alloc(rows * C);
-        half_t* kv = alloc((long)B * text_len * 2 * C);
-        half_t *h3 = nullptr, *h4 = nullptr, *q2 = nullptr, *mid = nullptr;
-        if (!h2 || !kv) return UV_ERR_STATE;
-        half_t *gm2 = W(b + ".norm2.weight"), *bt2 = W(b + ".norm2.bias"), *gm3 = W(b + ".norm3.weight"), *bt3 = W(b + ".norm3.bias");
-        half_t* tb = u.animatediff ? nullptr : W(b + ".attn_temporal.to_out.0.bias");      // (the AnimateDiff block has no attn_temp)
-        if (!gm2 || !bt2 || !gm3 || !bt3 || (!tb && !u.animatediff)) return u.missing_error("unet");
-        const bool qs2 = u.find(b + ".attn2.to_q.weight#qs") != nullptr;
-        const std::string wq2 = b + (qs2 ? ".attn2.to_q.weight#qs" : ".attn2.to_q.weight");
-        const bool t_attn = u.temporal_attn_active.count(b) != 0;
+        k.t_attn = u.temporal_attn_active.count(b) != 0;
         // proj_out as extra K columns of ff.net.2 (kcat_fold; weights composed at finalize): ONE GEMM with K = 5C over the row [mid | h3] — residual = the
         // block's input, GroupNorm statistics as proj_out leaves them — replaces ff.net.2 + residual and proj_out + residual: one launch and the round trip
         // of h4 less per block.  The two halves of the row stay the two buffers they are (a 1x1 conv over the channel concat [mid | h3], as conv_shortcut
         // runs over [x | skip]): a contiguous 5C-wide buffer needs 5 units of the first-fit arena in one piece where this graph needs 4 + 1, and
         // raised its high-water mark.  Not with a trained temporal attention (it sits between the two linears) and not with a banded chain.
-        const std::string pkc = p + ".proj_out#kcat";
-        const bool kcat = (u.kcat_fold & 1) && !t_attn && nbands == 1 && C % 8 == 0 && u.find(pkc + ".weight#nhwc") && u.find(pkc + ".bias") &&
-                          rows * 16 * C < (1L << 31);           // (the conv kernels' 32-bit offsets into the wider source)
-        UV_RUN(linear(text, u.cfg.cross_attention_dim, (long)B * text_len, u.cfg.cross_attention_dim, b + ".attn2.kv#fused", "",
-                   2 * C, kv, 2 * C));
+        k.pkc = p + ".proj_out#kcat";
+        k.kcat = (u.kcat_fold & 1) && !k.t_attn && k.nbands == 1 && C % 8 == 0 && u.find(k.pkc + ".weight#nhwc") && u.find(k.pkc + ".bias") &&
+                 rows * 16 * C < (1L << 31);           // (the conv kernels' 32-bit offsets into the wider source)
+        // The text cross-attention as ONE launch where the shape allows (round 5, fused.hip): q projection (LayerNorm folded), the 77-key attention of the
+        // wave's two heads and the out projection + residual share one 64-row tile in LDS — Q and O never reach HBM.  Unbanded chains only.
+        const bool a2ok = k.nbands == 1 && u.attn2_fused && uv_attn2_fused_ok(C, heads, F * N, text_len) && u.find(b + ".attn2.to_out.0.weight#frag");
+        k.a2fused = a2ok && u.find(k.wq2 + (k.fold ? "#ln#frag" : "#frag"));
         // round 5, second step: the self-attention's out projection rides in FRONT of the fused text cross-attention (fused.hip, PRE): h2 = to_out(attn1) + h
         // is that kernel's input and residual and nothing else reads it, so it stays in the block's LDS
-        const std::string wqf0 = wq2 + "#ln#frag", wof0 = b + ".attn2.to_out.0.weight#frag", wpf0 = b + ".attn1.to_out.0.weight#frag";
-        const bool a2pre = nbands == 1 && fold && u.attn2_fused > 1 && uv_attn2_fused_ok(C, heads, F * N, text_len) && u.find(wqf0) && u.find(wof0) && u.find(wpf0);
-        for (int bd = 0; bd < nbands; ++bd) {
-            const long r0 = (long)bd * brows, o = r0 * C;
-            float* lb = lnst ? lnst + r0 * (C / 160) * 2 : nullptr;
-            if (a2pre) {
-                half_t* kvf = alloc(uv_attn2_kvf_halfs(B, heads, d));
-                if (!kvf || !(h3 = alloc(rows * C))) return UV_ERR_STATE;
-                UV_RUN(uv_launch_kv_frag_pack(kv, kvf, B, text_len, C, heads, s));
-                Attn2Params a2;
-                a2.X = t0; a2.ldx = C; a2.M = (int)rows;
-                a2.Wp_f = W(wpf0); a2.bias_p = W(b + ".attn1.to_out.0.bias"); a2.Rp = h; a2.ldrp = C;
-                a2.ln_eps = 1e-5f; a2.ln_slots = C / 160;
-                a2.ln_wsum = (const float*)W(wq2 + "#ln.wsum"); a2.ln_bias = (const float*)W(wq2 + "#ln.bias");
-                a2.Wq_f = W(wqf0); a2.kvf = kvf;
-                a2.rows_per_branch = F * N; a2.heads = heads; a2.Nkv = text_len;
-                a2.q_prescaled = qs2; a2.scale_log2e = ap.scale_log2e;
-                a2.Wo_f = W(wof0); a2.bias_o = W(b + ".attn2.to_out.0.bias");
-                a2.Y = h3; a2.ldy = C;
-                a2.stats_out = fold3 ? lb : nullptr;
-                if (!a2.bias_p || !a2.bias_o || !a2.ln_wsum || !a2.ln_bias) return u.missing_error("unet");
-                UV_RUN(uv_launch_attn2_fused(a2, C, s));
-                free(kvf);
-                free(kv);
-                free(h);
-                free(h2);
-            } else {
-            UV_RUN(linear(t0 + o, C, brows, C, b + ".attn1.to_out.0.weight", b + ".attn1.to_out.0.bias", C, h2 + o, C, h + o, C, nullptr, 0, lb));
-            if (nbands == 1) free(h);
-            // ---- attn2 (text)
-            // ONE launch where the shape allows (round 5, fused.hip): q projection (LayerNorm folded), the 77-key attention of the wave's two
-            // heads and the out projection + residual share one 64-row tile in LDS — Q and O never reach HBM
-            const std::string wqf = wq2 + (fold ? "#ln#frag" : "#frag"), wof = b + ".attn2.to_out.0.weight#frag";
-            if (nbands == 1 && u.attn2_fused && uv_attn2_fused_ok(C, heads, F * N, text_len) && u.find(wqf) && u.find(wof)) {
-                half_t* kvf = alloc(uv_attn2_kvf_halfs(B, heads, d));
-                if (!kvf || !(h3 = alloc(rows * C))) return UV_ERR_STATE;
-                UV_RUN(uv_launch_kv_frag_pack(kv, kvf, B, text_len, C, heads, s));
-                if (!fold) UV_RUN(uv_launch_layernorm(h2, C, t0, C, gm2, bt2, rows, C, 1e-5f, s));
-                Attn2Params a2;
-                a2.X = fold ? h2 : t0; a2.ldx = C; a2.M = (int)rows;
-                if (fold) {
-                    a2.ln_stats = lb; a2.ln_slots = C / 160; a2.ln_eps = 1e-5f;
-                    a2.ln_wsum = (const float*)W(wq2 + "#ln.wsum"); a2.ln_bias = (const float*)W(wq2 + "#ln.bias");
-                    if (!a2.ln_wsum || !a2.ln_bias) return u.missing_error("unet");
-                }
-                a2.Wq_f = W(wqf); a2.kvf = kvf;
-                a2.rows_per_branch = F * N; a2.heads = heads; a2.Nkv = text_len;
-                a2.q_prescaled = qs2; a2.scale_log2e = ap.scale_log2e;
-                a2.Wo_f = W(wof); a2.bias_o = W(b + ".attn2.to_out.0.bias");
-                a2.R = h2; a2.ldr = C; a2.Y = h3; a2.ldy = C;
-                a2.stats_out = fold3 ? lb : nullptr;
-                if (!a2.bias_o) return u.missing_error("unet");
-                UV_RUN(uv_launch_attn2_fused(a2, C, s));
-                free(kvf);
-                free(kv);
-                free(h2);
-            } else {
-            if (!q2 && !(q2 = alloc(brows * C))) return UV_ERR_STATE;
-            if (!fold) UV_RUN(uv_launch_layernorm(h2 + o, C, t0 + o, C, gm2, bt2, brows, C, 1e-5f, s));
-            if (fold) UV_RUN(linear(h2 + o, C, brows, C, wq2 + "#ln", "", C, q2, C, nullptr, 0, nullptr, 0, nullptr, lb));
-            else UV_RUN(linear(t0 + o, C, brows, C, wq2, "", C, q2, C));
-            ap.q = q2; ap.ldq = C;
-            ap.k = kv; ap.v = kv + C; ap.ldkv = 2 * C;
-            ap.o = t0 + o; ap.ldo = C;
-            ap.src_idx = idx_text + bd * band_imgs; ap.src_cnt = nullptr; ap.src_logw = nullptr; ap.nsrc = 1; ap.Nkv = text_len;
-            ap.BF = band_imgs;
-            ap.q_prescaled = qs2;
-            UV_RUN(uv_launch_attention(ap, s));
-            if (nbands == 1) { free(q2); free(kv); }
-            if (!h3 && !(h3 = alloc(rows * C))) return UV_ERR_STATE;
-            UV_RUN(linear(t0 + o, C, brows, C, b + ".attn2.to_out.0.weight", b + ".attn2.to_out.0.bias", C, h3 + o, C, h2 + o, C, nullptr, 0, fold3 ? lb : nullptr));
-            if (nbands == 1) free(h2);
-            }
-            }
-            if (!mid && !(mid = alloc(brows * 4 * C))) return UV_ERR_STATE;
-            // ---- GEGLU feed-forward (+ the bias-only temporal attention, attention.py:233)
-            // (K = 320: the X-resident kernel and its weight order, any row count)
-            const bool xres = u.find(b + ".ff.net.0.proj.weight#xres") != nullptr && uv_geglu_xres_ok(8 * C, C, brows);
-            const std::string wff = b + (xres ? ".ff.net.0.proj.weight#xres" : ".ff.net.0.proj.weight#geglu");
-            const std::string bff = b + (xres ? ".ff.net.0.proj.bias#xres" : ".ff.net.0.proj.bias#geglu");
-            if (!fold3) {
-                UV_RUN(uv_launch_layernorm(h3 + o, C, t0 + o, C, gm3, bt3, brows, C, 1e-5f, s));
-                UV_RUN(linear(t0 + o, C, brows, C, wff, bff, 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1));
-            } else {
-                UV_RUN(linear(h3 + o, C, brows, C, wff + "#ln", "", 8 * C, mid, 4 * C, nullptr, 0, nullptr, xres ? 2 : 1, nullptr, lb));
-            }
-            if (nbands == 1 && lnst) free(lnst);
-            if (kcat) continue;           // ff.net.2 runs inside the K = 5C GEMM behind the loop
-            if (!h4 && !(h4 = alloc(rows * C))) return UV_ERR_STATE;
-            UV_RUN(linear(mid, 4 * C, brows, 4 * C, b + ".ff.net.2.weight", b + ".ff.net.2.bias", C, h4 + o, C, h3 + o, C, t_attn ? nullptr : tb));
+        k.a2pre = k.a2fused && k.fold && u.attn2_fused > 1 && u.find(b + ".attn1.to_out.0.weight#frag");
+        return UV_OK;
+    }
+    // The block's GroupNorm, or its fold into proj_in: h (and the row statistics of h when the LayerNorms are folded)
+    int proj_in(Block& k) {
+        const Act& x = *k.x;
+        const int C = k.C;
+        if (!(k.t0 = alloc(k.rows * C))) return UV_ERR_STATE;
+        LinOpt lo;
+        half_t* wsets = nullptr;
+        float* b32 = nullptr;
+        if (k.gnf) {
+            wsets = alloc((long)x.imgs * C * C);
+            b32 = (float*)alloc((long)x.imgs * C * 2);
+            if (!wsets || !b32) return UV_ERR_STATE;
+            UvGnFold gf;
+            gf.W = W(k.wpi); gf.bias = W(k.p + ".proj_in.bias"); gf.N = C; gf.W_out = wsets; gf.bias32 = b32;
+            if (!gf.W || !gf.bias) return u.missing_error("unet");
+            UV_RUN(groupnorm(x, nullptr, k.N, 1e-6f, k.p + ".norm", 0, nullptr, false, &gf));
+            lo.wsets = wsets; lo.bias32 = b32; lo.rows_per_set = k.N;
+        } else {
+            UV_RUN(groupnorm(x, nullptr, k.N, 1e-6f, k.p + ".norm", 0, k.t0));
         }
-        ap.BF = x.imgs;                // (the band loop narrowed it)
-        if (nbands > 1) {
-            free(h);
-            free(q2);
-            free(kv);
-            free(h2);
-            if (lnst) free(lnst);
+        if (!(k.h = alloc(k.rows * C))) return UV_ERR_STATE;
+        if (k.fold && !(k.lnst = (float*)alloc(k.rows * (C / 160) * 4))) return UV_ERR_STATE;
+        lo.stats_out = k.lnst;
+        UV_RUN(linear(k.gnf ? x.p : k.t0, C, k.rows, C, k.wpi, k.p + ".proj_in.bias", C, k.h, C, lo));
+        free(wsets);      // (null without the fold: release ignores it)
+        free(b32);
+        return UV_OK;
+    }
+    // norm1, q|k|v, the AdaIN shift and the self-attention (into t0).  Frame shard: the boundary frames' hidden rows leave right behind norm1 (kv_post), the
+    // attention runs over the key frames this rank holds while they travel, and on ranks > 0 a second phase over the two halo frames follows (attn1_halo)
+    int attn1(Block& k) {
+        const int C = k.C, N = k.N;
+        const long rows = k.rows;
+        half_t *gm = W(k.b + ".norm1.weight"), *bt = W(k.b + ".norm1.bias");
+        if (!gm || !bt) return u.missing_error("unet");
+        if (!k.fold) UV_RUN(uv_launch_layernorm(k.h, C, k.t0, C, gm, bt, rows, C, 1e-5f, s));
+        const bool shard = u.world > 1, halo = shard && u.rank > 0;
+        if (shard) UV_RUN(kv_post(k.h, C, N));                  // the boundary frames' hidden rows leave now, on the forked stream
+        const long extra_rows = shard ? (long)2 * B * N : 0;     // the halo frames' q|k|v rows behind the local ones: [prev: B x N | first: B x N]
+        half_t* qkv = alloc((rows + extra_rows) * 3 * C);
+        if (!qkv) return UV_ERR_STATE;
+        LinOpt lq;
+        lq.ln_in = k.lnst;      // (set when `fold`: the linear then reads the raw rows)
+        UV_RUN(linear(k.fold ? k.h : k.t0, C, rows, C, k.fold ? k.wqkv + "#ln" : k.wqkv, "", 3 * C, qkv, 3 * C, lq));
+        if (k.shift) UV_RUN(uv_launch_adain_shift(qkv, 3 * C, F, N, C, ad_ws, ad_ws + (long)F * 2 * C, pnp->alpha, k.beta, pnp->gamma, s));
+        AttnParams ap;
+        ap.q = qkv; ap.k = qkv + C; ap.v = qkv + 2 * C;
+        ap.ldq = ap.ldkv = 3 * C;
+        ap.o = k.t0; ap.ldo = C;
+        if (u.animatediff) {      // plain per-frame self-attention (attention.py:344: no video_length, no key frames), registered or not
+            ap.src_idx = idx_self;
+            ap.nsrc = 1;
+        } else {
+            ap.src_idx = k.registered ? idx_pnp : idx_stock;
+            ap.src_cnt = k.registered ? cnt_pnp : cnt_stock;
+            ap.src_logw = k.registered ? lw_pnp : lw_stock;
+            ap.nsrc = k.registered ? 2 : 3;
         }
-        if (kcat) {
-            free(t0);
-            Act am{mid, x.imgs, x.H, x.W, 4 * C}, a3{h3, x.imgs, x.H, x.W, C};
-            UV_RUN(conv(am, &a3, pkc, C, 1, 1, 0, nullptr, x.p, out, 0, true));
-            free(mid);
-            free(h3);
+        ap.BF = k.x->imgs; ap.Nq = N; ap.Nkv = N; ap.heads = k.heads; ap.d = k.d;
+        ap.scale_log2e = k.scale_log2e;
+        ap.q_prescaled = k.qs;
+        float* state = nullptr;
+        if (halo) {               // phase 1: the key frames this rank holds; (m, l) per query stays behind for phase 2
+            state = (float*)alloc((long)k.x->imgs * k.heads * N * 4);
+            if (!state) return UV_ERR_STATE;
+            ap.state_out = state;
+        }
+        UV_RUN(uv_launch_attention(ap, s));
+        if (shard) UV_RUN(kv_join());
+        if (halo) UV_RUN(attn1_halo(k, ap, qkv, gm, bt, state));
+        free(qkv);
+        return UV_OK;
+    }
+    // the two halo frames: LayerNorm (norm1) of the received hidden rows -> to_k | to_v (all of q|k|v inside the window: the shift kernel works on
+    // the fused rows) -> the AdaIN shift of each frame -> phase 2 over them.  The sender would have computed the same K | V from the same fp16 rows
+    // (with the LayerNorm folded into the GEMM when `fold`: equal up to fp16 rounding of the normalised rows).
+    int attn1_halo(Block& k, AttnParams& ap, half_t* qkv, const half_t* gm, const half_t* bt, float* state) {
+        const int C = k.C, N = k.N;
+        const long hrows = 2L * B * N;
+        half_t* tn = alloc(hrows * C);
+        if (!tn) return UV_ERR_STATE;
+        UV_RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_prev), C, tn, C, gm, bt, (long)B * N, C, 1e-5f, s));
+        UV_RUN(uv_launch_layernorm((const half_t*)(u.comm_ws + kvs.o_rfirst), C, tn + (long)B * N * C, C, gm, bt, (long)B * N, C, 1e-5f, s));
+        half_t* qh = qkv + k.rows * 3 * C;
+        half_t* wfull = W(k.wqkv);
+        if (!wfull) return u.missing_error("unet");
+        if (k.shift) {
+            UV_RUN(linear(tn, C, hrows, C, k.wqkv, "", 3 * C, qh, 3 * C));
+            for (int sl = 0; sl < 2; ++sl)            // rows [slot][3 branches][N] = the shift kernel's [3][F = 1][N]
+                UV_RUN(uv_launch_adain_shift(qh + (long)sl * B * N * 3 * C, 3 * C, 1, N, C, ad_ws, ad_ws + 2L * C, pnp->alpha, k.beta, pnp->gamma, s));
+        } else {
+            LinOpt kv_only;
+            kv_only.wsets = wfull + (long)C * C;      // the to_k | to_v rows of the fused weight
+            UV_RUN(linear(tn, C, hrows, C, k.wqkv, "", 2 * C, qh + C, 3 * C, kv_only));
+        }
+        free(tn);
+        ap.src_idx = k.registered ? idx2_pnp : idx2_stock;
+        ap.src_cnt = k.registered ? cnt2_pnp : cnt2_stock;
+        ap.src_logw = nullptr;
+        ap.state_out = nullptr;
+        ap.state_in = state;
+        UV_RUN(uv_launch_attention(ap, s));
+        free(state);
+        return UV_OK;
+    }
+    // Opens the row-local chain: its first buffers, the norms it reads, and the text K | V of the cross-attention (one projection for all bands).
+    // (buffers are taken when first needed and, with ONE band, released as soon as the chain is past them — the arena's
+    // high-water mark of the unbanded graph is unchanged; with bands the full-height tensors live until the last band, the band-sized
+    // q2 / hidden buffers are reused by every band)
+    int chain_begin(Block& k) {
+        const int C = k.C;
+        k.h2 = alloc(k.rows * C);
+        k.kv = alloc((long)B * text_len * 2 * C);
+        if (!k.h2 || !k.kv) return UV_ERR_STATE;
+        k.gm2 = W(k.b + ".norm2.weight"); k.bt2 = W(k.b + ".norm2.bias"); k.gm3 = W(k.b + ".norm3.weight"); k.bt3 = W(k.b + ".norm3.bias");
+        k.tb = u.animatediff ? nullptr : W(k.b + ".attn_temporal.to_out.0.bias");      // (the AnimateDiff block has no attn_temp)
+        if (!k.gm2 || !k.bt2 || !k.gm3 || !k.bt3 || (!k.tb && !u.animatediff)) return u.missing_error("unet");
+        return linear(text, u.cfg.cross_attention_dim, (long)B * text_len, u.cfg.cross_attention_dim, k.b + ".attn2.kv#fused", "", 2 * C, k.kv, 2 * C);
+    }
+    // attn1's out projection + residual, norm2 and the text cross-attention + residual: h3.  Three forms (decide): the fused launch with the out
+    // projection in front, the fused launch behind a separate out projection, and q projection + attention + out projection
+    int attn2(Block& k, const Band& r) {
+        if (k.a2pre) return attn2_fused(k, r);
+        LinOpt lo;
+        lo.R = k.h + r.o; lo.ldr = k.C; lo.stats_out = r.lb;
+        UV_RUN(linear(k.t0 + r.o, k.C, r.rows, k.C, k.b + ".attn1.to_out.0.weight", k.b + ".attn1.to_out.0.bias", k.C, k.h2 + r.o, k.C, lo));
+        if (k.nbands == 1) free(k.h);
+        return k.a2fused ? attn2_fused(k, r) : attn2_unfused(k, r);
+    }
+    int attn2_fused(Block& k, const Band& r) {      // (nbands == 1: the band is the tensor)
+        const int C = k.C;
+        half_t* kvf = alloc(uv_attn2_kvf_halfs(B, k.heads, k.d));
+        if (!kvf || !(k.h3 = alloc(k.rows * C))) return UV_ERR_STATE;
+        UV_RUN(uv_launch_kv_frag_pack(k.kv, kvf, B, text_len, C, k.heads, s));
+        if (!k.fold) UV_RUN(uv_launch_layernorm(k.h2, C, k.t0, C, k.gm2, k.bt2, k.rows, C, 1e-5f, s));
+        Attn2Params a2;
+        a2.ldx = C; a2.M = (int)k.rows;
+        a2.Wq_f = W(k.wq2 + (k.fold ? "#ln#frag" : "#frag")); a2.kvf = kvf;
+        a2.rows_per_branch = F * k.N; a2.heads = k.heads; a2.Nkv = text_len;
+        a2.q_prescaled = k.qs2; a2.scale_log2e = k.scale_log2e;
+        a2.Wo_f = W(k.b + ".attn2.to_out.0.weight#frag"); a2.bias_o = W(k.b + ".attn2.to_out.0.bias");
+        a2.Y = k.h3; a2.ldy = C;
+        a2.stats_out = k.fold3 ? r.lb : nullptr;
+        if (k.fold) {
+            a2.ln_slots = C / 160; a2.ln_eps = 1e-5f;
+            a2.ln_wsum = (const float*)W(k.wq2 + "#ln.wsum"); a2.ln_bias = (const float*)W(k.wq2 + "#ln.bias");
+        }
+        if (k.a2pre) {            // X = the self-attention's output; h2 = to_out(X) + h is formed (and its statistics taken) inside
+            a2.X = k.t0;
+            a2.Wp_f = W(k.b + ".attn1.to_out.0.weight#frag"); a2.bias_p = W(k.b + ".attn1.to_out.0.bias"); a2.Rp = k.h; a2.ldrp = C;
+        } else {
+            a2.X = k.fold ? k.h2 : k.t0;
+            a2.ln_stats = k.fold ? r.lb : nullptr;
+            a2.R = k.h2; a2.ldr = C;
+        }
+        if (!a2.bias_o || (k.fold && (!a2.ln_wsum || !a2.ln_bias)) || (k.a2pre && !a2.bias_p)) return u.missing_error("unet");
+        UV_RUN(uv_launch_attn2_fused(a2, C, s));
+        free(kvf);
+        free(k.kv);
+        if (k.a2pre) free(k.h);
+        free(k.h2);
+        return UV_OK;
+    }
+    int attn2_unfused(Block& k, const Band& r) {
+        const int C = k.C;
+        if (!k.q2 && !(k.q2 = alloc(r.rows * C))) return UV_ERR_STATE;
+        if (!k.fold) UV_RUN(uv_launch_layernorm(k.h2 + r.o, C, k.t0 + r.o, C, k.gm2, k.bt2, r.rows, C, 1e-5f, s));
+        LinOpt lq;
+        lq.ln_in = r.lb;
+        UV_RUN(linear((k.fold ? k.h2 : k.t0) + r.o, C, r.rows, C, k.fold ? k.wq2 + "#ln" : k.wq2, "", C, k.q2, C, lq));
+        AttnParams ap;
+        ap.q = k.q2; ap.ldq = C;
+        ap.k = k.kv; ap.v = k.kv + C; ap.ldkv = 2 * C;
+        ap.o = k.t0 + r.o; ap.ldo = C;
+        ap.src_idx = idx_text + r.bd * r.imgs; ap.nsrc = 1;
+        ap.BF = r.imgs; ap.Nq = k.N; ap.Nkv = text_len; ap.heads = k.heads; ap.d = k.d;
+        ap.scale_log2e = k.scale_log2e;
+        ap.q_prescaled = k.qs2;
+        UV_RUN(uv_launch_attention(ap, s));
+        if (k.nbands == 1) { free(k.q2); free(k.kv); }
+        if (!k.h3 && !(k.h3 = alloc(k.rows * C))) return UV_ERR_STATE;
+        LinOpt lo;
+        lo.R = k.h2 + r.o; lo.ldr = C; lo.stats_out = k.fold3 ? r.lb : nullptr;
+        UV_RUN(linear(k.t0 + r.o, C, r.rows, C, k.b + ".attn2.to_out.0.weight", k.b + ".attn2.to_out.0.bias", C, k.h3 + r.o, C, lo));
+        if (k.nbands == 1) free(k.h2);
+        return UV_OK;
+    }
+    // GEGLU feed-forward (+ the bias-only temporal attention, attention.py:233): norm3 / GEGLU projection into mid, then ff.net.2 + residual into h4 —
+    // unless ff.net.2 runs inside the K = 5C GEMM behind the chain (kcat)
+    int ff(Block& k, const Band& r) {
+        const int C = k.C;
+        if (!k.mid && !(k.mid = alloc(r.rows * 4 * C))) return UV_ERR_STATE;
+        // (K = 320: the X-resident kernel and its weight order, any row count)
+        const bool xres = u.find(k.b + ".ff.net.0.proj.weight#xres") != nullptr && uv_geglu_xres_ok(8 * C, C, r.rows);
+        const std::string wff = k.b + (xres ? ".ff.net.0.proj.weight#xres" : ".ff.net.0.proj.weight#geglu");
+        const std::string bff = k.b + (xres ? ".ff.net.0.proj.bias#xres" : ".ff.net.0.proj.bias#geglu");
+        if (!k.fold3) UV_RUN(uv_launch_layernorm(k.h3 + r.o, C, k.t0 + r.o, C, k.gm3, k.bt3, r.rows, C, 1e-5f, s));
+        LinOpt l1;
+        l1.geglu = xres ? 2 : 1; l1.ln_in = k.fold3 ? r.lb : nullptr;
+        UV_RUN(linear((k.fold3 ? k.h3 : k.t0) + r.o, C, r.rows, C, k.fold3 ? wff + "#ln" : wff, bff, 8 * C, k.mid, 4 * C, l1));
+        if (k.nbands == 1 && k.lnst) free(k.lnst);
+        if (k.kcat) return UV_OK;
+        if (!k.h4 && !(k.h4 = alloc(k.rows * C))) return UV_ERR_STATE;
+        LinOpt l2;
+        l2.R = k.h3 + r.o; l2.ldr = C; l2.bias2 = k.t_attn ? nullptr : k.tb;
+        return linear(k.mid, 4 * C, r.rows, 4 * C, k.b + ".ff.net.2.weight", k.b + ".ff.net.2.bias", C, k.h4 + r.o, C, l2);
+    }
+
+    // TRAINED temporal attention (attention.py:336-346): LayerNorm, q|k|v, softmax over the F frames of every pixel, to_out + residual: a new h4
+    int temporal_attn(Block& k) {
+        const int C = k.C, N = k.N, heads = k.heads;
+        const long rows = k.rows;
+        UV_REQUIRE(F <= 32, "temporal attention: clips of %d frames (kernel holds <= 32 scores per query)", F);
+        half_t *gm = W(k.b + ".norm_temporal.weight"), *bt = W(k.b + ".norm_temporal.bias");
+        if (!gm || !bt) return u.missing_error("unet");
+        UV_RUN(uv_launch_layernorm(k.h4, C, k.t0, C, gm, bt, rows, C, 1e-5f, s));
+        half_t *qkvt = alloc(rows * 3 * C), *t0 = k.t0;
+        if (!qkvt) return UV_ERR_STATE;
+        UV_RUN(linear(t0, C, rows, C, k.b + ".attn_temporal.qkv#fused", "", 3 * C, qkvt, 3 * C));
+        const long nthr = (long)B * N * heads * F;
+        const float sc = 1.f / sqrtf((float)k.d);
+#define TA_CASE(D8) case 8 * D8: hipLaunchKernelGGL((temporal_attn_kernel<D8>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
+        switch (k.d) {
+            TA_CASE(1) TA_CASE(2) TA_CASE(4) TA_CASE(5) TA_CASE(8) TA_CASE(10) TA_CASE(20)
+            default: uv_set_error("temporal attention: head_dim=%d not instantiated", k.d); return UV_ERR_UNSUPPORTED;
+        }
+#undef TA_CASE
+        UV_LAUNCH_CHECK();
+        free(qkvt);
+        half_t* h5 = alloc(rows * C);
+        if (!h5) return UV_ERR_STATE;
+        LinOpt lo;
+        lo.R = k.h4; lo.ldr = C;
+        UV_RUN(linear(t0, C, rows, C, k.b + ".attn_temporal.to_out.0.weight", k.b + ".attn_temporal.to_out.0.bias", C, h5, C, lo));
+        free(k.h4);
+        k.h4 = h5;
+        return UV_OK;
+    }
+
+    // proj_out + the block's input, leaving the GroupNorm statistics of the result for the next resnet — as a plain linear over h4, or (kcat) with
+    // ff.net.2 in front of it as one K = 5C GEMM over [mid | h3]
+    int proj_out(Block& k, Act* out) {
+        const Act& x = *k.x;
+        free(k.t0);
+        if (k.kcat) {
+            Act am{k.mid, x.imgs, x.H, x.W, 4 * k.C}, a3{k.h3, x.imgs, x.H, x.W, k.C};
+            ConvOpt co;
+            co.R = x.p; co.want_gst = true;
+            UV_RUN(conv(am, &a3, k.pkc, k.C, 1, out, co));
+            free(k.mid);
+            free(k.h3);
             return UV_OK;
         }
-        free(mid);
-        free(h3);
-        if (t_attn) {      // TRAINED temporal attention (attention.py:336-346): LayerNorm, q|k|v, softmax over the F frames of every pixel, to_out + residual
-            UV_REQUIRE(F <= 32, "temporal attention: clips of %d frames (kernel holds <= 32 scores per query)", F);
-            gm = W(b + ".norm_temporal.weight"); bt = W(b + ".norm_temporal.bias");
-            if (!gm || !bt) return u.missing_error("unet");
-            UV_RUN(uv_launch_layernorm(h4, C, t0, C, gm, bt, rows, C, 1e-5f, s));
-            half_t* qkvt = alloc(rows * 3 * C);
-            if (!qkvt) return UV_ERR_STATE;
-            UV_RUN(linear(t0, C, rows, C, b + ".attn_temporal.qkv#fused", "", 3 * C, qkvt, 3 * C));
-            const long nthr = (long)B * N * heads * F;
-            const float sc = 1.f / sqrtf((float)d);
-            switch (d) {
-                case 8: hipLaunchKernelGGL((temporal_attn_kernel<1>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                case 16: hipLaunchKernelGGL((temporal_attn_kernel<2>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                case 32: hipLaunchKernelGGL((temporal_attn_kernel<4>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                case 40: hipLaunchKernelGGL((temporal_attn_kernel<5>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                case 64: hipLaunchKernelGGL((temporal_attn_kernel<8>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                case 80: hipLaunchKernelGGL((temporal_attn_kernel<10>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                case 160: hipLaunchKernelGGL((temporal_attn_kernel<20>), dim3(nb(nthr)), dim3(256), 0, s, qkvt, t0, B, F, N, C, heads, sc); break;
-                default: uv_set_error("temporal attention: head_dim=%d not instantiated", d); return UV_ERR_UNSUPPORTED;
-            }
-            UV_LAUNCH_CHECK();
-            free(qkvt);
-            half_t* h5 = alloc(rows * C);
-            if (!h5) return UV_ERR_STATE;
-            UV_RUN(linear(t0, C, rows, C, b + ".attn_temporal.to_out.0.weight", b + ".attn_temporal.to_out.0.bias", C, h5, C, h4, C));
-            free(h4);
-            h4 = h5;
-        }
-        free(t0);
-        out->imgs = x.imgs; out->H = x.H; out->W = x.W; out->C = C;
-        out->p = alloc(rows * C);
-        if (!out->p) return UV_ERR_STATE;
-        UV_RUN(linear(h4, C, rows, C, p + (u.find(p + ".proj_out.weight#nhwc") ? ".proj_out.weight#nhwc" : ".proj_out.weight"), p + ".proj_out.bias", C, out->p,
-                   C, x.p, C, nullptr, 0, nullptr, nullptr, &out->gst));
-        free(h4);
+        out->imgs = x.imgs; out->H = x.H; out->W = x.W; out->C = k.C;
+        if (!(out->p = alloc(k.rows * k.C))) return UV_ERR_STATE;
+        LinOpt lo;
+        lo.R = x.p; lo.ldr = k.C; lo.gst_out = &out->gst;
+        UV_RUN(linear(k.h4, k.C, k.rows, k.C, k.p + (u.find(k.p + ".proj_out.weight#nhwc") ? ".proj_out.weight#nhwc" : ".proj_out.weight"), k.p + ".proj_out.bias",
+                      k.C, out->p, k.C, lo));
+        free(k.h4);
         return UV_OK;
+    }
+
+    int transformer(const std::string& p, const Act& x, bool pnp_layer, int heads, Act* out) {
+        Block k;
+        k.p = p; k.b = p + ".transformer_blocks.0"; k.x = &x;
+        k.C = x.C; k.heads = heads; k.d = x.C / heads; k.N = x.H * x.W; k.rows = x.rows();
+        UV_RUN(decide(k, pnp_layer));
+        UV_RUN(proj_in(k));
+        UV_RUN(attn1(k));
+        UV_RUN(chain_begin(k));
+        Band r;
+        r.imgs = x.imgs / k.nbands;
+        r.rows = (long)r.imgs * k.N;
+        for (r.bd = 0; r.bd < k.nbands; ++r.bd) {
+            r.o = r.bd * r.rows * k.C;
+            r.lb = k.lnst ? k.lnst + r.bd * r.rows * (k.C / 160) * 2 : nullptr;
+            UV_RUN(attn2(k, r));
+            UV_RUN(ff(k, r));
+        }
+        if (k.nbands > 1)      // (one band released them on its way)
+            for (void* q : std::initializer_list<void*>{k.h, k.q2, k.kv, k.h2, k.lnst}) free(q);
+        if (!k.kcat) {
+            free(k.mid);
+            free(k.h3);
+            if (k.t_attn) UV_RUN(temporal_attn(k));
+        }
+        return proj_out(k, out);
     }
 
     // The motion module `p` ("down_blocks.0.motion_modules.1") behind a resnet / transformer pair (unet_blocks.py:411): x becomes module(x), its old
@@ -1263,68 +1308,22 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     UV_RUN(reserve(B, F, H, Wd));
     clear_missing();
     const int* boc = cfg.block_out_channels;
-    const int C0 = boc[0], TED = 4 * C0, L = cfg.layers_per_block;
+    const int C0 = boc[0], L = cfg.layers_per_block;
     Fwd f{*this, s, B, F, text_len, pnp};
     f.text = text;
-    const int* tab = idx_tables[((long)B << 20) | F | ((long)rank << 40) | ((long)world << 50)];
-    const long BF_ = (long)B * F;
-    f.idx_stock = tab;
-    f.idx_pnp = tab + BF_ * 3;
-    f.idx_text = tab + BF_ * 5;
-    f.cnt_stock = tab + BF_ * 6;
-    f.cnt_pnp = tab + BF_ * 7;
-    f.lw_stock = (const float*)(tab + BF_ * 8);
-    f.lw_pnp = (const float*)(tab + BF_ * 11);
-    if (world > 1 && rank > 0) {
-        f.idx2_stock = tab + BF_ * 13;
-        f.idx2_pnp = tab + BF_ * 16;
-        f.cnt2_stock = tab + BF_ * 18;
-        f.cnt2_pnp = tab + BF_ * 19;
-    }
-    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats(B * F, cfg.norm_num_groups) * sizeof(float));
-    f.ad_ws = (float*)arena.alloc((size_t)F * 2 * boc[3] * 2 * sizeof(float) + 1024);
-    f.sk_ws = (float*)arena.alloc(UV_SPLITK_WS_BYTES);
-    UV_REQUIRE(f.gn_ws && f.ad_ws && f.sk_ws, "forward: arena too small");
-    if (animatediff) {
-        f.idx_self = tab + BF_ * 13;
-        if (!motions.empty()) {       // (without modules the motion config is not validated and not used)
-            f.mgn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats(B * F, ad.motion.norm_groups) * sizeof(float) + 256);
-            UV_REQUIRE(f.mgn_ws, "forward: arena too small");
-        }
-    }
-    if (gn_producer) {             // statistics of up to 64 level-0-sized tensors: [rows/16][G][2] fp32 each (3 MB per tensor at 3 x 16 x 64 x 64: 201 MB, counted in
-                                   // reserve()); taken AFTER the mandatory workspaces, so it is the part that degrades first (consumers fall back to their own pass)
-        f.gst_left = (size_t)(((long)B * F * H * Wd + 15) / 16) * cfg.norm_num_groups * 2 * 64;
-        f.gst_pool = (float*)arena.alloc(f.gst_left * sizeof(float));
-        if (!f.gst_pool) f.gst_left = 0;
-    }
-
-    // ---- time embedding (unet_3d_condition.py:359-365)
-    half_t* tsin = f.alloc((long)B * C0);
-    half_t* e1 = f.alloc((long)B * TED);
-    f.emb = f.alloc((long)B * TED);
-    if (!tsin || !e1 || !f.emb) return UV_ERR_STATE;
-    UV_RUN(uv_launch_timestep_embed(timestep, tsin, B, C0, cfg.flip_sin_to_cos, cfg.freq_shift, s));
-    {
-        half_t *w1 = W("time_embedding.linear_1.weight"), *b1 = W("time_embedding.linear_1.bias");
-        half_t *w2 = W("time_embedding.linear_2.weight"), *b2 = W("time_embedding.linear_2.bias");
-        if (!w1 || !b1 || !w2 || !b2) return missing_error("unet");
-        UV_RUN(uv_launch_linear_small(tsin, w1, b1, e1, B, TED, C0, 0, s));
-        UV_RUN(uv_launch_linear_small(e1, w2, b2, f.emb, B, TED, TED, 1, s));
-        if (temb_total > 0) {           // resnet.py:349-351 for all resnets at once
-            half_t *wa = W("time_emb_proj#all.weight"), *ba = W("time_emb_proj#all.bias");
-            f.temb_all = f.alloc((long)B * temb_total);
-            if (!wa || !ba || !f.temb_all) return missing_error("unet");
-            UV_RUN(uv_launch_linear_small(f.emb, wa, ba, f.temb_all, B, (int)temb_total, TED, 1, s));
-        }
-    }
+    UV_RUN(f.workspaces(idx_tables[((long)B << 20) | F | ((long)rank << 40) | ((long)world << 50)], H, Wd));
+    UV_RUN(f.time_embedding(timestep));
     // ---- conv_in
     const int CP = (cfg.in_channels + 7) / 8 * 8;
     Act x0{f.alloc((long)B * F * H * Wd * CP), B * F, H, Wd, CP};
     if (!x0.p) return UV_ERR_STATE;
     UV_RUN(uv_launch_ncfhw_to_nhwc(sample, x0.p, B, cfg.in_channels, F, H * Wd, CP, s));
     Act x;
-    UV_RUN(f.conv(x0, nullptr, "conv_in", C0, 9, 1, 0, nullptr, nullptr, &x, 0, true));
+    ConvOpt with_gst, down2, up2;      // the three plain forms: GroupNorm statistics from the epilogue; also stride 2; also over the nearest-x2 upsampled input
+    with_gst.want_gst = down2.want_gst = up2.want_gst = true;
+    down2.stride = 2;
+    up2.up = 1;
+    UV_RUN(f.conv(x0, nullptr, "conv_in", C0, 9, &x, with_gst));
     f.free(x0.p);
 
     std::vector<Act> skips;
@@ -1351,7 +1350,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         }
         if (i != 3) {
             Act y;
-            UV_RUN(f.conv(x, nullptr, p + ".downsamplers.0.conv", boc[i], 9, 2, 0, nullptr, nullptr, &y, 0, true));
+            UV_RUN(f.conv(x, nullptr, p + ".downsamplers.0.conv", boc[i], 9, &y, down2));
             x = y;
             skips.push_back(x);
         }
@@ -1391,7 +1390,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         }
         if (i != 3) {
             Act y;
-            UV_RUN(f.conv(x, nullptr, p + ".upsamplers.0.conv", Cout, 9, 1, 1, nullptr, nullptr, &y, 0, true));
+            UV_RUN(f.conv(x, nullptr, p + ".upsamplers.0.conv", Cout, 9, &y, up2));
             f.free(x.p);
             x = y;
         }
@@ -1403,7 +1402,7 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     if (!n) return UV_ERR_STATE;
     UV_RUN(f.groupnorm(x, nullptr, (animatediff && ad.inflated_groupnorm ? 1 : F) * x.H * x.W, cfg.norm_eps, "conv_norm_out", 1, n, true));
     Act na{n, x.imgs, x.H, x.W, x.C}, y;
-    UV_RUN(f.conv(na, nullptr, "conv_out", cfg.out_channels, 9, 1, 0, nullptr, nullptr, &y));
+    UV_RUN(f.conv(na, nullptr, "conv_out", cfg.out_channels, 9, &y));
     UV_RUN(uv_launch_nhwc_to_ncfhw(y.p, cfg.out_channels, eps_out, B, cfg.out_channels, F, H * Wd, s));
     if (x_dirty) {                 // the forked stream's posts of this forward complete before anything the caller queues behind it (and a capture can end)
         UV_HIP(hipEventRecord(ev_join, xstream));

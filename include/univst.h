@@ -81,6 +81,32 @@ int univst_unet_forward(univst_unet* h, const void* sample, float timestep, cons
  * for batch element 0 as [F,H',W',C] fp16 (animatediff/models/unet.py:453-459).  feat_out NULL or ft_index outside 0..3: UNIVST_ERR_ARG before any launch. */
 int univst_unet_forward_tap(univst_unet* h, const void* sample, float timestep, const void* text, int B, int F, int H, int W, int text_len,
                             const univst_pnp* pnp, void* eps_out, void* feat_out, int ft_index, void* stream);
+/* Static style: the style branch of the PnP step as ONE frame instead of F copies of it (DESIGN.md "Static style branch").  The style input of
+ * the SD path is a single image repeated F times (ddim_inversion.py:45-65); with 2-D-initialised temporal layers F identical frames give F identical
+ * results, and all the stylised branch takes from the style branch is the to_k / to_v rows of the same frame at the eight PnP layers
+ * (pnp_utils.py:54-55).  A step inside the window is then two calls: univst_unet_style_bank (one frame, B = F = 1) fills the bank, and
+ * univst_unet_forward_static_style (B = 2: content, stylised) shifts against it.
+ *
+ * The bank is caller-owned device memory, 16-byte aligned, of univst_unet_style_bank_bytes(h, H, W) bytes (a negative code on a bad argument).  Layout:
+ * for each PnP layer in graph order (up_blocks.1.attentions.1, .2, up_blocks.2.attentions.0 .. 2, up_blocks.3.attentions.0 .. 2) the K | V rows
+ * [N_l, 2 C_l] fp16 of the style frame (N_l = that level's H' * W', row stride 2 C_l, K columns first), each layer's block starting at a multiple of
+ * 256 bytes.  The column statistics of the shift are NOT kept in the bank: the shift takes them from the rows (one frame) on every call.
+ *
+ *   style_bank            sample [1,Cin,1,H,W], text [1,L,D].  Runs the frame with the PnP key sources and WITHOUT the shift (the reference only ever
+ *                         modifies chunk 2, pnp_utils.py:53-57) up to the last PnP layer's projection, leaving every layer's rows in the bank.
+ *                         *active_out = whether pnp->idx is inside the window; outside it the call returns UNIVST_OK without a launch and
+ *                         leaves the bank alone.  pnp NULL or not registered, a NULL bank with the window open, bank_bytes too small: UNIVST_ERR_ARG.
+ *   forward_static_style  sample [2,Cin,F,H,W] (content, stylised), text [2,L,D] -> eps [2,Cout,F,H,W].  Inside the window the eight PnP layers
+ *                         run univst_attention_adain_shift_static against the bank; a NULL or too small bank there is UNIVST_ERR_ARG.  Outside the
+ *                         window (or with pnp NULL / not registered) it is exactly univst_unet_forward with B = 2, and bank may be NULL.
+ * Refused with UNIVST_ERR_UNSUPPORTED before any launch, both entries: a handle of univst_unet_create_animatediff (the motion modules' position
+ * encoding makes identical frames differ), a handle on which finalize found a trained temporal unit (the frames are coupled), a handle with a
+ * communicator attached (the halo phase of a frame shard shifts against the style's hidden rows). */
+int64_t univst_unet_style_bank_bytes(univst_unet* h, int H, int W);
+int univst_unet_style_bank(univst_unet* h, const void* sample, float timestep, const void* text, int H, int W, int text_len, const univst_pnp* pnp,
+                           void* bank, int64_t bank_bytes, int* active_out, void* stream);
+int univst_unet_forward_static_style(univst_unet* h, const void* sample, float timestep, const void* text, int F, int H, int W, int text_len,
+                                     const univst_pnp* pnp, const void* bank, int64_t bank_bytes, void* eps_out, void* stream);
 /* frame-sharded multi-GPU: this rank holds frames [rank*F, (rank+1)*F) of a clip of world*F frames
  * for ALL branches.  comm_ws is a caller-owned device workspace (>= 64 KiB + 4 x the largest frame pack); the callbacks are invoked on the
  * host while forward() enqueues work and must enqueue the collective on the SAME stream forward() was given (RCCL through
@@ -635,6 +661,13 @@ int univst_axpbypcz(const void* x, const void* y, const void* z, void* out, floa
  * Replaces pnp_utils.py:47-57 + attention_adain :114-125. */
 int univst_attention_adain_shift(void* qkv, int64_t ld, int F, int N, int C, float alpha, float beta, float gamma,
                                  void* stats_ws, void* stream);
+/* The same shift where the style is ONE frame held elsewhere: qkv is the fused buffer of TWO branches [2*F*N, ld >= 3C] (content rows, then stylised
+ * rows), style_kv one frame of style K | V rows [N, ld_style >= 2C].  Every frame f reads the same style rows, and one set of column statistics —
+ * computed here from style_kv on every call, not precomputed — serves all frames: per element the arithmetic of univst_attention_adain_shift on a
+ * three-branch buffer whose style branch is that frame repeated F times.  Only the first 3C columns of the stylised rows are written.  stats_ws: 4C floats.
+ * C % 8 != 0, C > 2048, ld or ld_style no multiple of 8, ld < 3C, ld_style < 2C, F or N < 1: UNIVST_ERR_ARG before any launch. */
+int univst_attention_adain_shift_static(void* qkv, int64_t ld, const void* style_kv, int64_t ld_style, int F, int N, int C, float alpha, float beta,
+                                        float gamma, void* stats_ws, void* stream);
 /* latent_adain on [1,C,F,H,W] (pnp_utils.py:128-139) */
 int univst_latent_adain(const void* cnt, const void* sty, void* out, int C, int F, int HW, void* stream);
 /* the same in two halves for frame shards: stats[c] = {sum, sumsq} of the content over the LOCAL (F,H,W) (the caller

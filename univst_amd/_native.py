@@ -88,6 +88,9 @@ SIGNATURES = {
     "univst_unet_reserve": (_I, [_P, _I, _I, _I, _I]),
     "univst_unet_forward": (_I, [_P, _P, _F, _P, _I, _I, _I, _I, _I, C.POINTER(PnP), _P, _P, _I, _P]),
     "univst_unet_forward_tap": (_I, [_P, _P, _F, _P, _I, _I, _I, _I, _I, C.POINTER(PnP), _P, _P, _I, _P]),
+    "univst_unet_style_bank_bytes": (_L, [_P, _I, _I]),
+    "univst_unet_style_bank": (_I, [_P, _P, _F, _P, _I, _I, _I, C.POINTER(PnP), _P, _L, C.POINTER(_I), _P]),
+    "univst_unet_forward_static_style": (_I, [_P, _P, _F, _P, _I, _I, _I, _I, C.POINTER(PnP), _P, _L, _P, _P]),
     "univst_unet_set_comm": (_I, [_P, _I, _I, _P, _L, ALLREDUCE_FN, KVEXCHANGE_FN, _P]),
     "univst_unet_set_option": (_I, [_P, C.c_char_p, _I]),
     "univst_unet_query": (_I, [_P, C.c_char_p, C.POINTER(C.c_double)]),
@@ -185,6 +188,7 @@ SIGNATURES = {
     "univst_sd3_unpatchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "univst_axpbypcz": (_I, [_P, _P, _P, _P, _F, _F, _F, _L, _P]),
     "univst_attention_adain_shift": (_I, [_P, _L, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "univst_attention_adain_shift_static": (_I, [_P, _L, _P, _L, _I, _I, _I, _F, _F, _F, _P, _P]),
     "univst_latent_adain": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "univst_latent_adain_stats": (_I, [_P, _P, _I, _I, _I, _P]),
     "univst_latent_adain_apply": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _P]),
@@ -883,6 +887,20 @@ def attention_adain_shift_(qkv, F, N, C_, alpha, beta, gamma, return_stats=False
           "attention_adain_shift")
     if return_stats:
         return qkv, ws[:F * 2 * C_].view(F, 2 * C_), ws[F * 2 * C_:2 * F * 2 * C_].view(F, 2 * C_)
+    return qkv
+
+
+def attention_adain_shift_static_(qkv, style_kv, F, N, C_, alpha, beta, gamma):
+    """in place on the fused TWO-branch buffer [2*F*N, >= 3C] (content rows, then stylised rows) against ONE frame of style K | V rows
+    [N, >= 2C] that serves every frame; both may be column-sliced views of wider buffers (unit column stride)."""
+    for t, rows, what in ((qkv, 2 * F * N, "qkv"), (style_kv, N, "style_kv")):
+        if not (t.is_cuda and t.dtype == torch.float16):
+            raise ValueError(f"adain shift: {what}: expected an fp16 CUDA/HIP tensor, got {t.dtype} {t.device}")
+        if t.dim() != 2 or t.shape[0] != rows or t.stride(1) != 1:
+            raise ValueError(f"adain shift: {what}: expected {rows} rows with unit column stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    ws = torch.empty(4 * C_, device=qkv.device, dtype=torch.float32)
+    check(load().univst_attention_adain_shift_static(ptr(qkv), qkv.stride(0), ptr(style_kv), style_kv.stride(0), F, N, C_, alpha, beta, gamma,
+                                                     ptr(ws), stream_ptr()), "attention_adain_shift_static")
     return qkv
 
 

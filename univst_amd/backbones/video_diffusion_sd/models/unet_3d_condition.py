@@ -501,6 +501,58 @@ class UNetPseudo3DConditionModel(nn.Module):
             self.last_feature_map = feat
         return UNetPseudo3DConditionOutput(sample=eps.to(sample.dtype) if sample.dtype != torch.float16 else eps)
 
+    # ------------------------------------------------------------------ static style (include/univst.h univst_unet_style_bank)
+    def _static_style_args(self, what, sample, timestep, text, batch):
+        if sample.dim() != 5 or sample.shape[0] != batch:
+            raise ValueError(f"{what}: sample must be [{batch},C,F,H,W], got {tuple(sample.shape)}")
+        if getattr(self, "_frame_shard", None) is not None:
+            raise NotImplementedError(f"{what}: the static style is not built for a frame shard (detach the shard first)")
+        self._sync_native()
+        x = sample.to(torch.float16).contiguous()
+        txt = text.to(torch.float16).contiguous()
+        if txt.shape[0] != batch:
+            raise ValueError(f"{what}: encoder_hidden_states batch {txt.shape[0]} != sample batch {batch}")
+        t = float(timestep.reshape(-1)[0].item()) if torch.is_tensor(timestep) else float(timestep)
+        return x, txt, t
+
+    @torch.no_grad()
+    def style_bank(self, frame: torch.Tensor, timestep, text: torch.Tensor, bank: Optional[torch.Tensor] = None):
+        """The style image as ONE frame: runs ``frame`` [1,C,1,H,W] with the PnP key sources and leaves the K | V rows of the eight PnP layers in a
+        bank (a uint8 device tensor, allocated here unless ``bank`` is given for reuse) for ``forward_static_style``.  Returns the bank, or ``None`` when
+        the registered step index lies outside the PnP window (nothing is launched then, and a given ``bank`` stays as it is)."""
+        import ctypes as C
+        x, txt, t = self._static_style_args("style_bank", frame, timestep, text, 1)
+        if x.shape[2] != 1:
+            raise ValueError(f"style_bank: the style is one frame, got {x.shape[2]}")
+        lib = _native.load()
+        H, W = x.shape[-2:]
+        pnp = self._pnp_state()
+        need = lib.univst_unet_style_bank_bytes(self._native_handle, H, W)
+        if need < 0:
+            _native.check(int(need), "unet_style_bank_bytes")
+        if bank is None:
+            bank = torch.empty(need, device=x.device, dtype=torch.uint8)
+        active = C.c_int(0)
+        _native.check(lib.univst_unet_style_bank(self._native_handle, x.data_ptr(), t, txt.data_ptr(), H, W, txt.shape[1],
+                                                 C.byref(pnp) if pnp is not None else None, bank.data_ptr(), bank.numel() * bank.element_size(),
+                                                 C.byref(active), _native.stream_ptr()), "unet_style_bank")
+        return bank if active.value else None
+
+    @torch.no_grad()
+    def forward_static_style(self, sample2: torch.Tensor, timestep, text2: torch.Tensor, bank: Optional[torch.Tensor]):
+        """The step of the stylised branch against a style bank: ``sample2`` [2,C,F,H,W] = (content, stylised), ``text2`` [2,L,D] -> eps [2,C,F,H,W].
+        ``bank`` is what ``style_bank`` returned for this step; ``None`` outside the PnP window, where this is the ordinary two-branch forward."""
+        import ctypes as C
+        x, txt, t = self._static_style_args("forward_static_style", sample2, timestep, text2, 2)
+        _, _, F_, H, W = x.shape
+        eps = torch.empty(2, self.config.out_channels, F_, H, W, device=x.device, dtype=torch.float16)
+        pnp = self._pnp_state()
+        _native.check(_native.load().univst_unet_forward_static_style(
+            self._native_handle, x.data_ptr(), t, txt.data_ptr(), F_, H, W, txt.shape[1], C.byref(pnp) if pnp is not None else None,
+            bank.data_ptr() if bank is not None else None, bank.numel() * bank.element_size() if bank is not None else 0, eps.data_ptr(),
+            _native.stream_ptr()), "unet_forward_static_style")
+        return UNetPseudo3DConditionOutput(sample=eps.to(sample2.dtype) if sample2.dtype != torch.float16 else eps)
+
     # ------------------------------------------------------------------ loading (unet_3d_condition.py:445-509)
     @classmethod
     def from_2d_model(cls, model_path, model_config=None):

@@ -216,7 +216,7 @@ class SpatioTemporalStableDiffusionPipeline:
                              generator=None, latents=None, output_type="tensor", return_dict=True, callback=None,
                              callback_steps=1, content_inv_path=None, style_inv_path=None, mask_path=None,
                              content_inv_latents=None, style_inv_latents=None, masks=None, smoother=None, flow_fn=None,
-                             latent_flows=None, skip_dead_branches=False, shard=None, **kwargs):
+                             latent_flows=None, skip_dead_branches=False, shard=None, static_style=False, **kwargs):
         if eta != 0.0:
             raise NotImplementedError("eta != 0")
         device = self._execution_device
@@ -261,6 +261,11 @@ class SpatioTemporalStableDiffusionPipeline:
                 frames = sliding_window_smooth(frames, flow_fn, m01)
                 return engine.return_to_timestep(self.scheduler, t, lat, self.get_latent_image(frames))
         cb = (lambda i, t, l: callback(i, t, l) if i % callback_steps == 0 else None) if callback is not None else None
+        if static_style and shard is None:      # (the style branch as one frame is not built for a frame shard: no automatic sharding either)
+            from ....parallel import dist_rank_world
+            if dist_rank_world()[1] > 1:
+                raise NotImplementedError("static_style under torchrun: pass shard=False (every rank on the whole clip) or drop static_style")
+            shard = False
         if shard is None:            # one process per GPU under torchrun: shard the frames (checked once per pipeline and geometry)
             from ....parallel import auto_frame_shard, dist_rank_world
             if dist_rank_world()[1] > 1:
@@ -270,7 +275,7 @@ class SpatioTemporalStableDiffusionPipeline:
         if shard is not None and skip_dead_branches:
             raise NotImplementedError("skip_dead_branches with a frame shard (the single-branch call has its own K/V exchange schedule)")
         latents = engine.transfer_loop(self, latents.to(device), text3, content_inv_latents, style_inv_latents, masks, n,
-                                       smoother=sm, callback=cb, skip_dead_branches=skip_dead_branches, shard=shard)
+                                       smoother=sm, callback=cb, skip_dead_branches=skip_dead_branches, shard=shard, static_style=static_style)
         if shard is not None and shard.rank != 0 and output_type != "latent":      # rank 0 decodes and writes; the others are done
             return StableDiffusionPipelineOutput(images=None) if return_dict else (None, None)
         return self._finish(latents, output_type, return_dict)

@@ -198,7 +198,11 @@ int univst_unet_query(univst_unet* h, const char* name, double* out) {
         return UV_OK;
     }
     if (model_query(h->impl, name, out)) return UV_OK;
-    if (!strcmp(name, "motion_active")) {        // AnimateDiff handles: the motion modules finalize found with a non-zero proj_out
+    if (!strcmp(name, "idx_tables")) {           // the (B, F) geometries whose K/V source tables are on the device (each uploaded once, at its first forward)
+        *out = (double)h->impl.idx_tables.size();
+        return UV_OK;
+    }
+    if (!strcmp(name, "motion_active")) {     // AnimateDiff handles: the motion modules finalize found with a non-zero proj_out
         *out = (double)h->impl.motion_active.size();
         return UV_OK;
     }
@@ -226,6 +230,44 @@ int univst_unet_forward_tap(univst_unet* h, const void* sample, float t, const v
     UV_REQUIRE(feat, "unet_forward_tap: feat_out must not be NULL (univst_unet_forward is the entry without a tap)");
     UV_REQUIRE(ft_index >= 0 && ft_index <= 3, "unet_forward_tap: ft_index %d outside 0..3", ft_index);
     return h->impl.forward(H(sample), t, H(text), B, F, Hh, W, text_len, pnp, HM(eps), HM(feat), ft_index, S(s), true);
+}
+int64_t univst_unet_style_bank_bytes(univst_unet* h, int Hh, int W) {
+    UV_REQUIRE(h && Hh >= 8 && W >= 8 && Hh % 8 == 0 && W % 8 == 0, "unet_style_bank_bytes: null handle or unsupported geometry H=%d W=%d (multiples of 8)", Hh, W);
+    return h->impl.style_bank_layout(Hh, W).back();
+}
+int univst_unet_style_bank(univst_unet* h, const void* sample, float t, const void* text, int Hh, int W, int text_len, const univst_pnp* pnp, void* bank,
+                           int64_t bank_bytes, int* active_out, void* s) {
+    UV_REQUIRE(h && sample && text && active_out, "unet_style_bank: null argument");
+    UV_RUN(h->impl.static_style_check("unet_style_bank"));
+    UV_REQUIRE(pnp && pnp->registered, "unet_style_bank: pnp is NULL or not registered: without the PnP key sources the frame's K | V rows are not the ones the shift wants");
+    UV_REQUIRE(Hh >= 8 && W >= 8 && Hh % 8 == 0 && W % 8 == 0, "unet_style_bank: unsupported geometry H=%d W=%d (multiples of 8)", Hh, W);
+    *active_out = UNet::pnp_window_active(false, pnp) ? 1 : 0;
+    if (!*active_out) return UV_OK;      // outside the window nothing reads the bank
+    const std::vector<long> off = h->impl.style_bank_layout(Hh, W);
+    UV_REQUIRE(off.size() > 1, "unet_style_bank: this configuration has no PnP layer");
+    UV_REQUIRE(bank, "unet_style_bank: the PnP window is open (idx %d) and bank is NULL", pnp->idx);
+    UV_REQUIRE(bank_bytes >= off.back(), "unet_style_bank: bank of %lld bytes, univst_unet_style_bank_bytes asks for %ld", (long long)bank_bytes, off.back());
+    UV_REQUIRE(((uintptr_t)bank & 15) == 0, "unet_style_bank: bank must be 16-byte aligned");
+    UNet::StyleBank sb;
+    sb.mode = UNet::StyleBank::WRITE;
+    sb.base = (char*)bank;
+    return h->impl.forward(H(sample), t, H(text), 1, 1, Hh, W, text_len, pnp, nullptr, nullptr, -1, S(s), false, &sb);
+}
+int univst_unet_forward_static_style(univst_unet* h, const void* sample, float t, const void* text, int F, int Hh, int W, int text_len, const univst_pnp* pnp,
+                                     const void* bank, int64_t bank_bytes, void* eps, void* s) {
+    UV_REQUIRE(h && sample && text && eps, "unet_forward_static_style: null argument");
+    UV_RUN(h->impl.static_style_check("unet_forward_static_style"));
+    if (!UNet::pnp_window_active(false, pnp))      // outside the window: the ordinary two-branch forward
+        return h->impl.forward(H(sample), t, H(text), 2, F, Hh, W, text_len, pnp, HM(eps), nullptr, -1, S(s));
+    UV_REQUIRE(Hh >= 8 && W >= 8 && Hh % 8 == 0 && W % 8 == 0, "unet_forward_static_style: unsupported geometry H=%d W=%d (multiples of 8)", Hh, W);
+    UV_REQUIRE(bank, "unet_forward_static_style: the PnP window is open (idx %d) and bank is NULL", pnp->idx);
+    const long need = h->impl.style_bank_layout(Hh, W).back();
+    UV_REQUIRE(bank_bytes >= need, "unet_forward_static_style: bank of %lld bytes, univst_unet_style_bank_bytes asks for %ld", (long long)bank_bytes, need);
+    UV_REQUIRE(((uintptr_t)bank & 15) == 0, "unet_forward_static_style: bank must be 16-byte aligned");
+    UNet::StyleBank sb;
+    sb.mode = UNet::StyleBank::READ;
+    sb.base = (char*)bank;
+    return h->impl.forward(H(sample), t, H(text), 2, F, Hh, W, text_len, pnp, HM(eps), nullptr, -1, S(s), false, &sb);
 }
 int univst_unet_set_comm(univst_unet* h, int rank, int world, void* comm_ws, int64_t comm_ws_bytes, univst_allreduce_fn ar,
                          univst_kv_exchange_fn kv, void* user) {
@@ -695,6 +737,12 @@ int univst_attention_adain_shift(void* qkv, int64_t ld, int F, int N, int C, flo
     UV_REQUIRE(qkv && ws, "adain_shift: null argument");
     float* w = (float*)ws;
     return uv_launch_adain_shift(HM(qkv), ld, F, N, C, w, w + (long)F * 2 * C, alpha, beta, gamma, S(s));
+}
+int univst_attention_adain_shift_static(void* qkv, int64_t ld, const void* style_kv, int64_t ld_style, int F, int N, int C, float alpha, float beta,
+                                        float gamma, void* ws, void* s) {
+    UV_REQUIRE(qkv && style_kv && ws, "adain_shift_static: null argument");
+    float* w = (float*)ws;
+    return uv_launch_adain_shift_static(HM(qkv), ld, H(style_kv), ld_style, F, N, C, w, w + 2L * C, alpha, beta, gamma, S(s));
 }
 int univst_latent_adain(const void* cnt, const void* sty, void* out, int C, int F, int HW, void* s) {
     UV_REQUIRE(cnt && sty && out, "latent_adain: null argument");

@@ -267,6 +267,9 @@ int uv_launch_tr16_probe(float* out, hipStream_t stream);
 int uv_launch_colstats(const half_t* x, long ld, int F, int N, int ncols, float* mean, float* stdv, hipStream_t stream);
 int uv_launch_adain_shift(half_t* qkv, long ld, int F, int N, int C, float* mean, float* stdv, float alpha, float beta,
                           float gamma, hipStream_t stream);
+// the shift on the two-branch buffer [2*F*N, >= 3C] (content, stylised) against ONE frame of style K | V rows [N, >= 2C]; mean / stdv: 2C floats each
+int uv_launch_adain_shift_static(half_t* qkv, long ld, const half_t* style_kv, long ld_style, int F, int N, int C, float* mean, float* stdv,
+                                 float alpha, float beta, float gamma, hipStream_t stream);
 int uv_launch_latent_adain(const half_t* cnt, const half_t* sty, half_t* out, int Cl, int F, int HW, hipStream_t stream);
 int uv_launch_latent_adain_stats(const half_t* cnt, float* st, int Cl, int F, int HW, hipStream_t stream);
 int uv_launch_latent_adain_apply(const half_t* cnt, const half_t* sty, const float* st, long n_total, half_t* out, int Cl, int F, int HW,

@@ -8,6 +8,8 @@
 // N tokens, and LN_C is the affine-free LayerNorm over the channel axis per (frame, token) — the
 // reference's F.instance_norm layout quirk, reproduced on purpose.
 // Replaces pnp_utils.py:44-57 + attention_adain :114-125, and latent_adain :128-139.
+// The static form (adain_shift_static_kernel) runs the same row arithmetic on a TWO-branch buffer (content, stylised) with K1 | V1 and their statistics taken
+// from ONE style frame held outside the buffer, for every frame f: the style of the SD path is a single image (DESIGN.md "Static style branch").
 #include "common.h"
 #include "kernels.h"
 
@@ -86,19 +88,13 @@ __global__ __launch_bounds__(256) void colstats_kernel(const half_t* __restrict_
     }
 }
 
+// One token row of the shift, one wave: row0 = the content branch's q | k | v row (only Q is read), row2 = the stylised branch's (rewritten in place),
+// sty = the style K | V of the same token (2C columns), mp / sp = the style's column mean / std of that frame (2C each).
 template <int MAXCH>
-__global__ __launch_bounds__(256) void adain_shift_kernel(half_t* __restrict__ qkv, long ld, int F, int N, int C,
-                                                          const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                          float alpha, float beta, float gamma) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long FN = (long)F * N;
-    if (r >= FN) return;
-    const int f = (int)(r / N);
+__device__ __forceinline__ void adain_shift_row(const half_t* __restrict__ row0, const half_t* __restrict__ sty, half_t* __restrict__ row2,
+                                                const float* __restrict__ mp0, const float* __restrict__ sp0, int C, int lane, float alpha,
+                                                float beta, float gamma) {
     const int nch = C / 8;
-    half_t* row0 = qkv + r * ld;
-    half_t* row1 = qkv + (FN + r) * ld;
-    half_t* row2 = qkv + (2 * FN + r) * ld;
     // Q
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
@@ -145,19 +141,45 @@ __global__ __launch_bounds__(256) void adain_shift_kernel(half_t* __restrict__ q
         for (int i = 0; i < MAXCH; ++i) {
             const int ch = lane + 64 * i;
             if (ch < nch) {
-                h8 sty = *reinterpret_cast<const h8*>(row1 + off + ch * 8);
-                const float* mp = mean + (long)f * 2 * C + t * C + ch * 8;
-                const float* sp = stdv + (long)f * 2 * C + t * C + ch * 8;
+                h8 st = *reinterpret_cast<const h8*>(sty + t * C + ch * 8);
+                const float* mp = mp0 + t * C + ch * 8;
+                const float* sp = sp0 + t * C + ch * 8;
                 h8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     float ad = ((float)x[i][e] - mu) * rstd * sp[e] + mp[e];
-                    o[e] = (half_t)(beta * ad + (1.f - beta) * (float)sty[e]);
+                    o[e] = (half_t)(beta * ad + (1.f - beta) * (float)st[e]);
                 }
                 *reinterpret_cast<h8*>(row2 + off + ch * 8) = o;
             }
         }
     }
+}
+
+template <int MAXCH>
+__global__ __launch_bounds__(256) void adain_shift_kernel(half_t* __restrict__ qkv, long ld, int F, int N, int C,
+                                                          const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                          float alpha, float beta, float gamma) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long FN = (long)F * N;
+    if (r >= FN) return;
+    const int f = (int)(r / N);
+    adain_shift_row<MAXCH>(qkv + r * ld, qkv + (FN + r) * ld + C, qkv + (2 * FN + r) * ld, mean + (long)f * 2 * C, stdv + (long)f * 2 * C, C, lane,
+                           alpha, beta, gamma);
+}
+
+// The same shift on a TWO-branch buffer (content rows, then stylised rows) whose style is one frame held elsewhere: every frame f reads the style
+// rows [N, >= 2C] (K | V) and their one set of column statistics — what F identical style frames give the three-branch kernel.
+template <int MAXCH>
+__global__ __launch_bounds__(256) void adain_shift_static_kernel(half_t* __restrict__ qkv, long ld, const half_t* __restrict__ style_kv,
+                                                                 long ld_style, int F, int N, int C, const float* __restrict__ mean,
+                                                                 const float* __restrict__ stdv, float alpha, float beta, float gamma) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long FN = (long)F * N;
+    if (r >= FN) return;
+    adain_shift_row<MAXCH>(qkv + r * ld, style_kv + (r % N) * ld_style, qkv + (FN + r) * ld, mean, stdv, C, lane, alpha, beta, gamma);
 }
 
 // latent_adain on [1,Cl,F,h,w] fp16: one block per channel.
@@ -334,6 +356,26 @@ int uv_launch_adain_shift(half_t* qkv, long ld, int F, int N, int C, float* mean
     if (nch <= 1) hipLaunchKernelGGL((adain_shift_kernel<1>), grid, block, 0, stream, qkv, ld, F, N, C, mean, stdv, alpha, beta, gamma);
     else if (nch == 2) hipLaunchKernelGGL((adain_shift_kernel<2>), grid, block, 0, stream, qkv, ld, F, N, C, mean, stdv, alpha, beta, gamma);
     else hipLaunchKernelGGL((adain_shift_kernel<4>), grid, block, 0, stream, qkv, ld, F, N, C, mean, stdv, alpha, beta, gamma);
+    uv_prof_end(stream);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+
+int uv_launch_adain_shift_static(half_t* qkv, long ld, const half_t* style_kv, long ld_style, int F, int N, int C, float* mean, float* stdv,
+                                 float alpha, float beta, float gamma, hipStream_t stream) {
+    UV_REQUIRE(F >= 1 && N >= 1, "adain_shift_static: F=%d N=%d must be positive", F, N);
+    UV_REQUIRE(C >= 8 && C % 8 == 0 && C <= 2048 && ld % 8 == 0 && ld_style % 8 == 0, "adain_shift_static: C=%d ld=%ld ld_style=%ld unsupported", C, ld,
+               ld_style);
+    UV_REQUIRE(ld >= 3L * C, "adain_shift_static: ld=%ld is less than the 3C=%ld columns of q | k | v", ld, 3L * C);
+    UV_REQUIRE(ld_style >= 2L * C, "adain_shift_static: ld_style=%ld is less than the 2C=%ld columns of the style k | v", ld_style, 2L * C);
+    uv_prof_begin(UV_CLS_ADAIN, 0.0, 2.0 * (double)F * N * C * 9.0 + 4.0 * N * C, stream);   // 4 reads + 3 writes + 2 style reads of [F,N,C] fp16 (the style rows from cache), the statistics pass over one frame
+    int rc = uv_launch_colstats(style_kv, ld_style, 1, N, 2 * C, mean, stdv, stream);
+    if (rc) return rc;
+    dim3 grid((unsigned)(((long)F * N + 3) / 4)), block(256);
+    const int nch = (C / 8 + 63) / 64;
+    if (nch <= 1) hipLaunchKernelGGL((adain_shift_static_kernel<1>), grid, block, 0, stream, qkv, ld, style_kv, ld_style, F, N, C, mean, stdv, alpha, beta, gamma);
+    else if (nch == 2) hipLaunchKernelGGL((adain_shift_static_kernel<2>), grid, block, 0, stream, qkv, ld, style_kv, ld_style, F, N, C, mean, stdv, alpha, beta, gamma);
+    else hipLaunchKernelGGL((adain_shift_static_kernel<4>), grid, block, 0, stream, qkv, ld, style_kv, ld_style, F, N, C, mean, stdv, alpha, beta, gamma);
     uv_prof_end(stream);
     UV_LAUNCH_CHECK();
     return UV_OK;

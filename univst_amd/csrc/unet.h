@@ -53,11 +53,23 @@ struct UNet : Model {
     unsigned emu_epoch = 0;
     int comm_streams();                          // creates the forked stream + events on first use
 
+    // Static style (include/univst.h univst_unet_style_bank): the style branch of the PnP step as ONE frame.  The bank is caller-owned device memory that
+    // holds, per PnP layer in graph order, the K | V rows [N_l, 2 C_l] fp16 of that frame, each layer's block starting on a 256-byte boundary.
+    struct StyleBank {
+        enum { WRITE = 1, READ = 2 };
+        int mode = 0;              // WRITE: the one-frame forward leaves its K | V rows and stops behind the last PnP layer; READ: the B = 2 forward shifts against them
+        char* base = nullptr;
+    };
+    std::vector<long> style_bank_layout(int H, int W) const;       // byte offset of every PnP layer's block, then the total
+    int static_style_check(const char* entry) const;                 // the handles the static style is refused on (UV_ERR_UNSUPPORTED), by name
+
     UNet() : Model("unet") {}
     ~UNet();
     int load_tensor(const char* key, const void* dev_ptr, int dtype, const int64_t* shape, int ndim, hipStream_t s);
     int finalize(hipStream_t s);
     int reserve(int B, int F, int H, int W);
     int forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int W, int text_len,
-                const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s, bool tap_entry = false);
+                const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s, bool tap_entry = false,
+                const StyleBank* bank = nullptr);
+    static bool pnp_window_active(bool animatediff, const univst_pnp* pnp);      // registered and idx inside the shift window of that backbone
 };

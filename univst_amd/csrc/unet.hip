@@ -163,9 +163,47 @@ __global__ __launch_bounds__(256) void temporal_attn_kernel(const half_t* __rest
     }
 }
 
+// the decoder attn1 layers that carry the PnP forward: [up block][attention] (pnp_utils.py:104-111)
+const int kPnpLayers[4][3] = {{0, 0, 0}, {0, 1, 1}, {1, 1, 1}, {1, 1, 1}};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ handle
+bool UNet::pnp_window_active(bool animatediff, const univst_pnp* pnp) {
+    if (!pnp || !pnp->registered) return false;
+    // AnimateDiff's closure (pnp_utils.py:45 of that backbone): eta1 * 50 <= idx < eta2 * 50, evaluated in double as Python does
+    return animatediff ? (double)pnp->idx >= (double)pnp->eta1 * 50.0 && (double)pnp->idx < (double)pnp->eta2 * 50.0
+                       : pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f;
+}
+
+std::vector<long> UNet::style_bank_layout(int H, int Wd) const {
+    std::vector<long> off;
+    long at = 0;
+    for (int i = 1; i < 4; ++i)                                    // up_blocks.i runs on level 3 - i
+        for (int j = 0; j < cfg.layers_per_block + 1 && j < 3; ++j) {
+            if (!kPnpLayers[i][j]) continue;
+            off.push_back(at);
+            const long N = (long)(H >> (3 - i)) * (Wd >> (3 - i));
+            at += (N * 2 * cfg.block_out_channels[3 - i] * (long)sizeof(half_t) + 255) & ~255L;
+        }
+    off.push_back(at);
+    return off;
+}
+
+int UNet::static_style_check(const char* entry) const {
+    const char* why = animatediff ? "the AnimateDiff UNet: the motion modules' position encoding makes identical frames differ"
+                      : !temporal_conv_active.empty() || !temporal_attn_active.empty()
+                          ? "a checkpoint with trained temporal layers: they couple the frames, so a repeated style frame does not give identical frames"
+                      : world > 1 || native_comm ? "a handle with a communicator attached: the halo phase of a frame shard shifts against the style's hidden rows"
+                                                 : nullptr;
+    if (why) {
+        uv_set_error("%s: the static style is not available on %s", entry, why);
+        return UV_ERR_UNSUPPORTED;
+    }
+    UV_REQUIRE(finalized, "%s: call univst_unet_finalize after loading weights", entry);
+    return UV_OK;
+}
+
 UNet::~UNet() {
     for (auto& kv : idx_tables) (void)hipFree(kv.second);
     if (d_counter) (void)hipFree(d_counter);
@@ -607,6 +645,11 @@ struct Fwd {
     float* ad_ws = nullptr;
     float* gst_pool = nullptr;     // bump region for the producers' GroupNorm statistics (never reused inside a forward)
     size_t gst_left = 0;           // floats
+    // static style (UNet::StyleBank): the bank of this call, its layers' byte offsets, the next PnP layer, and "the last layer has left its rows"
+    const UNet::StyleBank* sb = nullptr;
+    std::vector<long> sb_off;
+    size_t sb_layer = 0;
+    bool sb_done = false;
 
     float* gst_take(long rows, int C) {   // [C/10][rows/16][2] floats, or null (pool exhausted / switched off: the consumer runs its own pass)
         const size_t n = (size_t)(rows / 16) * (C / 10) * 2;
@@ -909,11 +952,10 @@ struct Fwd {
         k.qs2 = u.find(b + ".attn2.to_q.weight#qs") != nullptr;
         k.wq2 = b + (k.qs2 ? ".attn2.to_q.weight#qs" : ".attn2.to_q.weight");
         k.registered = pnp_layer && pnp && pnp->registered;
-        // AnimateDiff's closure (pnp_utils.py:45 of that backbone): eta1 * 50 <= idx < eta2 * 50, evaluated in double as Python does
-        k.shift = k.registered && (u.animatediff ? (double)pnp->idx >= (double)pnp->eta1 * 50.0 && (double)pnp->idx < (double)pnp->eta2 * 50.0
-                                                  : pnp->idx >= pnp->eta1 && pnp->idx <= pnp->eta2 * 50.f);
+        // (the one-frame style call never shifts: the reference only ever modifies chunk 2, pnp_utils.py:53-57)
+        k.shift = k.registered && UNet::pnp_window_active(u.animatediff, pnp) && !(sb && sb->mode == UNet::StyleBank::WRITE);
         if (k.shift) {
-            UV_REQUIRE(B == 3, "PnP attention shift needs the three-branch batch (B=3), got B=%d", B);
+            UV_REQUIRE(B == 3 || (sb && B == 2), "PnP attention shift needs the three-branch batch (B=3), got B=%d", B);
             k.beta = (0.9f - 0.1f) / (pnp->eta1 * 50.f - pnp->eta2 * 50.f) * ((float)pnp->idx - pnp->eta2 * 50.f) + 0.1f;
         }
         // The row-local chain behind the self-attention: to_out + residual -> (norm2) -> attn2 -> to_out + residual -> (norm3) ->
@@ -997,7 +1039,22 @@ struct Fwd {
         LinOpt lq;
         lq.ln_in = k.lnst;      // (set when `fold`: the linear then reads the raw rows)
         UV_RUN(linear(k.fold ? k.h : k.t0, C, rows, C, k.fold ? k.wqkv + "#ln" : k.wqkv, "", 3 * C, qkv, 3 * C, lq));
-        if (k.shift) UV_RUN(uv_launch_adain_shift(qkv, 3 * C, F, N, C, ad_ws, ad_ws + (long)F * 2 * C, pnp->alpha, k.beta, pnp->gamma, s));
+        if (k.registered && sb) {      // static style: this layer's K | V rows of the one style frame go to the bank, or the shift reads them from there
+            UV_REQUIRE(sb_layer + 1 < sb_off.size(), "static style: more PnP layers in the graph than the bank's layout has");
+            half_t* slot = (half_t*)(sb->base + sb_off[sb_layer++]);
+            if (sb->mode == UNet::StyleBank::WRITE) {
+                UV_HIP(hipMemcpy2DAsync(slot, 2L * C * sizeof(half_t), qkv + C, 3L * C * sizeof(half_t), 2L * C * sizeof(half_t), (size_t)N,
+                                        hipMemcpyDeviceToDevice, s));
+                if (sb_layer + 1 == sb_off.size()) {      // nothing behind the last PnP layer's projection is wanted (the style's eps is discarded)
+                    sb_done = true;
+                    return UV_OK;
+                }
+            } else if (k.shift) {
+                UV_RUN(uv_launch_adain_shift_static(qkv, 3 * C, slot, 2 * C, F, N, C, ad_ws, ad_ws + 2L * C, pnp->alpha, k.beta, pnp->gamma, s));
+            }
+        } else if (k.shift) {
+            UV_RUN(uv_launch_adain_shift(qkv, 3 * C, F, N, C, ad_ws, ad_ws + (long)F * 2 * C, pnp->alpha, k.beta, pnp->gamma, s));
+        }
         AttnParams ap;
         ap.q = qkv; ap.k = qkv + C; ap.v = qkv + 2 * C;
         ap.ldq = ap.ldkv = 3 * C;
@@ -1223,6 +1280,7 @@ struct Fwd {
         UV_RUN(decide(k, pnp_layer));
         UV_RUN(proj_in(k));
         UV_RUN(attn1(k));
+        if (sb_done) return UV_OK;      // (the style bank is complete: the call ends here, the arena is reset by the next one)
         UV_RUN(chain_begin(k));
         Band r;
         r.imgs = x.imgs / k.nbands;
@@ -1288,7 +1346,7 @@ struct Fwd {
 };
 
 int UNet::forward(const half_t* sample, float timestep, const half_t* text, int B, int F, int H, int Wd, int text_len,
-                  const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s, bool tap_entry) {
+                  const univst_pnp* pnp, half_t* eps_out, half_t* feat_out, int ft_index, hipStream_t s, bool tap_entry, const StyleBank* bank) {
     UV_REQUIRE(finalized, "forward: call univst_unet_finalize after loading weights");
     UV_REQUIRE(world == 1 || (temporal_conv_active.empty() && temporal_attn_active.empty()),
                "forward: trained temporal layers couple all frames of a pixel; frame sharding (world=%d) is not supported with them", world);
@@ -1311,6 +1369,10 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
     const int C0 = boc[0], L = cfg.layers_per_block;
     Fwd f{*this, s, B, F, text_len, pnp};
     f.text = text;
+    if (bank) {
+        f.sb = bank;
+        f.sb_off = style_bank_layout(H, Wd);
+    }
     UV_RUN(f.workspaces(idx_tables[((long)B << 20) | F | ((long)rank << 40) | ((long)world << 50)], H, Wd));
     UV_RUN(f.time_embedding(timestep));
     // ---- conv_in
@@ -1367,7 +1429,6 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
         x = w;   // previous x is skips.back(), still owned by the skip list
     }
     // ---- up
-    static const int pnp_layers[4][3] = {{0, 0, 0}, {0, 1, 1}, {1, 1, 1}, {1, 1, 1}};   // pnp_utils.py:104-111
     for (int i = 0; i < 4; ++i) {
         const std::string p = "up_blocks." + std::to_string(i);
         const int Cout = boc[3 - i];
@@ -1382,7 +1443,8 @@ int UNet::forward(const half_t* sample, float timestep, const half_t* text, int 
             x = y;
             if (has_attn) {
                 Act z;
-                UV_RUN(f.transformer(p + ".attentions." + std::to_string(j), x, j < 3 && pnp_layers[i][j], cfg.attention_heads[3 - i], &z));
+                UV_RUN(f.transformer(p + ".attentions." + std::to_string(j), x, j < 3 && kPnpLayers[i][j], cfg.attention_heads[3 - i], &z));
+                if (f.sb_done) return missing.empty() ? UV_OK : missing_error("unet");
                 f.free(x.p);
                 x = z;
             }

@@ -65,11 +65,23 @@ def _dev16(t, device):
     return t.to(device=device, dtype=torch.float16).contiguous()
 
 
+def style_inv_frames(t: torch.Tensor, frames: int, static_style: bool) -> torch.Tensor:
+    """A style inversion latent as the loop wants it.  The files hold [1,4,F,h,w] (the image repeated F times, ddim_inversion.py:45-65) or
+    [1,4,1,h,w] (run_style_inversion_sd.py --static_style); the static loop takes ONE frame (frame 0 of an F-frame entry), the three-branch
+    loop F frames (a one-frame entry as F copies)."""
+    if t.dim() != 5 or t.shape[2] not in (1, frames):
+        raise ValueError(f"style inversion latent of shape {tuple(t.shape)}: expected [1,4,{frames},h,w] or [1,4,1,h,w]")
+    if static_style:
+        return t[:, :, :1].contiguous()
+    return t if t.shape[2] == frames else t.expand(-1, -1, frames, -1, -1).contiguous()
+
+
 def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv: Sequence[torch.Tensor],
                   style_inv: Sequence[torch.Tensor], mask_u8: Optional[torch.Tensor], num_inference_steps: int = 50,
                   smoother: Optional[Callable] = None, callback: Optional[Callable] = None,
                   skip_dead_branches: bool = False, shard=None, *, adain_from_inclusive: bool = False,
-                  register_time_fn: Optional[Callable] = None, pnp_window_closed: Optional[Callable] = None) -> torch.Tensor:
+                  register_time_fn: Optional[Callable] = None, pnp_window_closed: Optional[Callable] = None,
+                  static_style: bool = False) -> torch.Tensor:
     """stable_diffusion.py:680-766 of the reference, device-resident; with the three keyword-only parameters also
     animatediff/pipelines/pipeline_animation.py:503-591.
 
@@ -88,6 +100,12 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
     pnp_window_closed  ``(i, eta2) -> bool``, the test ``skip_dead_branches`` uses for "the PnP window is closed at step i";
                     default ``i > eta2 * 50`` (the SD closure's window is inclusive at the top), the AnimateDiff closure's
                     exclusive window takes ``i >= eta2 * 50``
+    static_style    the style is ONE image (the SD path repeats it F times: ddim_inversion.py:45-65): its branch runs as one frame.  A
+                    ``style_inv`` entry of one frame ([1,4,1,h,w]) is used as is, of an F-frame entry frame 0 is taken.  Inside the PnP
+                    window a step is ``unet.style_bank`` (one frame) + ``unet.forward_static_style`` (content, stylised); outside it the
+                    two-branch ``forward`` (with ``skip_dead_branches`` the single branch, as without this switch).  ``latent_adain`` gets
+                    the frame expanded to F frames.  Valid only where identical frames give identical results: the native UNet refuses
+                    trained temporal layers; with a shard this raises.  Off by default.
     shard           optional ``parallel.FrameShard`` already attached to ``pipe.unet`` (one process per GPU):
                     every argument is the FULL clip on every rank; this rank runs its frames of all three branches and the
                     full stylised latents come back on every rank (all-gather at the end).  The smoother is sequential over
@@ -100,6 +118,8 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
     sched.set_timesteps(n)
     reg_time = register_time if register_time_fn is None else register_time_fn
     closed = (lambda i, e2: i > e2 * 50) if pnp_window_closed is None else pnp_window_closed
+    if static_style and shard is not None:
+        raise NotImplementedError("transfer_loop: static_style is not built for a frame shard (shard must be None)")
     sharded = shard is not None and shard.world > 1
     if sharded and latents.shape[2] != shard.frames:
         raise ValueError(f"transfer_loop: the shard was built for {shard.frames} frames, the clip has {latents.shape[2]}")
@@ -108,6 +128,9 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
     text3 = _dev16(text3, dev)
     cinv = [cut(_dev16(t, dev)) for t in content_inv]
     sinv = [cut(_dev16(t, dev)) for t in style_inv]
+    if not sharded:
+        sinv = [style_inv_frames(t, latents.shape[2], static_style) for t in sinv]
+    bank = None
     adain = shard.latent_adain if sharded else latent_adain
     m = None
     if mask_u8 is not None:
@@ -126,10 +149,15 @@ def transfer_loop(pipe, latents: torch.Tensor, text3: torch.Tensor, content_inv:
         if m is not None and i <= 0.9 * n:
             latents = _native.mask_blend(latents, c_t, m)
         if (i >= 0.8 * n if adain_from_inclusive else i > 0.8 * n) and i <= 0.9 * n:
-            latents = _native.mask_blend(adain(latents, s_t), c_t, m)
+            s_f = s_t.expand(-1, -1, latents.shape[2], -1, -1).contiguous() if static_style else s_t
+            latents = _native.mask_blend(adain(latents, s_f), c_t, m)
         reg_time(pipe, i)
         if skip_dead_branches and closed(i, eta2):
             eps = _unet_single_branch(unet, latents, t, text3[2:3])
+        elif static_style:
+            live = unet.style_bank(s_t, t, text3[1:2], bank=bank)      # None outside the window: the two-branch forward then
+            bank = live if live is not None else bank                  # (one buffer for the whole loop)
+            eps = unet.forward_static_style(torch.cat([c_t, latents]), t, text3[::2].contiguous(), live).sample[1:2]
         else:
             x = torch.cat([c_t, s_t, latents])
             eps = unet(x, t, encoder_hidden_states=text3).sample[2:3]

@@ -20,7 +20,9 @@ def main(a):
     os.makedirs(inv, exist_ok=True)
     os.makedirs(rec, exist_ok=True)
     with torch.no_grad():
-        style_inversion_reconstruction(pipe, inv_sched, a.style_path, inv, rec, a.num_frames, a.height, a.width, a.time_steps,
+        # --static_style: the style is one image, so ONE frame is inverted (F identical frames give F identical trajectories with 2-D-initialised
+        # temporal layers); the files keep their names and hold [1,4,1,h,w], which run_video_style_transfer_sd.py takes as well as [1,4,F,h,w]
+        style_inversion_reconstruction(pipe, inv_sched, a.style_path, inv, rec, 1 if a.static_style else a.num_frames, a.height, a.width, a.time_steps,
                                        a.weight_dtype, is_opt=a.is_opt, reconstruct=not a.skip_reconstruction)
 
 
@@ -33,6 +35,8 @@ def parser():
     p.add_argument("--width", type=int, default=512)
     p.add_argument("--is_opt", action="store_true", help="use Easy-Inv")
     p.add_argument("--skip_reconstruction", action="store_true")
+    p.add_argument("--static_style", action="store_true",
+                   help="extra: invert ONE frame instead of --num_frames copies of the image; ddim_latents_{k}.pt are then [1,4,1,h,w]")
     return p
 
 

@@ -44,12 +44,14 @@ def main(a):
     pipe, _ = build_pipeline(a.pretrained_model_path, a.weight_dtype)
     content_noise = load_ddim_latents_at_t(a.time_steps, ddim_latents_path=a.content_inv_path).to(a.weight_dtype).cuda()
     style_noise = load_ddim_latents_at_t(a.time_steps, ddim_latents_path=a.style_inv_path).to(a.weight_dtype).cuda()
+    if style_noise.shape[2] == 1 and content_noise.shape[2] > 1:           # a one-frame style inversion (run_style_inversion_sd.py --static_style)
+        style_noise = style_noise.expand(-1, -1, content_noise.shape[2], -1, -1).contiguous()
     latents = latent_adain(content_noise, style_noise)                     # init latent-shift
     register_spatial_attention_pnp(pipe)                                   # PnP: AdaIN-guided attention injection
     sample = pipe.video_style_transfer("", latents=latents, num_inference_steps=a.time_steps,
                                        content_inv_path=a.content_inv_path, style_inv_path=a.style_inv_path,
                                        mask_path=a.mask_path or None, skip_dead_branches=a.skip_dead_branches,
-                                       shard=False if a.no_shard else None, **smoother_kwargs(a, pipe, latents.shape[2], latents.shape[-2:])).images
+                                       shard=False if a.no_shard else None, static_style=a.static_style, **smoother_kwargs(a, pipe, latents.shape[2], latents.shape[-2:])).images
     if sample is None:            # ranks > 0 of a frame-sharded run: rank 0 decodes and writes
         return
     sample = sample.permute(0, 4, 1, 2, 3).contiguous()
@@ -66,6 +68,9 @@ def parser():
     p.add_argument("--output_path", type=str, default="results/stylizations")
     p.add_argument("--skip_dead_branches", action="store_true",
                    help="extra: drop the content/style branches once the PnP window is closed (identical output)")
+    p.add_argument("--static_style", action="store_true",
+                   help="extra: run the style branch as ONE frame (the style is a single image): --style_inv_path may hold [1,4,1,h,w] latents "
+                        "(run_style_inversion_sd.py --static_style) or F-frame ones, of which frame 0 is taken; not with frame sharding")
     p.add_argument("--smoother", choices=["none", "pixel", "latent"], default="none",
                    help="extra: sliding-window optical-flow smoothing on steps 20..24 (stable_diffusion.py:713-759; the reference hard-wires None)")
     p.add_argument("--content_path", type=str, default="", help="content frames (folder / .mp4) for --smoother latent")

@@ -142,6 +142,25 @@ def test_chunked_attention(nat, h, w, budget, last):
     _hold(f"chunked_encode_{h}x{w}", mom, sd, x, cfg, R.encode_moments, max_abs_diff_from_unchunked=d_enc)
 
 
+def test_encoder_is_the_temporal_vae_encoder_bit_for_bit(nat):
+    """the native twin of tests/test_klvae_ref.py::test_encoder_equals_the_temporal_vae_encoder: a NativeTemporalVAE and a NativeAutoencoderKL
+    (use_quant_conv) with the same encoder.* and quant_conv.* tensors give the same moments, bit for bit — both handles run one encoder.  SMALL's
+    widths, 2 images of 64 x 64 pixels: an 8 x 8 latent, 64 attention tokens, one chunk."""
+    from univst_amd import synth, vae
+    tcfg = dict(synth.SVD_VAE_CONFIG, block_out_channels=SMALL["block_out_channels"])
+    tsd = synth.vae_state_dict(tcfg, seed=13)
+    shared = {k: t for k, t in tsd.items() if k.startswith(("encoder.", "quant_conv."))}
+    ksd = {**synth.klvae_state_dict(V15, seed=14), **shared}
+    assert len(shared) > 0 and all(k in ksd and ksd[k].shape == t.shape for k, t in shared.items())
+    assert set(k for k in ksd if k.startswith(("encoder.", "quant_conv."))) == set(shared)
+    t, k = vae.NativeTemporalVAE(tsd, tcfg), vae.NativeAutoencoderKL(ksd, V15)
+    x = _img(2, 64, 64, seed=8)
+    want, got = t.encode(x).latent_dist.parameters, k.encode(x).latent_dist.parameters
+    assert k.query("attn_chunks") == 1 and k.query("passes") == 1
+    assert got.shape == want.shape == (2, 8, 8, 8) and torch.isfinite(got.float()).all() and got.float().abs().max().item() > 0
+    assert torch.equal(got, want)
+
+
 def test_passes_over_images(nat):
     """3 images under a pass_bytes that holds 2: two groups, the last one ragged; the budget is read from a handle that ran 2 images (its arena is sized
     from the group), so the test does not restate the library's formula"""

@@ -1,6 +1,7 @@
 // Internal launcher interface shared by the kernel translation units, the UNet graph and the C ABI.
 #pragma once
 #include "common.h"
+#include "model.h"
 #include <initializer_list>
 #include <string>
 
@@ -95,6 +96,25 @@ inline GemmParams lin_params(const half_t* X, long M, int K, const half_t* W, in
     g.geglu = geglu;
     g.partial = ws;
     g.partial_bytes = ws_bytes;
+    return g;
+}
+
+// The geometry of an NHWC implicit-GEMM conv (mode 1) over `a`, or over the virtual channel concat a ++ b: 1x1, or 3x3 with padding 1 (taps = 1 / 9),
+// at `stride` over the source enlarged by nearest x(1 << up).  pad_end: the 3x3 window over an input padded at the bottom / right only (the VAE
+// encoder's stride-2 conv; taps = 9).  The conv twin of lin_params: it fills X, C1, Hs, Ws, X2, C2, up, stride, taps, (pad_end: tapw, pady, padx,) Ho, Wo, M, K and
+// nothing else — the weight layout, the epilogue and the output stay with the graph that launches it.
+inline GemmParams conv_params(const Act& a, const Act* b, int taps, int stride = 1, int up = 0, bool pad_end = false) {
+    GemmParams g;
+    g.X = a.p; g.C1 = a.C; g.Hs = a.H; g.Ws = a.W;
+    g.X2 = b ? b->p : nullptr; g.C2 = b ? b->C : 0;
+    g.up = up; g.stride = stride; g.taps = taps;
+    const int He = a.H << up, We = a.W << up;
+    const int pad = pad_end ? 1 : 2;      // rows / columns of padding in all
+    if (pad_end) { g.tapw = 3; g.pady = g.padx = 0; }
+    g.Ho = (taps == 9) ? (He + pad - 3) / stride + 1 : He;
+    g.Wo = (taps == 9) ? (We + pad - 3) / stride + 1 : We;
+    g.M = a.imgs * g.Ho * g.Wo;
+    g.K = taps * (g.C1 + g.C2);
     return g;
 }
 

@@ -756,14 +756,8 @@ struct Fwd {
         return UV_OK;
     }
     int conv(const Act& a, const Act* b, const std::string& p, int Cout, int taps, Act* out, const ConvOpt& o = ConvOpt()) {
-        GemmParams g;
-        g.X = a.p; g.C1 = a.C; g.Hs = a.H; g.Ws = a.W;
-        g.X2 = b ? b->p : nullptr; g.C2 = b ? b->C : 0;
-        g.up = o.up; g.stride = o.stride; g.taps = taps;
-        const int He = a.H << o.up, We = a.W << o.up;
-        g.Ho = (taps == 9) ? (He + 2 - 3) / o.stride + 1 : He;
-        g.Wo = (taps == 9) ? (We + 2 - 3) / o.stride + 1 : We;
-        g.M = a.imgs * g.Ho * g.Wo; g.N = Cout; g.K = taps * (g.C1 + g.C2);
+        GemmParams g = conv_params(a, b, taps, o.stride, o.up);
+        g.N = Cout;
         g.korder = (taps == 9 && g.C1 % 64 == 0 && g.C2 % 64 == 0 && u.find(p + ".weight#ti")) ? 1 : 0;
         g.W = W(p + (g.korder ? ".weight#ti" : ".weight#nhwc"));
         if (taps == 9 && o.stride == 1 && u.find(p + ".weight#t32")) g.W32 = W(p + ".weight#t32");

@@ -14,6 +14,8 @@ struct Vae : Model {
 
     Vae() : Model("vae") {}
     int finalize(hipStream_t s);
+    // the arena formula of both handles: `wide` = the widest channel count at the full resolution, score_rows = the query rows of one attention chunk
+    size_t arena_need(long imgs, int H, int W, int wide, long score_rows) const;
     int reserve(long imgs, int H, int W);
     int decode(const half_t* z, long imgs, int num_frames, int h, int w, half_t* out, hipStream_t s);
     int encode(const half_t* x, long imgs, int H, int W, half_t* moments, hipStream_t s);
@@ -32,6 +34,5 @@ struct KlVae : Vae {
     int encode(const half_t* x, long imgs, int H, int W, half_t* moments, hipStream_t s);
 
   private:
-    int decode_pass(const half_t* z, long imgs, int h, int w, half_t* out, hipStream_t s);
-    int encode_pass(const half_t* x, long imgs, int H, int W, half_t* moments, hipStream_t s);
+    int decode_pass(const half_t* z, long imgs, int h, int w, half_t* out, hipStream_t s);      // one group (an encode pass is VFwd::encoder itself)
 };

@@ -184,27 +184,8 @@ struct VFwd {
     // 2-D conv on [imgs, H, W, C]; asym: the encoder's stride-2 conv (input padded at the bottom / right only)
     // ldy > Cout (the plain VAE's post_quant_conv in front of a conv that reads channels padded to 8): rows of ldy halfs, the columns behind Cout zero
     int conv(const Act& a, const std::string& p, int Cout, int taps, int stride, int up, bool asym, const half_t* R, Act* out, int ldy = 0) {
-        GemmParams g;
-        g.X = a.p;
-        g.C1 = a.C;
-        g.Hs = a.H;
-        g.Ws = a.W;
-        g.up = up;
-        g.stride = stride;
-        g.taps = taps;
-        const int He = a.H << up, We = a.W << up;
-        if (asym) {
-            g.tapw = 3;
-            g.pady = g.padx = 0;
-            g.Ho = (He + 1 - 3) / stride + 1;
-            g.Wo = (We + 1 - 3) / stride + 1;
-        } else {
-            g.Ho = taps == 9 ? (He + 2 - 3) / stride + 1 : He;
-            g.Wo = taps == 9 ? (We + 2 - 3) / stride + 1 : We;
-        }
-        g.M = a.imgs * g.Ho * g.Wo;
+        GemmParams g = conv_params(a, nullptr, taps, stride, up, asym);
         g.N = Cout;
-        g.K = taps * a.C;
         g.korder = (taps == 9 && !asym && stride == 1 && a.C % 64 == 0 && u.find(p + ".weight#ti")) ? 1 : 0;
         g.W = W(p + (g.korder ? ".weight#ti" : ".weight#nhwc"));
         g.bias = W(p + ".bias");
@@ -248,19 +229,7 @@ struct VFwd {
         return uv_launch_gemm(g, 1, s);
     }
     int linear(const half_t* X, long M, int K, const half_t* Wt, const half_t* bias, int N, half_t* Y, const half_t* R = nullptr) {
-        GemmParams g;
-        g.X = X;
-        g.ldx = K;
-        g.M = (int)M;
-        g.K = K;
-        g.N = N;
-        g.W = Wt;
-        g.bias = bias;
-        g.Y = Y;
-        g.ldy = N;
-        g.R = R;
-        g.ldr = N;
-        return uv_launch_gemm(g, 0, s);
+        return uv_launch_gemm(lin_params(X, M, K, Wt, N, Y, bias, R), 0, s);
     }
     // diffusers ResnetBlock2D without a time embedding: GroupNorm (per image) + SiLU -> conv -> GroupNorm + SiLU -> conv, + (1x1 conv of) the input
     int resnet2d(const std::string& p, const Act& x, int Cout, Act* out) {
@@ -371,75 +340,118 @@ struct VFwd {
         free(gn);
         return UV_OK;
     }
+
+    // ---- the walks.  The arena is first-fit, so where a buffer is taken and given back is part of the graph: a stage takes what it needs, then its
+    // input is released
+    // one step of a walk: stage(&y) runs on `cur` into a fresh y, cur's buffer is released, cur = y
+    template <class Stage>
+    int step(Act& cur, Stage stage) {
+        Act nxt;
+        UV_RUN(stage(&nxt));
+        free(cur.p);
+        cur = nxt;
+        return UV_OK;
+    }
+    int take_gn_ws(long imgs) {
+        gn_ws = (float*)u.arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, u.cfg.norm_num_groups) * 4);
+        return gn_ws ? UV_OK : UV_ERR_STATE;
+    }
+    // the caller's [imgs, C, H, W] as NHWC rows with the channels zero padded to 8
+    int load_nchw(const half_t* src, long imgs, int C, int H, int Wd, Act* out) {
+        const int Cp = (C + 7) / 8 * 8;
+        *out = Act{alloc(imgs * H * Wd * Cp), (int)imgs, H, Wd, Cp};
+        if (!out->p) return UV_ERR_STATE;
+        return uv_launch_ncfhw_to_nhwc(src, out->p, (int)imgs, C, 1, H * Wd, Cp, s);
+    }
+    // the end of the encoder and of the decoder: GroupNorm + SiLU + conv_out.  Not a step: cur goes back as soon as it is normalised, before the conv takes its output
+    int norm_conv_out(const std::string& side, Act& cur, int Cout) {
+        Act na{alloc(cur.rows() * cur.C), cur.imgs, cur.H, cur.W, cur.C};
+        if (!na.p) return UV_ERR_STATE;
+        UV_RUN(groupnorm(cur, (long)cur.H * cur.W, side + ".conv_norm_out", 1, na.p));
+        free(cur.p);
+        UV_RUN(conv(na, side + ".conv_out", Cout, 9, 1, 0, false, nullptr, &cur));
+        free(na.p);
+        return UV_OK;
+    }
+    // The encoder of both handles (it has no temporal layer): x [imgs, in_channels, H, W] -> moments [imgs, 2*latent, H/8, W/8].  quant_conv: the 1x1 conv
+    // behind conv_out runs (the temporal VAE always has it, the plain one by its config); score_bytes / chunks: the attention's (0 / null: one chunk)
+    int encoder(const half_t* xin, long imgs, int H, int Wd, half_t* moments, bool quant_conv, long score_bytes, long* chunks) {
+        const int* boc = u.cfg.block_out_channels;
+        const int L2 = 2 * u.cfg.latent_channels;
+        UV_RUN(take_gn_ws(imgs));
+        Act cur;
+        UV_RUN(load_nchw(xin, imgs, u.cfg.in_channels, H, Wd, &cur));
+        UV_RUN(step(cur, [&](Act* y) { return conv(cur, "encoder.conv_in", boc[0], 9, 1, 0, false, nullptr, y); }));
+        for (int b = 0; b < 4; ++b) {
+            const std::string down = "encoder.down_blocks." + std::to_string(b);
+            for (int l = 0; l < u.cfg.layers_per_block; ++l)
+                UV_RUN(step(cur, [&](Act* y) { return resnet2d(down + ".resnets." + std::to_string(l), cur, boc[b], y); }));
+            if (b < 3) UV_RUN(step(cur, [&](Act* y) { return conv(cur, down + ".downsamplers.0.conv", boc[b], 9, 2, 0, true, nullptr, y); }));
+        }
+        UV_RUN(step(cur, [&](Act* y) { return resnet2d("encoder.mid_block.resnets.0", cur, boc[3], y); }));
+        UV_RUN(step(cur, [&](Act* y) { return attention("encoder.mid_block.attentions.0", cur, y, score_bytes, chunks); }));
+        UV_RUN(step(cur, [&](Act* y) { return resnet2d("encoder.mid_block.resnets.1", cur, boc[3], y); }));
+        UV_RUN(norm_conv_out("encoder", cur, L2));
+        if (quant_conv) UV_RUN(step(cur, [&](Act* y) { return conv(cur, "quant_conv", L2, 1, 1, 0, false, nullptr, y); }));
+        UV_RUN(uv_launch_nhwc_to_ncfhw(cur.p, L2, moments, (int)imgs, L2, 1, cur.H * cur.W, s));
+        free(cur.p);
+        free(gn_ws);
+        return UV_OK;
+    }
+    // The decoder of both handles from conv_in through conv_out, on cur = the latents as NHWC rows (channels padded to 8); cur leaves as conv_out's
+    // rows.  F > 0: the temporal decoder on clips of F frames (ST-resblocks; MidBlockTemporalDecoder.forward zips resnets[1:] with its ONE attention, so
+    // resnets[1] runs behind it only where layers_per_block >= 2).  F == 0: the plain one (ResnetBlock2D; UNetMidBlock2D always has resnets[1]).
+    int decoder(Act& cur, int F, long score_bytes, long* chunks) {
+        const int* boc = u.cfg.block_out_channels;
+        auto resblock = [&](const std::string& p, int Cout, Act* y) { return F > 0 ? st_resblock(p, cur, F, Cout, y) : resnet2d(p, cur, Cout, y); };
+        UV_RUN(step(cur, [&](Act* y) { return conv(cur, "decoder.conv_in", boc[3], 9, 1, 0, false, nullptr, y); }));
+        UV_RUN(step(cur, [&](Act* y) { return resblock("decoder.mid_block.resnets.0", boc[3], y); }));
+        UV_RUN(step(cur, [&](Act* y) { return attention("decoder.mid_block.attentions.0", cur, y, score_bytes, chunks); }));
+        if (F == 0 || u.cfg.layers_per_block >= 2) UV_RUN(step(cur, [&](Act* y) { return resblock("decoder.mid_block.resnets.1", boc[3], y); }));
+        for (int b = 0; b < 4; ++b) {
+            const int Cout = boc[3 - b];
+            const std::string up = "decoder.up_blocks." + std::to_string(b);
+            for (int l = 0; l < u.cfg.layers_per_block + 1; ++l)
+                UV_RUN(step(cur, [&](Act* y) { return resblock(up + ".resnets." + std::to_string(l), Cout, y); }));
+            if (b < 3) UV_RUN(step(cur, [&](Act* y) { return conv(cur, up + ".upsamplers.0.conv", Cout, 9, 1, 1, false, nullptr, y); }));
+        }
+        return norm_conv_out("decoder", cur, u.cfg.out_channels);
+    }
 };
 }  // namespace
 
+// The arena for imgs images of H x W pixels.  The largest live set is at the output resolution: ~5 tensors of `wide` channels (the last upsampler's
+// output and the GroupNorm copies around it; the widest width a graph has there) plus the attention at 1/8 resolution: its score matrix of
+// score_rows x N and the token tensors around it
+size_t Vae::arena_need(long imgs, int H, int Wd, int wide, long score_rows) const {
+    const size_t rows = (size_t)imgs * H * Wd;
+    const size_t N = (size_t)(H / 8) * (Wd / 8);
+    return rows * wide * 2 * 5 + (size_t)score_rows * N * 2 + (size_t)imgs * N * cfg.block_out_channels[3] * 2 * 8 + (256u << 20);
+}
+
 int Vae::reserve(long imgs, int H, int Wd) {
-    // the largest live set is at the output resolution: ~5 tensors of the second-narrowest width (the last upsampler's output and the GroupNorm copies
-    // around it) plus the one-frame score matrix of the attention at 1/8 resolution
-    const long rows = imgs * H * Wd;
-    const long N = (long)(H / 8) * (Wd / 8);
-    size_t need = (size_t)rows * cfg.block_out_channels[1] * 2 * 5 + (size_t)N * N * 2 + (size_t)imgs * N * cfg.block_out_channels[3] * 2 * 8 + (256u << 20);
-    return arena.ensure(need);
+    // the second-narrowest width at the output resolution, the whole score matrix of one frame
+    return arena.ensure(arena_need(imgs, H, Wd, cfg.block_out_channels[1], (long)(H / 8) * (Wd / 8)));
 }
 
 // z [imgs, latent, h, w] fp16 (already divided by the scaling factor) -> out [imgs, out_channels, 8h, 8w] fp16; imgs = clips x num_frames
 int Vae::decode(const half_t* z, long imgs, int num_frames, int h, int w, half_t* out, hipStream_t s) {
     UV_REQUIRE(finalized, "vae_decode: call univst_vae_finalize after loading weights");
     UV_REQUIRE(imgs > 0 && num_frames > 0 && imgs % num_frames == 0 && h > 0 && w > 0, "vae_decode: %ld images are not whole clips of %d frames", imgs, num_frames);
-    const int* boc = cfg.block_out_channels;
     UV_RUN(reserve(imgs, h * 8, w * 8));
     clear_missing();
     VFwd f{*this, s};
-    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
-    if (!f.gn_ws) return UV_ERR_STATE;
-    const int Lp = (cfg.latent_channels + 7) / 8 * 8;
-    Act x{f.alloc(imgs * h * w * Lp), (int)imgs, h, w, Lp};
-    if (!x.p) return UV_ERR_STATE;
-    UV_RUN(uv_launch_ncfhw_to_nhwc(z, x.p, (int)imgs, cfg.latent_channels, 1, h * w, Lp, s));
+    UV_RUN(f.take_gn_ws(imgs));
     Act cur;
-    UV_RUN(f.conv(x, "decoder.conv_in", boc[3], 9, 1, 0, false, nullptr, &cur));
-    f.free(x.p);
-    Act nxt;
-    // mid block: resnets[0], attention, resnets[1]
-    UV_RUN(f.st_resblock("decoder.mid_block.resnets.0", cur, num_frames, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.attention("decoder.mid_block.attentions.0", cur, &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    if (cfg.layers_per_block >= 2) {      // (MidBlockTemporalDecoder.forward zips resnets[1:] with its ONE attention: only resnets[1] runs behind it)
-        UV_RUN(f.st_resblock("decoder.mid_block.resnets.1", cur, num_frames, boc[3], &nxt));
-        f.free(cur.p);
-        cur = nxt;
-    }
-    for (int b = 0; b < 4; ++b) {
-        const int Cout = boc[3 - b];
-        for (int l = 0; l < cfg.layers_per_block + 1; ++l) {
-            UV_RUN(f.st_resblock("decoder.up_blocks." + std::to_string(b) + ".resnets." + std::to_string(l), cur, num_frames, Cout, &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-        if (b < 3) {
-            UV_RUN(f.conv(cur, "decoder.up_blocks." + std::to_string(b) + ".upsamplers.0.conv", Cout, 9, 1, 1, false, nullptr, &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-    }
-    half_t* n = f.alloc(cur.rows() * cur.C);
-    if (!n) return UV_ERR_STATE;
-    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "decoder.conv_norm_out", 1, n));
-    Act na{n, cur.imgs, cur.H, cur.W, cur.C};
-    f.free(cur.p);
-    UV_RUN(f.conv(na, "decoder.conv_out", cfg.out_channels, 9, 1, 0, false, nullptr, &nxt));
-    f.free(n);
+    UV_RUN(f.load_nchw(z, imgs, cfg.latent_channels, h, w, &cur));
+    UV_RUN(f.decoder(cur, num_frames, 0, nullptr));
     half_t *tw = W("decoder.time_conv_out.weight"), *tb = W("decoder.time_conv_out.bias");
     if (!tw || !tb) return missing_error("vae");
-    const long HW = (long)nxt.H * nxt.W;
-    hipLaunchKernelGGL(v_time_conv_out_kernel, dim3(nb(imgs * HW)), dim3(256), 0, s, nxt.p, cfg.out_channels, out, tw, tb, (int)(imgs / num_frames), num_frames, HW,
+    const long HW = (long)cur.H * cur.W;
+    hipLaunchKernelGGL(v_time_conv_out_kernel, dim3(nb(imgs * HW)), dim3(256), 0, s, cur.p, cfg.out_channels, out, tw, tb, (int)(imgs / num_frames), num_frames, HW,
                        cfg.out_channels);
     UV_LAUNCH_CHECK();
-    f.free(nxt.p);
+    f.free(cur.p);
     return UV_OK;
 }
 
@@ -447,70 +459,25 @@ int Vae::decode(const half_t* z, long imgs, int num_frames, int h, int w, half_t
 int Vae::encode(const half_t* xin, long imgs, int H, int Wd, half_t* moments, hipStream_t s) {
     UV_REQUIRE(finalized, "vae_encode: call univst_vae_finalize after loading weights");
     UV_REQUIRE(imgs > 0 && H % 8 == 0 && Wd % 8 == 0, "vae_encode: %ld images of %d x %d (multiples of 8)", imgs, H, Wd);
-    const int* boc = cfg.block_out_channels;
     UV_RUN(reserve(imgs, H, Wd));
     clear_missing();
     VFwd f{*this, s};
-    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
-    if (!f.gn_ws) return UV_ERR_STATE;
-    const int Ip = (cfg.in_channels + 7) / 8 * 8;
-    Act x{f.alloc(imgs * H * Wd * Ip), (int)imgs, H, Wd, Ip};
-    if (!x.p) return UV_ERR_STATE;
-    UV_RUN(uv_launch_ncfhw_to_nhwc(xin, x.p, (int)imgs, cfg.in_channels, 1, H * Wd, Ip, s));
-    Act cur, nxt;
-    UV_RUN(f.conv(x, "encoder.conv_in", boc[0], 9, 1, 0, false, nullptr, &cur));
-    f.free(x.p);
-    for (int b = 0; b < 4; ++b) {
-        for (int l = 0; l < cfg.layers_per_block; ++l) {
-            UV_RUN(f.resnet2d("encoder.down_blocks." + std::to_string(b) + ".resnets." + std::to_string(l), cur, boc[b], &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-        if (b < 3) {
-            UV_RUN(f.conv(cur, "encoder.down_blocks." + std::to_string(b) + ".downsamplers.0.conv", boc[b], 9, 2, 0, true, nullptr, &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-    }
-    UV_RUN(f.resnet2d("encoder.mid_block.resnets.0", cur, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.attention("encoder.mid_block.attentions.0", cur, &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.resnet2d("encoder.mid_block.resnets.1", cur, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    half_t* n = f.alloc(cur.rows() * cur.C);
-    if (!n) return UV_ERR_STATE;
-    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "encoder.conv_norm_out", 1, n));
-    Act na{n, cur.imgs, cur.H, cur.W, cur.C};
-    f.free(cur.p);
-    UV_RUN(f.conv(na, "encoder.conv_out", 2 * cfg.latent_channels, 9, 1, 0, false, nullptr, &cur));
-    f.free(n);
-    UV_RUN(f.conv(cur, "quant_conv", 2 * cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt));
-    f.free(cur.p);
-    UV_RUN(uv_launch_nhwc_to_ncfhw(nxt.p, 2 * cfg.latent_channels, moments, (int)imgs, 2 * cfg.latent_channels, 1, nxt.H * nxt.W, s));
-    f.free(nxt.p);
-    return UV_OK;
+    return f.encoder(xin, imgs, H, Wd, moments, true, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------ the plain AutoencoderKL (univst_klvae)
 // diffusers 0.35 AutoencoderKL (models/autoencoders/autoencoder_kl.py; vae.py Encoder / Decoder, unet_2d_blocks.py DownEncoderBlock2D / UpDecoderBlock2D /
 // UNetMidBlock2D with mid_block_add_attention) under that class's state-dict names — THIRD-PARTY, restated from the published definition; PARITY UNPINNED
-// (tests/klvae_ref.py is a second restatement).  The encoder is Vae::encode's (quant_conv only where the config has one); the decoder is
+// (tests/klvae_ref.py is a second restatement).  Both handles run VFwd::encoder (quant_conv only where the config has one) and VFwd::decoder, here with
+// plain resblocks:
 //   [post_quant_conv 1x1] | conv_in | mid: resnet, 1-head attention, resnet | 4 x [layers_per_block + 1 ResnetBlock2D, nearest x2 + conv on the first three] |
 //   GroupNorm + SiLU + conv_out
 // with no temporal layer.  No layer couples images, so a call runs its batch in groups whose arena need stays under pass_bytes, and the attention's
 // score matrix is bounded by attn_score_bytes (VFwd::attention).
 size_t KlVae::need_bytes(long imgs, int H, int Wd) const {
-    // Vae::reserve's live set per image, with the score matrix bounded by the budget
-    const size_t rows = (size_t)imgs * H * Wd;
-    const size_t N = (size_t)(H / 8) * (Wd / 8);
-    const size_t Qc = (size_t)uv_vae_attn_chunk_rows(score_bytes(), (long)N);
+    // the widest tensor at the full resolution (a config may have its first width above its second), the score matrix bounded by the budget
     const int* boc = cfg.block_out_channels;
-    const size_t wide = boc[0] > boc[1] ? boc[0] : boc[1];      // the widest tensor at the full resolution (a config may have its first width above its second)
-    return rows * wide * 2 * 5 + Qc * N * 2 + (size_t)imgs * N * cfg.block_out_channels[3] * 2 * 8 + (256u << 20);
+    return arena_need(imgs, H, Wd, boc[0] > boc[1] ? boc[0] : boc[1], uv_vae_attn_chunk_rows(score_bytes(), (long)(H / 8) * (Wd / 8)));
 }
 
 long KlVae::group_of(long imgs, int H, int Wd) const {
@@ -536,56 +503,17 @@ int KlVae::decode(const half_t* z, long imgs, int h, int w, half_t* out, hipStre
     return UV_OK;
 }
 
+// one group: the head (post_quant_conv, written with its channels padded to 8 as conv_in reads them), VFwd::decoder, the layout of the caller
 int KlVae::decode_pass(const half_t* z, long imgs, int h, int w, half_t* out, hipStream_t s) {
-    const int* boc = cfg.block_out_channels;
     VFwd f{*this, s};
-    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
-    if (!f.gn_ws) return UV_ERR_STATE;
-    const int Lp = (cfg.latent_channels + 7) / 8 * 8;
-    Act cur{f.alloc(imgs * h * w * Lp), (int)imgs, h, w, Lp}, nxt;
-    if (!cur.p) return UV_ERR_STATE;
-    UV_RUN(uv_launch_ncfhw_to_nhwc(z, cur.p, (int)imgs, cfg.latent_channels, 1, h * w, Lp, s));
-    if (kcfg.use_post_quant_conv) {
-        UV_RUN(f.conv(cur, "post_quant_conv", cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt, Lp));
-        f.free(cur.p);
-        cur = nxt;
-    }
-    UV_RUN(f.conv(cur, "decoder.conv_in", boc[3], 9, 1, 0, false, nullptr, &nxt));
+    UV_RUN(f.take_gn_ws(imgs));
+    Act cur;
+    UV_RUN(f.load_nchw(z, imgs, cfg.latent_channels, h, w, &cur));
+    if (kcfg.use_post_quant_conv)
+        UV_RUN(f.step(cur, [&](Act* y) { return f.conv(cur, "post_quant_conv", cfg.latent_channels, 1, 1, 0, false, nullptr, y, cur.C); }));
+    UV_RUN(f.decoder(cur, 0, score_bytes(), &attn_chunks));
+    UV_RUN(uv_launch_nhwc_to_ncfhw(cur.p, cfg.out_channels, out, (int)imgs, cfg.out_channels, 1, cur.H * cur.W, s));
     f.free(cur.p);
-    cur = nxt;
-    // UNetMidBlock2D: resnets[0], then (attention, resnets[1])
-    UV_RUN(f.resnet2d("decoder.mid_block.resnets.0", cur, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.attention("decoder.mid_block.attentions.0", cur, &nxt, score_bytes(), &attn_chunks));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.resnet2d("decoder.mid_block.resnets.1", cur, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    for (int b = 0; b < 4; ++b) {
-        const int Cout = boc[3 - b];
-        const std::string up = "decoder.up_blocks." + std::to_string(b);
-        for (int l = 0; l < cfg.layers_per_block + 1; ++l) {
-            UV_RUN(f.resnet2d(up + ".resnets." + std::to_string(l), cur, Cout, &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-        if (b < 3) {
-            UV_RUN(f.conv(cur, up + ".upsamplers.0.conv", Cout, 9, 1, 1, false, nullptr, &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-    }
-    half_t* n = f.alloc(cur.rows() * cur.C);
-    if (!n) return UV_ERR_STATE;
-    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "decoder.conv_norm_out", 1, n));
-    Act na{n, cur.imgs, cur.H, cur.W, cur.C};
-    f.free(cur.p);
-    UV_RUN(f.conv(na, "decoder.conv_out", cfg.out_channels, 9, 1, 0, false, nullptr, &nxt));
-    f.free(n);
-    UV_RUN(uv_launch_nhwc_to_ncfhw(nxt.p, cfg.out_channels, out, (int)imgs, cfg.out_channels, 1, nxt.H * nxt.W, s));
-    f.free(nxt.p);
     f.free(f.gn_ws);
     return UV_OK;
 }
@@ -601,59 +529,9 @@ int KlVae::encode(const half_t* xin, long imgs, int H, int Wd, half_t* moments, 
     passes = 0;
     for (long i0 = 0; i0 < imgs; i0 += g, ++passes) {
         const long n = imgs - i0 < g ? imgs - i0 : g;
-        UV_RUN(encode_pass(xin + i0 * cfg.in_channels * H * Wd, n, H, Wd, moments + i0 * 2 * cfg.latent_channels * (H / 8) * (Wd / 8), s));
+        VFwd f{*this, s};
+        UV_RUN(f.encoder(xin + i0 * cfg.in_channels * H * Wd, n, H, Wd, moments + i0 * 2 * cfg.latent_channels * (H / 8) * (Wd / 8), kcfg.use_quant_conv, score_bytes(),
+                         &attn_chunks));
     }
-    return UV_OK;
-}
-
-int KlVae::encode_pass(const half_t* xin, long imgs, int H, int Wd, half_t* moments, hipStream_t s) {
-    const int* boc = cfg.block_out_channels;
-    VFwd f{*this, s};
-    f.gn_ws = (float*)arena.alloc((size_t)uv_groupnorm_workspace_floats((int)imgs, cfg.norm_num_groups) * 4);
-    if (!f.gn_ws) return UV_ERR_STATE;
-    const int Ip = (cfg.in_channels + 7) / 8 * 8;
-    Act x{f.alloc(imgs * H * Wd * Ip), (int)imgs, H, Wd, Ip};
-    if (!x.p) return UV_ERR_STATE;
-    UV_RUN(uv_launch_ncfhw_to_nhwc(xin, x.p, (int)imgs, cfg.in_channels, 1, H * Wd, Ip, s));
-    Act cur, nxt;
-    UV_RUN(f.conv(x, "encoder.conv_in", boc[0], 9, 1, 0, false, nullptr, &cur));
-    f.free(x.p);
-    for (int b = 0; b < 4; ++b) {
-        const std::string down = "encoder.down_blocks." + std::to_string(b);
-        for (int l = 0; l < cfg.layers_per_block; ++l) {
-            UV_RUN(f.resnet2d(down + ".resnets." + std::to_string(l), cur, boc[b], &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-        if (b < 3) {
-            UV_RUN(f.conv(cur, down + ".downsamplers.0.conv", boc[b], 9, 2, 0, true, nullptr, &nxt));
-            f.free(cur.p);
-            cur = nxt;
-        }
-    }
-    UV_RUN(f.resnet2d("encoder.mid_block.resnets.0", cur, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.attention("encoder.mid_block.attentions.0", cur, &nxt, score_bytes(), &attn_chunks));
-    f.free(cur.p);
-    cur = nxt;
-    UV_RUN(f.resnet2d("encoder.mid_block.resnets.1", cur, boc[3], &nxt));
-    f.free(cur.p);
-    cur = nxt;
-    half_t* n = f.alloc(cur.rows() * cur.C);
-    if (!n) return UV_ERR_STATE;
-    UV_RUN(f.groupnorm(cur, (long)cur.H * cur.W, "encoder.conv_norm_out", 1, n));
-    Act na{n, cur.imgs, cur.H, cur.W, cur.C};
-    f.free(cur.p);
-    UV_RUN(f.conv(na, "encoder.conv_out", 2 * cfg.latent_channels, 9, 1, 0, false, nullptr, &cur));
-    f.free(n);
-    if (kcfg.use_quant_conv) {
-        UV_RUN(f.conv(cur, "quant_conv", 2 * cfg.latent_channels, 1, 1, 0, false, nullptr, &nxt));
-        f.free(cur.p);
-        cur = nxt;
-    }
-    UV_RUN(uv_launch_nhwc_to_ncfhw(cur.p, 2 * cfg.latent_channels, moments, (int)imgs, 2 * cfg.latent_channels, 1, cur.H * cur.W, s));
-    f.free(cur.p);
-    f.free(f.gn_ws);
     return UV_OK;
 }

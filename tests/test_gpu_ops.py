@@ -617,7 +617,8 @@ def test_attention_d40_long_merged_sources_and_text(nat):
     lw = torch.tensor([[math.log2(3), 0, 0], [1.0, 0, 0], [0, 0, 0]], dtype=torch.float32).cuda()
     got = nat.attention(q, k, v, dup, heads, ldq=3 * C, ldkv=3 * C, Nkv=N, C_=C, src_cnt=cnt, src_logw=lw, q_prescaled=True)
     close(got, ref, rtol=4e-3)
-    # 77 text tokens against 2304 queries: two key tiles, the second with 13 valid rows
+    # 77 text tokens against 2304 queries: one unweighted source of at most 80 keys goes to attn_text_kernel<40> (K/V in registers, no key tiles);
+    # the register-staged attn_pp40_kernel<1,0,false,0> and its tail tile are held by tests/test_gpu_attention.py
     qx = rnd(2, 2304, C, seed=4)
     kv = rnd(2, 77, 2 * C, seed=5)
     kt, vt = kv[..., :C], kv[..., C:]

@@ -430,9 +430,23 @@ int univst_unet_create_animatediff(const univst_unet_cfg* cfg, const univst_anim
 /* Y[M,N] = X[M,K] W[N,K]^T + bias + residual; geglu != 0: the diffusers GEGLU projection (FeedForward net[0], attention.py:241) — writes the
  * N/2 columns x * gelu(gate), W / bias rows pre-interleaved: geglu = 1 in blocks of [16 x rows | 16 gate rows] (any K), geglu = 2 in the
  * order of the X-resident kernel for K = 320 (N % 256 == 0, no residual; univst_geglu_xres_permute makes it from the [x | gate] weight).
- * Replaces torch Linear / 1x1 conv call sites attention.py:123,141,375-377,425. */
+ * Replaces torch Linear / 1x1 conv call sites attention.py:123,141,375-377,425.
+ * Shapes: M, N >= 1; K % 8 == 0 and ldx % 8 == 0 with X and W 16-byte aligned (the operand tiles move in 16-byte pieces); every other requirement is of
+ * the fast paths only.  N, ldy and ldr are otherwise free: rows of Y / residual that are 16-byte aligned (ldy % 8 == 0, ldr % 8 == 0, aligned pointers)
+ * take the row-contiguous epilogue of the 256x320 tile, anything else its register epilogue or the 128-wide tile, which store 4 channels (8 bytes) per lane
+ * at whatever alignment the row has — with N % 4 != 0 or an odd ldy that is a 2-byte aligned address, which gfx950 global memory accesses allow (slower,
+ * not wrong) — and finish a row whose N is not a multiple of 4 element by element.  bias needs 8-byte alignment.  geglu = 1 needs N % 32 == 0. */
 int univst_linear(const void* X, int64_t ldx, const void* W, const void* bias, const void* residual, int64_t ldr,
                   void* Y, int64_t ldy, int M, int N, int K, int geglu, void* stream);
+/* univst_linear with the rest of the plain epilogue and a caller-held split-K workspace (what the UNet graph passes to the same launcher):
+ *   Y = fp16( fp16( X W^T + bias + rowbias[m / rows_per_rowbias] + residual ) + bias2 )
+ * rowbias (may be NULL): rows of N halfs, ldrb apart (0: N), one per rows_per_rowbias output rows (the time-embedding add per branch); bias2 (may be
+ * NULL): [N], added AFTER the fp16 rounding, so the sum is rounded a second time.  workspace (may be NULL): workspace_bytes of device memory for the fp32
+ * partials of a split-K launch, 16-byte aligned; a launch that needs more than it holds (splits * M * N * 4 bytes, see univst_debug_gemm_plan) takes
+ * stream-ordered scratch of its own, as it does without one, and computes the same. */
+int univst_linear_epi(const void* X, int64_t ldx, const void* W, const void* bias, const void* residual, int64_t ldr, void* Y, int64_t ldy,
+                      int M, int N, int K, int geglu, const void* rowbias, int rows_per_rowbias, int64_t ldrb, const void* bias2,
+                      void* workspace, int64_t workspace_bytes, void* stream);
 /* Row permutation of a GEGLU projection's weight [rows][cols] (or bias / per-row fp16 vector: cols = 1) from the checkpoint's
  * [x rows | gate rows] order into the geglu = 2 order: row nt*256 + wn*64 + i*16 + g*4 + r <- x row (r < 2) or gate row (r >= 2) of hidden
  * column nt*128 + wn*32 + i*8 + g*2 + (r & 1).  rows % 256 == 0. */
@@ -739,8 +753,9 @@ int univst_debug_delay_us(double us, void* stream);
 /* What the GEMM / conv launcher and the attention launcher would do for a problem, read out on the host: no GPU, no stream, no device pointers
  * (every kernel-selection decision of the library is made by plain host code; tests/test_dispatch_plan.py holds it to a recorded table).  buf receives
  *     <kernel symbol> grid=<blocks> block=<threads> splits=<s>[ +splitk_reduce]
- * followed, for the GEMM, by the predicates the UNet graph consults for that shape:
- *      big_direct=<0|1> fold_producer=<0|1> fold_consumer=<0|1> geglu_consumer=<0|1> geglu_xres=<0|1>
+ * followed, for the GEMM, by the predicates the UNet graph consults for that shape and by what the launcher sets for the 256x320 kernels (the epilogue
+ * form: 0 registers, 1 rows through LDS, 3 the GEGLU slab; the tile order in groups of tile_gm row tiles x tile_gn column tiles, 0: column tile fastest):
+ *      big_direct=<0|1> fold_producer=<0|1> fold_consumer=<0|1> geglu_consumer=<0|1> geglu_xres=<0|1> epi_lds=<0|1|3> tile_gn=<n> tile_gm=<n>
  * or, with the launcher's non-zero return code, the launcher's error message.  Operands are 16-byte aligned with natural leading dimensions unless a flag
  * says otherwise.  ncu: compute units to plan for (an MI355X has 256).
  * gemm: mode 0 = linear [M, K] x [N, K]^T (geglu as univst_linear; rows_per_set > 0: weight sets with an fp32 bias, as univst_linear_sets);
@@ -760,6 +775,7 @@ int univst_debug_delay_us(double us, void* stream);
 #define UNIVST_PLAN_Y_UNALIGNED 2048  /* the output is 8 bytes off a 16-byte boundary */
 #define UNIVST_PLAN_WORKSPACE 4096    /* the caller holds the split-K workspace (the UNet graph, RAFT) */
 #define UNIVST_PLAN_W4 8192           /* the phase weight copy of an upsampler conv beside the others (the UNet graph; univst_conv_up2_phase_weights) */
+#define UNIVST_PLAN_LDY_ODD 16384     /* ldy = N + 1: output rows that are not 16-byte aligned */
 #define UNIVST_PLAN_GEOM_3X3 0        /* 3x3 with padding 1 (taps = 9) or 1x1 (taps = 1) */
 #define UNIVST_PLAN_GEOM_PAD_END 1    /* 3x3 over an input padded at the bottom / right only (the VAE encoder's stride-2 conv) */
 #define UNIVST_PLAN_GEOM_FRAME 2      /* 3x1 (taps = 3) over image rows = frames, image columns = pixels (the VAE's Conv3d (3,1,1)) */

@@ -43,6 +43,18 @@ def test_version_and_error_string(lib):
     assert isinstance(lib.univst_last_error(), bytes)
 
 
+def test_linear_epi_checks_its_arguments_before_any_launch(lib):
+    """univst_linear_epi (univst_linear + rowbias, bias2 and a caller-held split-K workspace) is an additive entry: the ABI version above stays at 3.
+    Null operands and a rows_per_rowbias below 1 are refused on the host, and the plan's own requirement (K % 8) comes out of it as of univst_linear."""
+    one = 16
+    assert lib.univst_linear_epi(None, 8, one, None, None, 0, one, 8, 4, 8, 8, 0, None, 1, 0, None, None, 0, None) == -1
+    assert b"linear_epi: null argument" in lib.univst_last_error()
+    assert lib.univst_linear_epi(one, 8, one, None, None, 0, one, 8, 4, 8, 8, 0, one, 0, 0, None, None, 0, None) == -1
+    assert b"rows_per_rowbias=0" in lib.univst_last_error()
+    assert lib.univst_linear_epi(one, 12, one, None, None, 0, one, 8, 4, 8, 12, 0, None, 1, 0, None, None, 0, None) == -1
+    assert lib.univst_last_error() == b"gemm: K=12 must be a multiple of 8"
+
+
 def test_no_product_import_of_oracle():
     """the product path must never route through the oracle (or any CPU fallback)."""
     bad = []

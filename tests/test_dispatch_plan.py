@@ -15,7 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = os.path.join(ROOT, "tests", "data", "dispatch_plan.txt")
 NCU = 256
-BIAS, RES, ROWBIAS, LN_STATS, STATS_OUT, ACT, GATE, W32_ONLY, W32, GN_OUT, TAPINNER, Y_UNALIGNED, WORKSPACE = (1 << i for i in range(13))
+BIAS, RES, ROWBIAS, LN_STATS, STATS_OUT, ACT, GATE, W32_ONLY, W32, GN_OUT, TAPINNER, Y_UNALIGNED, WORKSPACE, W4, LDY_ODD = (1 << i for i in range(15))
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +49,7 @@ def test_flag_values_match_the_header():
     src = open(os.path.join(ROOT, "include", "univst.h")).read()
     got = {k: int(v) for k, v in re.findall(r"#define UNIVST_PLAN_([A-Z0-9_]+) (\d+)", src)}
     want = dict(BIAS=BIAS, RESIDUAL=RES, ROWBIAS=ROWBIAS, LN_STATS=LN_STATS, STATS_OUT=STATS_OUT, ACT=ACT, GATE=GATE, W32_ONLY=W32_ONLY, W32=W32, GN_OUT=GN_OUT,
-                TAPINNER=TAPINNER, Y_UNALIGNED=Y_UNALIGNED, WORKSPACE=WORKSPACE)
+                TAPINNER=TAPINNER, Y_UNALIGNED=Y_UNALIGNED, WORKSPACE=WORKSPACE, W4=W4, LDY_ODD=LDY_ODD)
     assert {k: got.get(k) for k in want} == want
 
 

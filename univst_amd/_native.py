@@ -180,6 +180,7 @@ SIGNATURES = {
     "univst_rmsnorm_heads": (_I, [_P, _L, _L, _I, _I, _P, _F, _P]),
     "univst_rmsnorm_heads_pair": (_I, [_P, _L, _L, _I, _I, _L, _P, _L, _P, _F, _F, _P]),
     "univst_linear_gated": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _I, _P]),
+    "univst_linear_epi": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _L, _P, _P, _L, _P]),
     "univst_adaln_modulate": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _F, _P, _P, _P, _P]),
     "univst_gate_residual": (_I, [_P, _P, _L, _P, _P, _L, _L, _I, _P]),
     "univst_activation": (_I, [_P, _P, _L, _I, _P]),
@@ -422,6 +423,20 @@ def linear_mxfp8(xq, xs, wq, ws, bias=None, out=None):
     elif not (out.is_cuda and out.dtype == torch.float16 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N):
         raise ValueError(f"linear_mxfp8: out must be fp16 CUDA/HIP rows [>= {M}, >= {N}] with contiguous columns")
     check(load().univst_linear_mxfp8(ptr(xq), ptr(xs), ptr(wq), ptr(ws), ptr(bias), ptr(out), out.stride(0), M, N, K, stream_ptr()), "linear_mxfp8")
+    return out
+
+
+def linear_epi(x, w, bias=None, residual=None, rowbias=None, rows_per_rowbias=1, bias2=None, workspace=None, out=None):
+    """y[M,N] = fp16(fp16(x w^T + bias + rowbias[m // rows_per_rowbias] + residual) + bias2) (univst_linear_epi); rowbias a [B, N] row view;
+    workspace: a float32 tensor for the partials of a split-K launch (too small: the launcher takes its own scratch)."""
+    _f16(x), _f16(w)
+    M, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=torch.float16)
+    check(load().univst_linear_epi(ptr(x), K, ptr(w), ptr(bias), ptr(residual), N, ptr(out), N, M, N, K, 0, ptr(rowbias), rows_per_rowbias,
+                                   0 if rowbias is None else rowbias.stride(0), ptr(bias2), ptr(workspace),
+                                   0 if workspace is None else workspace.numel() * workspace.element_size(), stream_ptr()), "linear_epi")
     return out
 
 

@@ -316,6 +316,18 @@ int univst_linear_gated(const void* X, int64_t ldx, const void* W, const void* b
     g.gate = H(gate); g.ld_gate = ld_gate; g.rows_per_gate = gate ? rows_per_gate : 1;
     return uv_launch_gemm(g, 0, S(s));
 }
+int univst_linear_epi(const void* X, int64_t ldx, const void* W, const void* bias, const void* R, int64_t ldr, void* Y, int64_t ldy,
+                      int M, int N, int K, int geglu, const void* rowbias, int rows_per_rowbias, int64_t ldrb, const void* bias2,
+                      void* workspace, int64_t workspace_bytes, void* s) {
+    UV_REQUIRE(X && W && Y, "linear_epi: null argument");
+    UV_REQUIRE(!rowbias || rows_per_rowbias >= 1, "linear_epi: rows_per_rowbias=%d must be at least 1", rows_per_rowbias);
+    GemmParams g;
+    g.X = H(X); g.ldx = ldx; g.W = H(W); g.bias = H(bias); g.R = H(R); g.ldr = ldr; g.Y = HM(Y); g.ldy = ldy;
+    g.M = M; g.N = N; g.K = K; g.geglu = geglu;
+    g.rowbias = H(rowbias); g.rows_per_rb = rowbias ? rows_per_rowbias : 1; g.ldrb = ldrb; g.bias2 = H(bias2);
+    g.partial = (float*)workspace; g.partial_bytes = workspace && workspace_bytes > 0 ? (size_t)workspace_bytes : 0;
+    return uv_launch_gemm(g, 0, S(s));
+}
 int univst_geglu_xres_permute(const void* in, void* out, int rows, int cols, void* s) {
     UV_REQUIRE(in && out, "geglu_xres_permute: null argument");
     return uv_launch_geglu_xres_permute(H(in), HM(out), rows, cols, S(s));
@@ -804,7 +816,7 @@ int univst_debug_gemm_plan(int ncu, int mode, int M, int N, int K, int geglu, in
         g.M = M * g.Ho * g.Wo; g.K = taps * (C1 + C2);
         g.korder = on(UNIVST_PLAN_TAPINNER) ? 1 : 0;
     }
-    g.ldy = No; g.ldr = No;
+    g.ldy = on(UNIVST_PLAN_LDY_ODD) ? No + 1 : No; g.ldr = No;
     if (on(UNIVST_PLAN_BIAS)) g.bias = h;
     if (on(UNIVST_PLAN_RESIDUAL)) g.R = h;
     if (on(UNIVST_PLAN_ROWBIAS)) g.rowbias = h;

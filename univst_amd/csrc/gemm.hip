@@ -1834,9 +1834,10 @@ int uv_gemm_plan_text(const GemmParams& p0, int mode, int ncu, char* buf, int n)
         uv_set_error("%s", pl.err);
         return pl.rc;
     }
-    snprintf(buf, (size_t)n, "%s grid=%u block=%u splits=%d%s big_direct=%d fold_producer=%d fold_consumer=%d geglu_consumer=%d geglu_xres=%d", pl.sym, pl.grid,
-             pl.block, pl.splits, pl.reduce_grid ? " +splitk_reduce" : "", (int)takes_big_direct(p.M, p.N, p.K, p.ldx), (int)fold_producer_ok(p.M, p.N, p.K, ncu),
-             (int)fold_consumer_ok(p.M, p.N, p.K, false, ncu), (int)fold_consumer_ok(p.M, p.N, p.K, true, ncu), (int)geglu_xres_ok(p.N, p.K, p.M, ncu));
+    snprintf(buf, (size_t)n, "%s grid=%u block=%u splits=%d%s big_direct=%d fold_producer=%d fold_consumer=%d geglu_consumer=%d geglu_xres=%d epi_lds=%d tile_gn=%d tile_gm=%d",
+             pl.sym, pl.grid, pl.block, pl.splits, pl.reduce_grid ? " +splitk_reduce" : "", (int)takes_big_direct(p.M, p.N, p.K, p.ldx), (int)fold_producer_ok(p.M, p.N, p.K, ncu),
+             (int)fold_consumer_ok(p.M, p.N, p.K, false, ncu), (int)fold_consumer_ok(p.M, p.N, p.K, true, ncu), (int)geglu_xres_ok(p.N, p.K, p.M, ncu), pl.epi_lds,
+             pl.tile_gn, pl.tile_gm);
     return UV_OK;
 }
 

@@ -637,6 +637,35 @@ int univst_sd3_joint_attention_mx(const univst_sd3_attn_weights* w, const void* 
  * ws: 4*F*2C + 2*F*2*heads floats. */
 int univst_sd3_adain_shift(void* qkv, int64_t ld, int F, int N, int C, int heads, float alpha, float beta, float gamma, void* ws,
                            void* stream);
+/* ---- static style branch of the SD3 path (opt-in) ----
+ * The style input is ONE image: F identical style frames give every frame the key set [own image keys x 3 ++ own text keys], which is the
+ * joint attention at B = 1, clip_length = 1, and the stylised branch reads nothing of the style branch but its post-RMSNorm K | V image rows.
+ * So the style runs as one frame whose K | V rows are kept in a caller-owned bank [N, 2C] per attention module, and the other two branches
+ * run as a two-branch batch that shifts against the bank.
+ *
+ * The shift of univst_sd3_adain_shift on a TWO-branch fused buffer qkv2 [2*F*N, 3C] (branch 0 content, 1 stylised; row stride ld), in place on
+ * the stylised rows: the style K | V rows come from style_kv [N, 2C] (row stride ld_style >= 2C) and token n of EVERY frame blends against
+ * style row n; the style mean / unbiased std per channel over N are taken once, the stylised branch's joint (N, head_dim) statistics per
+ * (frame, head) as in the three-branch entry.  Same row arithmetic as the three-branch entry (one device function).  Content rows, style_kv
+ * and every column behind 3C / 2C are never written.
+ * UNIVST_ERR_ARG before any launch: a null qkv2 / style_kv / ws, N < 2, C % heads != 0, C % 8 != 0, ld % 8 != 0 or ld < 3C, ld_style % 8 != 0 or
+ * ld_style < 2C, qkv2 or style_kv not 16-byte aligned (rows move in 16-byte pieces).
+ * ws: (2 + 2*F)*2C + 2*F*2*heads floats. */
+int univst_sd3_adain_shift_static(void* qkv2, int64_t ld, const void* style_kv, int64_t ld_style, int F, int N, int C, int heads, float alpha,
+                                  float beta, float gamma, void* ws, void* stream);
+/* univst_sd3_joint_attention_mx (mx may be NULL: fp16 projections) without a communicator, in one of the two roles of the static style branch:
+ *   role 0, the bank call: the ordinary joint attention of the style batch (normally B = 1, clip_length = 1: sd3_index_kernel merges the frame's
+ *           three identical sources into one of weight log2 3), which also writes frame 0's post-norm K | V image rows [N, 2C] into the
+ *           caller-owned style_kv (row stride ld_style).  shift must be 0: the style branch is never shifted.
+ *   role 1, the apply call: B = 2 * clip_length, content frames then stylised frames.  With shift != 0 univst_sd3_adain_shift_static runs
+ *           against style_kv where the three-branch shift sits (after the q / k RMSNorm, before the cross-frame gather); with shift == 0 style_kv
+ *           may be NULL and the call is univst_sd3_joint_attention on the two-branch batch.
+ * UNIVST_ERR_ARG before any launch: role not 0 / 1, shift != 0 in role 0, B != 2 * clip_length in role 1, N < 2 in role 1 with shift != 0, a NULL style_kv where the role needs
+ * it, ld_style % 8 != 0 or ld_style < 2C, style_kv not 16-byte aligned; everything univst_sd3_joint_attention_mx refuses. */
+int univst_sd3_joint_attention_static(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin,
+                                      int heads, int head_dim, int clip_length, int shift, float beta, float rms_eps,
+                                      void* out_img, void* out_txt, const univst_sd3_gated_residual* gated_residual /* may be NULL */,
+                                      void* stream, const univst_sd3_mx_weights* mx /* may be NULL */, void* style_kv, int64_t ld_style, int role);
 /* diffusers RMSNorm over the head dim, in place: x[r, h*d + e] *= rsqrt(mean_e x^2 + eps) * weight[e]  (row stride ld >= heads*d) */
 int univst_rmsnorm_heads(void* x, int64_t ld, int64_t rows, int heads, int head_dim, const void* weight, float eps, void* stream);
 /* the same on two column blocks of one row-strided buffer, as the joint attention runs it on a fused q | k | v row: the heads * head_dim

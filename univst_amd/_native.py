@@ -177,6 +177,9 @@ SIGNATURES = {
     "univst_sd3_joint_attention_mx": (_I, [C.POINTER(Sd3AttnWeights), _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P,
                                            C.POINTER(Sd3GatedResidual), _P, _P, C.POINTER(Sd3MxWeights)]),
     "univst_sd3_adain_shift": (_I, [_P, _L, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "univst_sd3_adain_shift_static": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "univst_sd3_joint_attention_static": (_I, [C.POINTER(Sd3AttnWeights), _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P,
+                                               C.POINTER(Sd3GatedResidual), _P, C.POINTER(Sd3MxWeights), _P, _L, _I]),
     "univst_rmsnorm_heads": (_I, [_P, _L, _L, _I, _I, _P, _F, _P]),
     "univst_rmsnorm_heads_pair": (_I, [_P, _L, _L, _I, _I, _L, _P, _L, _P, _F, _F, _P]),
     "univst_linear_gated": (_I, [_P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _I, _P]),
@@ -732,7 +735,7 @@ class Sd3AttnParams(dict):
 
 
 def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False, idx=-1, eta1=0.0, eta2=0.6, rms_eps=1e-6, fuse=None, comm=None,
-                        qkv_dtype="fp16"):
+                        qkv_dtype="fp16", style_kv=None, static_role=None):
     """CrossFrameProcessor / AttentionShiftProcessor of the reference's SD3 plugin on the native kernels.  params: the state dict
     of diffusers' Attention module (to_q.weight, ..., to_add_out.bias; missing entries = absent).  hidden [B, N, Cin],
     enc [B, Nt, Cin] or None -> (img [B, N, Cin], txt [B, Nt, Cin]) or img alone.  clip_length 0: no cross-frame keys.
@@ -740,7 +743,22 @@ def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False,
     epilogue: the returned tensors are then res + gate[:, None] * attention output.
     comm (optional): pointer of a connected univst_comm — the batch is this rank's clip_length frames of every branch (frame shard).
     qkv_dtype: "fp16", or "mxfp8" for the two q | k | v projections on the block-scaled fp8 MFMA (univst_sd3_joint_attention_mx; params' quantised
-    weights are made on first use; input width a multiple of 128, no frame shard)."""
+    weights are made on first use; input width a multiple of 128, no frame shard).
+    static_role (optional, univst_sd3_joint_attention_static): 0 = the bank call — the ordinary joint attention of the style frame, which also writes
+    frame 0's post-norm K | V image rows into ``style_kv`` [N, >= 2C] (fp16, unit column stride; no shift); 1 = the apply call — the batch is
+    [content | stylised] (B = 2 * clip_length) and, inside the window, the shift runs against ``style_kv`` (outside it ``style_kv`` may be None).
+    No communicator in either role."""
+    if static_role is not None:
+        if static_role not in (0, 1):
+            raise ValueError(f"sd3_joint_attention: static_role must be None, 0 (bank) or 1 (apply), got {static_role!r}")
+        if comm is not None:
+            raise ValueError("sd3_joint_attention: static_role and comm (a frame shard) cannot be combined")
+        if style_kv is not None and not (style_kv.is_cuda and style_kv.dtype == torch.float16 and style_kv.dim() == 2 and style_kv.stride(1) == 1
+                                         and style_kv.shape[0] == hidden.shape[1]):
+            raise ValueError(f"sd3_joint_attention: style_kv must be an fp16 CUDA/HIP [N = {hidden.shape[1]}, >= 2C] tensor or row view with a unit "
+                             f"column stride, got {style_kv.dtype} {tuple(style_kv.shape)} strides {tuple(style_kv.stride())}")
+    elif style_kv is not None:
+        raise ValueError("sd3_joint_attention: style_kv needs static_role")
     if qkv_dtype not in ("fp16", "mxfp8"):
         raise ValueError(f"sd3_joint_attention: qkv_dtype must be 'fp16' or 'mxfp8', got {qkv_dtype!r}")
     _f16(hidden)
@@ -765,9 +783,14 @@ def sd3_joint_attention(params, hidden, enc, heads, clip_length=16, shift=False,
     beta = ((0.9 - 0.1) / (eta1 * 50 - eta2 * 50) * (idx - eta2 * 50) + 0.1) if active else 0.0
     args = (C.byref(w), ptr(hidden), ptr(enc), B, N, Nt, Cin, heads, inner // heads, clip_length, int(active), float(beta), rms_eps, ptr(out_i),
             ptr(out_t), C.byref(gr) if gr is not None else None, comm, stream_ptr())
+    mx = None
     if qkv_dtype == "mxfp8":
         m = keep.mx()
         mx = Sd3MxWeights(ptr(m["qkv"]), ptr(m["qkv_scale"]), ptr(m.get("add_qkv")), ptr(m.get("add_qkv_scale")))
+    if static_role is not None:
+        check(load().univst_sd3_joint_attention_static(*args[:-2], stream_ptr(), C.byref(mx) if mx is not None else None, ptr(style_kv),
+                                                       0 if style_kv is None else style_kv.stride(0), static_role), "sd3_joint_attention_static")
+    elif mx is not None:
         check(load().univst_sd3_joint_attention_mx(*args, C.byref(mx)), "sd3_joint_attention_mx")
     else:
         check(load().univst_sd3_joint_attention(*args), "sd3_joint_attention")
@@ -790,6 +813,20 @@ def sd3_adain_shift_(qkv, F, N, C_, heads, alpha, beta, gamma):
     ws = torch.empty(4 * F * 2 * C_ + 2 * F * 2 * heads, device=qkv.device, dtype=torch.float32)
     check(load().univst_sd3_adain_shift(ptr(qkv), ld, F, N, C_, heads, alpha, beta, gamma, ptr(ws), stream_ptr()), "sd3_adain_shift")
     return qkv
+
+
+def sd3_adain_shift_static_(qkv2, style_kv, F, N, C_, heads, alpha, beta, gamma):
+    """in place on the stylised rows of the fused TWO-branch [2*F*N, 3C] buffer (content, stylised) against one style frame's K | V rows
+    style_kv [N, 2C]; both may be column-sliced views (row strides >= 3C / 2C, unit column stride)."""
+    for what, t, rows in (("qkv2", qkv2, 2 * F * N), ("style_kv", style_kv, N)):
+        if not (t.is_cuda and t.dtype == torch.float16):
+            raise ValueError(f"sd3 static shift: {what}: expected an fp16 CUDA/HIP tensor, got {t.dtype} {t.device}")
+        if t.dim() != 2 or t.shape[0] != rows or t.stride(1) != 1:
+            raise ValueError(f"sd3 static shift: {what}: expected {rows} rows with unit column stride, got {tuple(t.shape)} strides {tuple(t.stride())}")
+    ws = torch.empty((2 + 2 * F) * 2 * C_ + 2 * F * 2 * heads, device=qkv2.device, dtype=torch.float32)
+    check(load().univst_sd3_adain_shift_static(ptr(qkv2), qkv2.stride(0), ptr(style_kv), style_kv.stride(0), F, N, C_, heads, alpha, beta, gamma,
+                                               ptr(ws), stream_ptr()), "sd3_adain_shift_static")
+    return qkv2
 
 
 def rmsnorm_heads_(x, heads, weight, eps=1e-6):

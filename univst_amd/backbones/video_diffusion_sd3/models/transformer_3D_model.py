@@ -366,6 +366,44 @@ class CustomSD3Transformer2DModel(nn.Module):
         return Transformer2DModelOutput(sample=out)
 
 
+    # ------------------------------------------------------------------ static style branch (addition, opt-in)
+    @torch.no_grad()
+    def style_bank(self, frame, timestep, enc1, pooled1, idx, bank=None):
+        """The style branch of step ``idx`` as ONE frame: runs ``frame`` [1, C, h, w] through the model with every joint attention writing its
+        post-norm K | V image rows into ``bank`` (a ``pnp_utils.StaticStyleBank``; None makes one) and returns the bank.  Outside the shift window of
+        the registered AttentionShiftProcessors nothing reads those rows: then nothing is run, nothing is written and None is returned."""
+        from ..pnp_utils import StaticStyleBank, shift_window, window_open
+        if not window_open(shift_window(self), idx):
+            return None
+        if frame.dim() != 4 or frame.shape[0] != 1:
+            raise ValueError(f"style_bank takes the one style frame [1, C, h, w], got {tuple(frame.shape)}")
+        bank = StaticStyleBank() if bank is None else bank
+        bank.mode = "write"
+        try:
+            self(hidden_states=frame, timestep=timestep, encoder_hidden_states=enc1, pooled_projections=pooled1, return_dict=False,
+                 joint_attention_kwargs={"idx": idx, "static_style": bank})
+        finally:
+            bank.mode = "read"
+        return bank
+
+    @torch.no_grad()
+    def forward_static_style(self, sample2, timestep, enc2, pooled2, idx, bank):
+        """The two-branch batch ``sample2`` [2F, C, h, w] = [content | stylised] of step ``idx`` -> its velocities [2F, C, h, w]: inside the shift
+        window the stylised branch shifts against ``bank`` (from ``style_bank`` at the same step); outside it (``bank`` None) this is the plain
+        forward of the two-branch batch.  The processors' ``clip_length`` must be F."""
+        from ..pnp_utils import shift_window, window_open
+        kw = {"idx": idx}
+        if window_open(shift_window(self), idx):
+            if bank is None:
+                raise ValueError(f"forward_static_style: step {idx} is inside the shift window and needs the bank of style_bank at that step")
+            if sample2.shape[0] % 2:
+                raise ValueError(f"forward_static_style takes the two-branch batch [content | stylised], got {sample2.shape[0]} frames")
+            bank.mode = "read"
+            kw["static_style"] = bank
+        return self(hidden_states=sample2, timestep=timestep, encoder_hidden_states=enc2, pooled_projections=pooled2, return_dict=False,
+                    joint_attention_kwargs=kw)[0]
+
+
 def sd35_medium(**overrides):
     """the MMDiT-X of stabilityai/stable-diffusion-3.5-medium (the reference's default checkpoint, src/sd3/run_*_sd3.py:103)."""
     return CustomSD3Transformer2DModel(**{**SD35_MEDIUM_CONFIG, **overrides})

@@ -53,6 +53,16 @@ def _blend_frames(a, b, m):
     return out
 
 
+def static_style_frame(z, frames, frame_shape):
+    """static_style: the one style frame [1, C, h, w] of a style inversion entry — ``[1, C, h, w]`` (a one-frame inversion,
+    run_style_inversion_sd3.py --static_style) or the reference's ``[F, C, h, w]`` (the image repeated), of which frame 0 is taken.
+    Anything else is refused by shape."""
+    if z.dim() != 4 or z.shape[0] not in (1, frames) or tuple(z.shape[1:]) != tuple(frame_shape):
+        dims = ", ".join(str(d) for d in frame_shape)
+        raise ValueError(f"static_style: a style inversion latent must be [1, {dims}] or [{frames}, {dims}] (frame 0 is taken), got {tuple(z.shape)}")
+    return z[:1]
+
+
 class CustomStableDiffusion3Pipeline:
     def __init__(self, transformer, scheduler, vae=None, text_encoder=None, tokenizer=None, text_encoder_2=None, tokenizer_2=None,
                  text_encoder_3=None, tokenizer_3=None, image_encoder=None, feature_extractor=None):
@@ -193,7 +203,8 @@ class CustomStableDiffusion3Pipeline:
                              negative_pooled_prompt_embeds=None, output_type="pil", return_dict=True, callback_on_step_end=None,
                              callback_on_step_end_tensor_inputs=("latents",), max_sequence_length=256, mu=None,
                              content_inv_path=None, style_inv_path=None, mask_path=None, eta_base=0.95, eta_trend="constant", start_step=10,
-                             end_step=20, img_latents=None, content_inv_latents=None, style_inv_latents=None, shard=None, masks=None):
+                             end_step=20, img_latents=None, content_inv_latents=None, style_inv_latents=None, shard=None, masks=None,
+                             static_style=False, skip_dead_branches=False):
         """``content_inv_latents`` / ``style_inv_latents`` (addition): the per-step inversion latents in memory (lists indexed by the
         step label k of ``ddim_latents_{k}.pt``) instead of ``*_inv_path`` — the in-process hand-off of SURVEY §8f-1; ``masks`` the
         ``load_mask`` tensor in memory instead of ``mask_path``.
@@ -202,7 +213,16 @@ class CustomStableDiffusion3Pipeline:
         frames are split over the ranks — ``None`` builds ``parallel.Sd3FrameShard`` for the group (K | V of the first and the previous
         frame travel through the library's IPC communicator inside every joint attention), ``False`` keeps the whole clip on every rank,
         an explicit ``Sd3FrameShard`` is used as is.  All arguments are the full clip on every rank; every rank gets the full latents
-        back and rank 0 decodes (``.images`` is None elsewhere unless ``output_type='latent'``)."""
+        back and rank 0 decodes (``.images`` is None elsewhere unless ``output_type='latent'``).
+
+        ``static_style`` (addition, off by default): the style image runs as ONE frame.  Inside the shift window a step is
+        ``transformer.style_bank`` (one frame; its K | V rows of every attention module go to a bank) followed by
+        ``transformer.forward_static_style`` on [content | stylised] (2F + 1 frame-forwards instead of 3F); outside it the two-branch batch runs
+        alone.  The style inversion latents may be the one frame ``[1, C, h, w]`` or the reference's ``[F, C, h, w]``, whose frame 0 is taken: the
+        result is that of a clip whose style frames are all frame 0 (the reference's F frames differ by the VAE's posterior noise).  Not built
+        under a frame shard.
+        ``skip_dead_branches`` (addition, off by default): outside the shift window of the registered processors the content and style
+        velocities are never read, so only the stylised branch runs (B = F).  Both switches combine."""
         if latents is None or img_latents is None:
             raise ValueError("video_style_transfer needs `latents` (the shifted content noise) and `img_latents`")
         if callback_on_step_end is not None:
@@ -224,6 +244,8 @@ class CustomStableDiffusion3Pipeline:
                 shard = cache[key]
         if shard is False or (shard is not None and shard.world == 1):
             shard = None
+        if static_style and shard is not None:
+            raise NotImplementedError(f"static_style under a frame shard (world {shard.world}) is not built; pass shard=False or static_style=False")
         cut = shard.slice_frames if shard is not None else (lambda t: t)
         latents, target = cut(_f16(latents)), cut(_f16(img_latents))
         F_ = latents.shape[0]
@@ -237,6 +259,31 @@ class CustomStableDiffusion3Pipeline:
         def inv(store, path, k):
             return cut(_f16(store[k] if store is not None else load_ddim_latents_at_t(k, path)))
 
+        def style_frame(k):
+            z = style_inv_latents[k] if style_inv_latents is not None else load_ddim_latents_at_t(k, style_inv_path)
+            return _f16(static_style_frame(z, F_all, tuple(latents.shape[1:])))
+
+        window = None
+        if static_style or skip_dead_branches:                       # which steps shift: read from the registered processors, which must agree
+            from ..pnp_utils import shift_window, window_open
+            window = shift_window(self.transformer)
+        tr, bank = self.transformer, None
+
+        def velocity(i, t, c_t, s_t):
+            """the stylised branch's velocity [F, C, h, w] of step i"""
+            nonlocal bank
+            if skip_dead_branches and not window_open(window, i):   # the stylised branch alone: nothing reads the other two out here
+                return tr(hidden_states=latents, timestep=t.expand(F_), encoder_hidden_states=pe_all[:F_], pooled_projections=pp_all[:F_],
+                          return_dict=False, joint_attention_kwargs={"idx": i})[0]
+            if static_style:
+                b = tr.style_bank(s_t, t.expand(1), pe_all[:1], pp_all[:1], i, bank)
+                bank = b if b is not None else bank                  # one bank for the whole loop
+                x = torch.cat([c_t, latents])
+                return tr.forward_static_style(x, t.expand(2 * F_), pe_all[:2 * F_], pp_all[:2 * F_], i, b)[F_:]
+            x = torch.cat([c_t, s_t, latents])
+            return tr(hidden_states=x, timestep=t.expand(x.shape[0]), encoder_hidden_states=pe_all, pooled_projections=pp_all, return_dict=False,
+                      joint_attention_kwargs={"idx": i})[0][2 * F_:]
+
         mask = None
         if mask_path or masks is not None:                           # load_mask + bilinear resize once (the reference redoes both per step)
             m = masks if masks is not None else load_mask(mask_path, n_frames=F_all)
@@ -247,16 +294,14 @@ class CustomStableDiffusion3Pipeline:
             for i, t in enumerate(ts):
                 if self.interrupt:
                     continue
-                c_t, s_t = inv(content_inv_latents, content_inv_path, 50 - i), inv(style_inv_latents, style_inv_path, 50 - i)
+                c_t = inv(content_inv_latents, content_inv_path, 50 - i)
+                s_t = style_frame(50 - i) if static_style else inv(style_inv_latents, style_inv_path, 50 - i)
                 if mask is not None and i <= 0.9 * n:                # localized latent blending (:289-294)
                     latents = _blend_frames(latents, c_t, mask)
                 if i >= 0.8 * n and i <= 0.9 * n:                    # :296-303, fixed reading of the undefined name: the content latents
-                    shifted = _f16(latent_adain(latents, s_t))
+                    shifted = _f16(latent_adain(latents, s_t.expand(F_, -1, -1, -1) if static_style else s_t))
                     latents = _blend_frames(shifted, c_t, mask) if mask is not None else shifted
-                x = torch.cat([c_t, s_t, latents])
-                v = self.transformer(hidden_states=x, timestep=t.expand(x.shape[0]), encoder_hidden_states=pe_all, pooled_projections=pp_all,
-                                     return_dict=False, joint_attention_kwargs={"idx": i})[0]
-                latents = self._euler_eta(latents, _f16(v[2 * F_:]), target, ds[i], eta_values[i], tl[i] / T)
+                latents = self._euler_eta(latents, _f16(velocity(i, t, c_t, s_t)), target, ds[i], eta_values[i], tl[i] / T)
                 bar.update()
         if shard is not None:
             latents = shard.gather_frames(latents)

@@ -27,7 +27,51 @@ def _params(attn):
     return cached[1]
 
 
-def _run(attn, hidden_states, encoder_hidden_states, shift, idx, eta1, eta2, clip_length=16, fuse=None):
+class StaticStyleBank:
+    """The static style branch's state: one fp16 [N, 2C] buffer per attention module — the post-norm K | V
+    image rows of the ONE style frame — and a mode.  ``mode == "write"``: the call is the style frame's own forward (one frame, a clip of its own,
+    never shifted) and every joint attention also writes its buffer; ``"read"``: the call is the two-branch batch [content | stylised] and, inside
+    the window, the shift reads the buffer.  Handed to the processors as the keyword ``static_style`` through ``joint_attention_kwargs``, as ``idx``
+    is.  The buffers are allocated on first use and reused for the whole loop (37 modules x N x 2C halfs for SD3.5-medium: 0.93 GB at 1024 px)."""
+
+    def __init__(self):
+        self.mode = "write"
+        self._buf = {}
+
+    def buffer(self, attn, N, C2, device):
+        """the [N, 2C] buffer of this attention module; a changed token count or width (another latent size) re-allocates it"""
+        b = self._buf.get(id(attn))
+        if b is None or tuple(b.shape) != (N, C2) or b.device != device:
+            if self.mode != "write":
+                raise RuntimeError(f"static_style: no style K | V rows of shape [{N}, {C2}] were banked for this attention module: run style_bank first, "
+                                   "at the same latent size")
+            b = torch.empty(N, C2, dtype=torch.float16, device=device)
+            self._buf[id(attn)] = b
+        return b
+
+    def buffers(self):
+        return list(self._buf.values())
+
+    def nbytes(self):
+        return sum(b.numel() * b.element_size() for b in self._buf.values())
+
+
+def shift_window(transformer):
+    """(eta1, eta2) of the registered AttentionShiftProcessors — the shift is applied while eta1*50 <= idx <= eta2*50 — or None when no such
+    processor is registered (the window is never open).  Processors that disagree raise: the static style branch and the dead-branch skip decide
+    per STEP which branches run."""
+    wins = {(p.eta1, p.thresh2) for p in transformer.attn_processors.values() if isinstance(p, AttentionShiftProcessor)}
+    if len(wins) > 1:
+        raise ValueError(f"the registered AttentionShiftProcessors disagree on the shift window (eta1, eta2): {sorted(wins)}")
+    return next(iter(wins)) if wins else None
+
+
+def window_open(window, idx):
+    """pnp_utils.py:183 in Python double, like the reference (and like _native.sd3_joint_attention)"""
+    return window is not None and idx >= window[0] * 50 and idx <= window[1] * 50
+
+
+def _run(attn, hidden_states, encoder_hidden_states, shift, idx, eta1, eta2, clip_length=16, fuse=None, static_style=None):
     dt, dev = hidden_states.dtype, hidden_states.device
     if dev.type != "cuda":
         raise RuntimeError("univst_amd SD3 processors run on the GPU only (no CPU path): move the tensors to cuda")
@@ -37,6 +81,9 @@ def _run(attn, hidden_states, encoder_hidden_states, shift, idx, eta1, eta2, cli
     comm = None
     shard = getattr(attn, "_uv_frame_shard", None)            # univst_amd.parallel.Sd3FrameShard.attach: this rank's frames of every branch
     if shard is not None and shard.world > 1:
+        if static_style is not None:
+            raise NotImplementedError(f"static_style under a frame shard (world {shard.world}) is not built: the bank holds one rank's rows and the "
+                                      "halo frames would need the shift on the receiving rank; run static_style unsharded or the frame shard without it")
         if clip_length == 0:
             raise RuntimeError("a frame-sharded MM-DiT needs the cross-frame processors (CrossFrameProcessor / AttentionShiftProcessor)")
         clip_length, comm = shard.local, shard.comm.ptr
@@ -44,8 +91,19 @@ def _run(attn, hidden_states, encoder_hidden_states, shift, idx, eta1, eta2, cli
     if qkv_dtype == "mxfp8" and comm is not None:
         raise RuntimeError(f"qkv_dtype 'mxfp8' under a frame shard (world {shard.world}) is not built: the receiver-side projection of the halo rows "
                            "is fp16 only; use set_qkv_dtype('fp16') on a sharded MM-DiT")
-    out = _native.sd3_joint_attention(_params(attn), hid, enc, attn.heads, clip_length=clip_length, shift=shift, idx=idx, eta1=eta1, eta2=eta2,
-                                      rms_eps=float(eps), fuse=fuse, comm=comm, qkv_dtype=qkv_dtype)
+    params = _params(attn)
+    static = {}
+    if static_style is not None:
+        if static_style.mode not in ("write", "read"):
+            raise ValueError(f"static_style.mode must be 'write' or 'read', got {static_style.mode!r}")
+        bank = static_style.buffer(attn, hid.shape[1], 2 * params["to_q"].shape[0], hid.device)
+        if static_style.mode == "write":                      # the style frame(s): each frame a clip of its own, never shifted
+            clip_length, shift = (1 if clip_length else 0), False
+            static = dict(style_kv=bank, static_role=0)
+        else:
+            static = dict(style_kv=bank, static_role=1)
+    out = _native.sd3_joint_attention(params, hid, enc, attn.heads, clip_length=clip_length, shift=shift, idx=idx, eta1=eta1, eta2=eta2,
+                                      rms_eps=float(eps), fuse=fuse, comm=comm, qkv_dtype=qkv_dtype, **static)
     if enc is None:
         return out.to(dt)
     return out[0].to(dt), out[1].to(dt)
@@ -54,14 +112,17 @@ def _run(attn, hidden_states, encoder_hidden_states, shift, idx, eta1, eta2, cli
 class CrossFrameProcessor:
     """pnp_utils.py:9-131: joint attention whose image keys / values are those of frames ['first', f-1, f] of the clip.
     ``fused_gated_residual`` (addition, keyword only): the native MM-DiT block hands its gated residual to processors that
-    advertise ``supports_fused_gated_residual``; the result is then hidden + gate * attention output (one epilogue, no extra pass)."""
+    advertise ``supports_fused_gated_residual``; the result is then hidden + gate * attention output (one epilogue, no extra pass).
+    ``static_style`` (addition, keyword only, through ``joint_attention_kwargs``): a ``StaticStyleBank`` — see there."""
     supports_fused_gated_residual = True
     clip_length = 16        # pnp_utils.py:26 hard-codes 16 frames per clip inside __call__; an attribute here so that other clip lengths can be set
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, idx=-1, *args, fused_gated_residual=None, **kwargs):
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, idx=-1, *args, fused_gated_residual=None,
+                 static_style=None, **kwargs):
         if attention_mask is not None:
             raise NotImplementedError("attention_mask is not used on the UniVST path")
-        return _run(attn, hidden_states, encoder_hidden_states, False, idx, 0.0, 0.0, clip_length=self.clip_length, fuse=fused_gated_residual)
+        return _run(attn, hidden_states, encoder_hidden_states, False, idx, 0.0, 0.0, clip_length=self.clip_length, fuse=fused_gated_residual,
+                    static_style=static_style)
 
 
 class AttentionShiftProcessor:
@@ -74,10 +135,12 @@ class AttentionShiftProcessor:
         self.eta1, self.eta2 = eta1, eta2
         self.thresh2 = eta2          # the attribute the reference forgets to set (see the module docstring)
 
-    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, idx=-1, *args, fused_gated_residual=None, **kwargs):
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, idx=-1, *args, fused_gated_residual=None,
+                 static_style=None, **kwargs):
         if attention_mask is not None:
             raise NotImplementedError("attention_mask is not used on the UniVST path")
-        return _run(attn, hidden_states, encoder_hidden_states, True, idx, self.eta1, self.thresh2, clip_length=self.clip_length, fuse=fused_gated_residual)
+        return _run(attn, hidden_states, encoder_hidden_states, True, idx, self.eta1, self.thresh2, clip_length=self.clip_length, fuse=fused_gated_residual,
+                    static_style=static_style)
 
 
 def register_spatial_attention_pnp(model, eta1=0.0, eta2=0.6):

@@ -120,9 +120,18 @@ __global__ void sd3_group_stats_kernel(const float* __restrict__ mean, const flo
     rstd[i] = (float)(1.0 / sqrt(var + 1e-5));
 }
 
-// the shift itself, one wave per token row of the stylised branch (rows [2*F*N, 3*F*N) of the fused [3*F*N, 3C] q|k|v buffer):
+// The arithmetic of the shift, one element; every shift kernel below goes through these two, so they cannot drift apart:
 //   q2 <- gamma * (alpha * q0 + (1 - alpha) * q2)
-//   k2 <- beta * ((k2 - mu) * rstd * sty_std + sty_mean) + (1 - beta) * k1        (same for v)
+//   k2 <- beta * ((k2 - mu) * rstd * sty_std + sty_mean) + (1 - beta) * k_style        (same for v)
+__device__ __forceinline__ half_t sd3_shift_q(float q0, float q2, float alpha, float gamma) {
+    return (half_t)(gamma * (alpha * q0 + (1.f - alpha) * q2));
+}
+__device__ __forceinline__ half_t sd3_shift_kv(float x, float sty, float mu, float rstd, float sstd, float smean, float beta) {
+    const float ad = (x - mu) * rstd * sstd + smean;
+    return (half_t)(beta * ad + (1.f - beta) * sty);
+}
+
+// the shift itself, one wave per token row of the stylised branch (rows [2*F*N, 3*F*N) of the fused [3*F*N, 3C] q|k|v buffer)
 __global__ __launch_bounds__(256) void sd3_shift_kernel(half_t* __restrict__ qkv, long ld, int F, int N, int C, int heads,
                                                         const float* __restrict__ smean, const float* __restrict__ sstd,
                                                         const float* __restrict__ mu, const float* __restrict__ rstd, float alpha,
@@ -135,14 +144,61 @@ __global__ __launch_bounds__(256) void sd3_shift_kernel(half_t* __restrict__ qkv
     half_t* row0 = qkv + r * ld;
     half_t* row1 = qkv + (FN + r) * ld;
     half_t* row2 = qkv + (2 * FN + r) * ld;
-    for (int c = lane; c < C; c += 64) row2[c] = (half_t)(gamma * (alpha * (float)row0[c] + (1.f - alpha) * (float)row2[c]));
+    for (int c = lane; c < C; c += 64) row2[c] = sd3_shift_q((float)row0[c], (float)row2[c], alpha, gamma);
     for (int t = 0; t < 2; ++t) {
         const int off = (1 + t) * C;
         for (int c = lane; c < C; c += 64) {
             const int gi = (f * 2 + t) * heads + c / d;
             const long ci = ((long)f * 2 + t) * C + c;
-            const float ad = ((float)row2[off + c] - mu[gi]) * rstd[gi] * sstd[ci] + smean[ci];
-            row2[off + c] = (half_t)(beta * ad + (1.f - beta) * (float)row1[off + c]);
+            row2[off + c] = sd3_shift_kv((float)row2[off + c], (float)row1[off + c], mu[gi], rstd[gi], sstd[ci], smean[ci], beta);
+        }
+    }
+}
+
+// The same shift on a TWO-branch buffer (content rows, then stylised rows) whose style is one frame held elsewhere: token n of every frame f reads
+// style row n of style_kv [N, >= 2C] (K | V) and the one set of column statistics smean / sstd [2C] — what F identical style frames give the
+// three-branch kernel.  mu / rstd [F][2][heads] are the stylised frames' own.  One wave per stylised row; a lane moves 16-byte pieces (8 halfs:
+// C % 8 == 0, ld % 8 == 0, ld_style % 8 == 0, 16-byte aligned bases), lanes l, l + 64, ... of a row's C / 8 pieces.
+__global__ __launch_bounds__(256) void sd3_shift_static_kernel(half_t* __restrict__ qkv, long ld, const half_t* __restrict__ style_kv,
+                                                               long ld_style, int F, int N, int C, int heads, const float* __restrict__ smean,
+                                                               const float* __restrict__ sstd, const float* __restrict__ mu,
+                                                               const float* __restrict__ rstd, float alpha, float beta, float gamma) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const long FN = (long)F * N;
+    if (r >= FN) return;
+    const long f = r / N;
+    const int d = C / heads;
+    const half_t* row0 = qkv + r * ld;
+    const half_t* sty = style_kv + (r - f * N) * ld_style;
+    half_t* row2 = qkv + (FN + r) * ld;
+    const float* mu_f = mu + f * 2 * heads;
+    const float* rstd_f = rstd + f * 2 * heads;
+    for (int c = lane * 8; c < C; c += 512) {
+        const h8 a = *reinterpret_cast<const h8*>(row0 + c), b = *reinterpret_cast<const h8*>(row2 + c);
+        h8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = sd3_shift_q((float)a[e], (float)b[e], alpha, gamma);
+        *reinterpret_cast<h8*>(row2 + c) = o;
+    }
+    for (int t = 0; t < 2; ++t) {
+        const int off = (1 + t) * C;
+        for (int c = lane * 8; c < C; c += 512) {
+            const h8 x = *reinterpret_cast<const h8*>(row2 + off + c), st = *reinterpret_cast<const h8*>(sty + t * C + c);
+            const float* sm = smean + t * C + c;
+            const float* ss = sstd + t * C + c;
+            int head = c / d, left = d - (c - head * d);          // one division per piece; `left` columns remain in this head (d % 8 may be non-zero)
+            h8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int gi = t * heads + head;
+                o[e] = sd3_shift_kv((float)x[e], (float)st[e], mu_f[gi], rstd_f[gi], ss[e], sm[e], beta);
+                if (--left == 0) {
+                    ++head;
+                    left = d;
+                }
+            }
+            *reinterpret_cast<h8*>(row2 + off + c) = o;
         }
     }
 }
@@ -474,16 +530,65 @@ int univst_sd3_adain_shift(void* qkv, int64_t ld, int F, int N, int C, int heads
     return UV_OK;
 }
 
-// the body of both entries: mx == NULL is univst_sd3_joint_attention, launch for launch; with mx the two q | k | v projections run in MX-fp8
+// in place on the fused TWO-branch [2*F*N, 3C] q | k | v buffer (branch 0 content, 1 stylised) against one style frame's K | V rows [N, 2C] (row
+// stride ld_style); ws: (2 + 2*F)*2C + 2*F*2*heads floats
+int univst_sd3_adain_shift_static(void* qkv2, int64_t ld, const void* style_kv, int64_t ld_style, int F, int N, int C, int heads, float alpha,
+                                  float beta, float gamma, void* ws, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    UV_REQUIRE(qkv2, "sd3_adain_shift_static: qkv2 is null");
+    UV_REQUIRE(style_kv, "sd3_adain_shift_static: style_kv is null");
+    UV_REQUIRE(ws, "sd3_adain_shift_static: ws is null");
+    UV_REQUIRE(F >= 1 && N >= 2, "sd3_adain_shift_static: F=%d must be positive and N=%d at least 2 (the style std is unbiased)", F, N);
+    UV_REQUIRE(heads >= 1 && C >= 8 && C % heads == 0 && C % 8 == 0, "sd3_adain_shift_static: C=%d heads=%d unsupported", C, heads);
+    UV_REQUIRE(ld % 8 == 0 && ld >= 3L * C, "sd3_adain_shift_static: ld=%ld must be a multiple of 8 and at least the 3C=%ld columns of q | k | v",
+               (long)ld, 3L * C);
+    UV_REQUIRE(ld_style % 8 == 0 && ld_style >= 2L * C,
+               "sd3_adain_shift_static: ld_style=%ld must be a multiple of 8 and at least the 2C=%ld columns of the style k | v", (long)ld_style, 2L * C);
+    UV_REQUIRE(aligned16(qkv2, style_kv), "sd3_adain_shift_static: qkv2 and style_kv must be 16-byte aligned");
+    half_t* q = (half_t*)qkv2;
+    const half_t* sty = (const half_t*)style_kv;
+    float *smean = (float*)ws, *sstd = smean + 2L * C, *cmean = sstd + 2L * C, *cstd = cmean + (long)F * 2 * C;
+    float *mu = cstd + (long)F * 2 * C, *rstd = mu + (long)F * 2 * heads;
+    const long FN = (long)F * N;
+    UV_RUN(uv_launch_colstats(sty, ld_style, 1, N, 2 * C, smean, sstd, s));                 // the one style frame's K | V: per channel over N, once
+    UV_RUN(uv_launch_colstats(q + FN * ld + C, ld, F, N, 2 * C, cmean, cstd, s));           // stylised branch K | V
+    hipLaunchKernelGGL(sd3_group_stats_kernel, dim3((unsigned)((F * 2 * heads + 127) / 128)), dim3(128), 0, s, cmean, cstd, F, N, C, heads, mu, rstd);
+    hipLaunchKernelGGL(sd3_shift_static_kernel, dim3((unsigned)((FN + 3) / 4)), dim3(256), 0, s, q, (long)ld, sty, (long)ld_style, F, N, C, heads, smean,
+                       sstd, mu, rstd, alpha, beta, gamma);
+    UV_LAUNCH_CHECK();
+    return UV_OK;
+}
+
+// static-style role of a joint attention call (univst_sd3_joint_attention_static): none = the three-branch entries
+enum { SD3_ROLE_NONE = -1, SD3_ROLE_BANK = 0, SD3_ROLE_APPLY = 1 };
+
+// the body of every entry: mx == NULL is univst_sd3_joint_attention, launch for launch; with mx the two q | k | v projections run in MX-fp8.
+// role BANK: frame 0's post-norm K | V rows are also written to style_kv; role APPLY: the batch is [content | stylised] and the shift runs against style_kv
 static int sd3_joint_attention_body(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin, int heads,
                                     int head_dim, int clip_length, int shift, float beta, float rms_eps, void* out_img, void* out_txt,
-                                    const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream, const univst_sd3_mx_weights* mx) {
+                                    const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream, const univst_sd3_mx_weights* mx,
+                                    void* style_kv = nullptr, int64_t ld_style = 0, int role = SD3_ROLE_NONE) {
     hipStream_t s = (hipStream_t)stream;
     UV_REQUIRE(w && hidden && out_img && B >= 1 && N >= 1 && heads >= 1, "sd3_joint_attention: null / empty argument");
     UV_REQUIRE(w->to_q && w->to_k && w->to_v && w->to_out, "sd3_joint_attention: to_q / to_k / to_v / to_out weights are required");
     UV_REQUIRE(clip_length >= 0 && (clip_length == 0 || B % clip_length == 0), "sd3_joint_attention: batch %d is not a whole number of %d-frame clips",
                B, clip_length);
-    UV_REQUIRE(!shift || B % 3 == 0, "sd3_joint_attention: the attention shift needs the three-branch batch");
+    const bool bank = role == SD3_ROLE_BANK, apply = role == SD3_ROLE_APPLY;
+    if (role != SD3_ROLE_NONE) {
+        UV_REQUIRE(bank || apply, "sd3_joint_attention_static: role=%d must be 0 (bank) or 1 (apply)", role);
+        UV_REQUIRE(!bank || !shift, "sd3_joint_attention_static: shift=%d must be 0 in the bank call (role 0): the style branch is never shifted", shift);
+        UV_REQUIRE(!apply || (clip_length >= 1 && B == 2 * clip_length),
+                   "sd3_joint_attention_static: B=%d must be 2 * clip_length=%d in the apply call (role 1): content frames, then stylised frames", B,
+                   clip_length);
+        UV_REQUIRE(!(apply && shift) || N >= 2, "sd3_joint_attention_static: N=%d must be at least 2 for the shift (the style std is unbiased)", N);
+        const bool need = bank || shift;
+        UV_REQUIRE(!need || style_kv, "sd3_joint_attention_static: style_kv is null (role %d%s needs the bank)", role, apply ? " with shift" : "");
+        UV_REQUIRE(!need || (ld_style % 8 == 0 && ld_style >= 2L * heads * head_dim),
+                   "sd3_joint_attention_static: ld_style=%ld must be a multiple of 8 and at least the 2C=%ld columns of the style k | v", (long)ld_style,
+                   2L * heads * head_dim);
+        UV_REQUIRE(!need || aligned16(style_kv), "sd3_joint_attention_static: style_kv must be 16-byte aligned");
+    }
+    UV_REQUIRE(apply || !shift || B % 3 == 0, "sd3_joint_attention: the attention shift needs the three-branch batch");
     UV_REQUIRE(!enc || (out_txt && Nt >= 1 && w->add_q && w->add_k && w->add_v), "sd3_joint_attention: text tokens need add_{q,k,v}_proj and out_txt");
     UV_REQUIRE(!gr || (gr->res_img && gr->gate_img && (!enc || !w->to_add_out || (gr->res_txt && gr->gate_txt))),
                "sd3_joint_attention: a gated residual needs residual and gate pointers for every projected stream");
@@ -516,7 +621,7 @@ static int sd3_joint_attention_body(const univst_sd3_attn_weights* w, const void
     const long rows_i = (long)B * N, rows_t = enc ? (long)B * Nt : 0;
     const long rows_x = sharded ? (long)2 * nbr * N : 0;               // halo row blocks behind the local frames: (first, previous) per branch
     // one stream-ordered scratch block: qkv_img [rows_i, 3C] | qkv_txt [rows_t, 3C] | o_img [rows_i, C] | o_txt [rows_t, C] | stats | index tables
-    const int Fb = B / 3;                                    // frames per branch (shift only)
+    const int Fb = apply ? B / 2 : B / 3;                    // frames per branch (shift only); the static shift's statistics fit the same n_stat
     const size_t n_half = (size_t)(rows_i + rows_t) * 4 * C + (size_t)rows_x * 3 * C;
     const int Fst = Fb > 1 ? Fb : 1;
     const size_t n_stat = shift ? (size_t)4 * Fst * 2 * C + (size_t)2 * Fst * 2 * heads : 0;
@@ -600,7 +705,15 @@ static int sd3_joint_attention_body(const univst_sd3_attn_weights* w, const void
         if (w->norm_q && w->norm_k) UV_RUN(launch_rms_pair(qkv_i, 3 * C, rows_i, heads, head_dim, 0, H(w->norm_q), C, H(w->norm_k), rms_eps, s, presc ? qscale : 1.f));
         else if (w->norm_q) UV_RUN(univst_rmsnorm_heads(qkv_i, 3 * C, rows_i, heads, head_dim, w->norm_q, rms_eps, s));
         else if (w->norm_k) UV_RUN(univst_rmsnorm_heads(qkv_i + C, 3 * C, rows_i, heads, head_dim, w->norm_k, rms_eps, s));
-        if (shift) {          // pnp_utils.py:183-194 (alpha 0.8, gamma 2.0); window test + beta come from the caller, evaluated in double
+        if (bank) {           // frame 0's post-norm K | V image rows -> the caller's bank: what the stylised branch reads from the style branch
+            const long cpn = (long)N * (2 * C / 8);
+            hipLaunchKernelGGL(sd3_copy2d_kernel, dim3((unsigned)((cpn + 255) / 256)), dim3(256), 0, s, qkv_i + C, (long)3 * C, (half_t*)style_kv,
+                               (long)ld_style, (long)N, 2 * C / 8);
+            UV_LAUNCH_CHECK();
+        }
+        if (shift && apply) {                                 // the same shift against the one style frame of the bank
+            UV_RUN(univst_sd3_adain_shift_static(qkv_i, 3 * C, style_kv, ld_style, Fb, N, C, heads, 0.8f, beta, 2.0f, st, s));
+        } else if (shift) {   // pnp_utils.py:183-194 (alpha 0.8, gamma 2.0); window test + beta come from the caller, evaluated in double
             UV_RUN(univst_sd3_adain_shift(qkv_i, 3 * C, Fb, N, C, heads, 0.8f, beta, 2.0f, st, s));
         }
         if (sharded && (rank == 0 || emu)) {          // the clip's first frame: finished K | V rows of every branch -> every rank
@@ -726,6 +839,15 @@ int univst_sd3_joint_attention_mx(const univst_sd3_attn_weights* w, const void* 
                                   const univst_sd3_gated_residual* gr, univst_comm* comm, void* stream, const univst_sd3_mx_weights* mx) {
     return sd3_joint_attention_body(w, hidden, enc, B, N, Nt, Cin, heads, head_dim, clip_length, shift, beta, rms_eps, out_img, out_txt, gr, comm, stream,
                                     mx);
+}
+
+int univst_sd3_joint_attention_static(const univst_sd3_attn_weights* w, const void* hidden, const void* enc, int B, int N, int Nt, int Cin, int heads,
+                                      int head_dim, int clip_length, int shift, float beta, float rms_eps, void* out_img, void* out_txt,
+                                      const univst_sd3_gated_residual* gr, void* stream, const univst_sd3_mx_weights* mx, void* style_kv,
+                                      int64_t ld_style, int role) {
+    UV_REQUIRE(role == SD3_ROLE_BANK || role == SD3_ROLE_APPLY, "sd3_joint_attention_static: role=%d must be 0 (bank) or 1 (apply)", role);
+    return sd3_joint_attention_body(w, hidden, enc, B, N, Nt, Cin, heads, head_dim, clip_length, shift, beta, rms_eps, out_img, out_txt, gr, nullptr,
+                                    stream, mx, style_kv, ld_style, role);
 }
 
 }  // extern "C"
